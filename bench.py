@@ -12,7 +12,7 @@ Workload = BASELINE.json's target configuration "C*": PSVO (the reference's back
 objective, BASELINE "SVO"), batch = 32 sequences per GPU, T = 200, N = 128, Dx = 2, M = 16,
 H = 32, Dh = 32.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 For N > 1 the driver launches one rank per GPU with torch.distributed.run; the batch of sequences
 is sharded (32 per rank: weak scaling) and the only collective is the gradient all-reduce.
@@ -212,6 +212,20 @@ def elbo_vs_oracle(wl, P, obs_cpu, sample_T, device, threads):
                       "with the kernels' indices (every draw verified against the oracle's CDF)" % (sample_T, T)}
 
 
+def dump_outputs(dirname, arrays, cap=4 << 20):
+    """--dump-outputs: every array as DIR/<name>.npy, float64 kept, everything else as float32.  An array of more than `cap`
+    elements is replaced by the same fixed, seeded sample of its flattened elements (sorted indices) on every run, which
+    keeps the dump below 16 MB per array."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        if a.size > cap:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def _free_port():
     import socket
     with socket.socket() as sk:
@@ -281,6 +295,10 @@ def main():
     ap.add_argument("--no-graph", dest="graph", action="store_false", help="issue every launch eagerly")
     ap.add_argument("--cpu-sample-T", type=int, default=40)
     ap.add_argument("--cpu-threads", type=int, default=16)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy: the ELBO and, "
+                         "training, the updated parameters and their gradient (flat layout), forward-only, the smoothed "
+                         "trajectories Xs (B, T, N, Dx).  Inputs are seeded: the same arguments give the same inputs")
     ap.add_argument("--plumbing-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--bsim-bwd-variant", type=int, default=-1, choices=[-1, 0, 1, 2, 3, 4],
                     help="A/B switch of the reverse backward-simulation kernel (psvo_set_tuning, include/psvo_hip.h): "
@@ -357,10 +375,13 @@ def main():
         opt.step(lr, world_size=world)
         return z
 
+    fwd_last = {}      # the smoothed trajectories of the last eager forward step (--dump-outputs)
+
     def fwd_step():
         mark_step()
         with torch.no_grad():
-            z, _ = smc.get_log_ZSMC(obs, hidden)
+            z, log = smc.get_log_ZSMC(obs, hidden)
+        fwd_last["Xs"] = log["Xs"]
         return z
 
     # The step is captured once into a hipGraph and replayed (same kernels, same buffers, fresh random
@@ -379,7 +400,7 @@ def main():
         dp.all_reduce_sum_(flat.grad)
         opt.step(lr, world_size=world)
 
-    use_graph, graph_note = (args.graph is not False), None
+    use_graph, graph_note, g_fwd = (args.graph is not False), None, None
     eager_step = train_step if args.mode == "train" else fwd_step
     step = eager_step
     if use_graph:
@@ -394,7 +415,10 @@ def main():
                     update()
                     return z
             else:
-                step = GraphedStep(lambda: fwd_step().detach(), generators=[smc.generator])
+                g_fwd = GraphedStep(lambda: (fwd_step().detach(), fwd_last["Xs"]), generators=[smc.generator])
+
+                def step():
+                    return g_fwd()[0]
         except Exception as exc:     # e.g. a kernel that cannot be captured (cooperative launches): issue eagerly
             use_graph, step = False, eager_step
             graph_note = "graph capture failed (%s: %s)" % (type(exc).__name__, str(exc)[:120])
@@ -450,6 +474,13 @@ def main():
     # recorded afterwards on the same step issued eagerly -- they cost ~1 ms per step of host time
     ticks = []
     elapsed, z = timed(step, args.steps, False, ticks)
+    if args.dump_outputs and rank == 0:
+        outs = {"elbo": torch.tensor(float(z.detach()), dtype=torch.float64)}
+        if args.mode == "train":
+            outs.update(params=flat.flat, grad=flat.grad)
+        else:
+            outs["Xs"] = g_fwd.out[1] if use_graph else fwd_last["Xs"]
+        dump_outputs(args.dump_outputs, outs)
     step_ms = sorted(ticks[i].elapsed_time(ticks[i + 1]) for i in range(len(ticks) - 1))
     elbo = float(z.detach())
     eager = train_step if args.mode == "train" else fwd_step
