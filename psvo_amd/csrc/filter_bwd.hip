@@ -1352,7 +1352,7 @@ PSVO_ENTRY(psvo_filter_backward)(
         a.scanAB = sacc + ((off + 3) & ~(size_t)3);
     }
     if (reinterpret_cast<uintptr_t>(a.scanAB) & 15) a.scanAB = nullptr;      // (a misaligned workspace: the persistent kernel)
-    a.scanPart = a.scanAB + (size_t)desc->T * desc->B * ((desc->Dx * desc->Dx + 2 * desc->Dx + 1 + 3) / 4 * 4) * desc->N;
+    a.scanPart = !a.scanAB ? nullptr : a.scanAB + (size_t)desc->T * desc->B * ((desc->Dx * desc->Dx + 2 * desc->Dx + 1 + 3) / 4 * 4) * desc->N;
     FilterBwdOut o{dsig_q1, dsig_q2, dsig_f, dsig_g, dsig0, dfsig0};
     hipStream_t s = static_cast<hipStream_t>(stream);
     switch (desc->Dx) {

@@ -1,5 +1,7 @@
 """Test-side glue between the oracle (reference layout (T, N, B, D), fp64) and the product
 (HBM layout (T, B, D, N), fp32).  Only tests import this."""
+import contextlib
+
 import torch
 
 from oracle import psvo_oracle as O
@@ -125,3 +127,26 @@ def replay_with_hip_indices(model, FLAGS, objective, obs, noise, log):
         off += int((d > 0).sum())
         worst = max(worst, float(d.max()))
     return z, ref, {"draws": draws, "off": off, "worst": worst}
+
+
+@contextlib.contextmanager
+def tuning(key, value):
+    """psvo_set_tuning(key, value) for the enclosed block, the previous value restored afterwards even when the block fails
+    (the switches are process-wide: a failing test must not leave its route to the next one)"""
+    from psvo_amd import _lib
+    lib = _lib.load()
+    old = lib.psvo_get_tuning(key)
+    assert lib.psvo_set_tuning(key, value) == _lib.PSVO_OK, (key, value)
+    try:
+        yield
+    finally:
+        assert lib.psvo_set_tuning(key, old) == _lib.PSVO_OK, (key, old)
+
+
+def kernel_names(fn):
+    """run fn() under torch.profiler and return (result, names of the device kernels it launched)"""
+    from torch.profiler import ProfilerActivity, profile
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        out = fn()
+        torch.cuda.synchronize()
+    return out, {e.name for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA}

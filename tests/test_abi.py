@@ -117,3 +117,51 @@ def test_no_register_copies_ahead_of_an_exec_restore(built_lib):
     assert not class_a, "register copies ahead of an EXEC restore in: %s" % class_a[:10]
     from psvo_amd import build
     assert build.L2_FLAGS == []          # (default allocator everywhere: nothing is exempt from the check above)
+
+
+# every psvo_set_tuning key (include/psvo_hip.h): default, accepted values, refused values
+TUNING = [
+    ("PSVO_TUNE_BSIM_BWD", -1, [-1, 0, 1, 2, 3, 4], [-2, 5, 100]),
+    ("PSVO_TUNE_ROWS_BWD", 0, [0, 16, 64], [-1, 1, 8, 32, 128]),
+    ("PSVO_TUNE_L2_SPLIT", 0, [0, 1], [-1, 2]),
+    ("PSVO_TUNE_SKEW", 0, [0, 1, 50, 100, 1000], [-1, 1001]),
+    ("PSVO_TUNE_WGRAD2", 0, [0, 2, 3], [-1, 1, 4]),
+    ("PSVO_TUNE_FILTER_BWD", 1, [0, 1, 2], [-1, 3]),
+]
+
+
+@pytest.mark.parametrize("name,default,good,bad", TUNING, ids=[t[0] for t in TUNING])
+def test_tuning_round_trip_and_refusals(built_lib, name, default, good, bad):
+    """set / get round trip of every accepted value; a refused value returns PSVO_ERR_INVALID and leaves the setting as it
+    was; tests.helpers.tuning restores the previous value even when its block raises"""
+    from psvo_amd import _lib
+    from tests import helpers as Hh
+    lib = _lib.load()
+    key = getattr(_lib, name)
+    assert lib.psvo_get_tuning(key) == default
+    try:
+        for v in good:
+            assert lib.psvo_set_tuning(key, v) == _lib.PSVO_OK, v
+            assert lib.psvo_get_tuning(key) == v
+            for w in bad:
+                assert lib.psvo_set_tuning(key, w) == _lib.PSVO_ERR_INVALID, w
+                assert lib.psvo_get_tuning(key) == v
+    finally:
+        assert lib.psvo_set_tuning(key, default) == _lib.PSVO_OK
+    with pytest.raises(RuntimeError):
+        with Hh.tuning(key, good[-1]):
+            assert lib.psvo_get_tuning(key) == good[-1]
+            raise RuntimeError("inside")
+    assert lib.psvo_get_tuning(key) == default
+    with pytest.raises(AssertionError):
+        with Hh.tuning(key, bad[0]):
+            pass
+    assert lib.psvo_get_tuning(key) == default
+
+
+def test_tuning_unknown_keys_are_refused(built_lib):
+    from psvo_amd import _lib
+    lib = _lib.load()
+    for key in (0, 7, -1, 1 << 20):
+        assert lib.psvo_set_tuning(key, 0) == _lib.PSVO_ERR_INVALID, key
+        assert lib.psvo_get_tuning(key) == _lib.PSVO_ERR_INVALID, key

@@ -181,3 +181,54 @@ def test_psvowr_collapsed_ancestry_gradients(built_lib):
         hip_pass()
     smc.check_exchange()
     _check_grads(model, P)
+
+
+@pytest.mark.timeout(900)
+@pytest.mark.parametrize("wl", ["C3", "C4", "C5"])
+def test_full_size_training_step(built_lib, wl):
+    """One forward + reverse pass at the BASELINE sizes, where the oracle is too slow (C3: T = 400, Dx = 3; C4: N = 256;
+    C5: T = 1000, N = 512, Dx = 4): every gradient of the objective is finite and non-zero somewhere.  At C4 a second eager
+    pass gives the same bit pattern (no float atomics across waves at N <= 256)."""
+    import os
+    import sys
+    from psvo_amd.optim import FlatParams
+    from tests.test_gpu_parity import _pairs
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    obj, B, T, N, Dx, Dy, M, H, Dh = bench.WORKLOADS[wl]
+    FLAGS, model, smc = bench.build_objective(bench.WORKLOADS[wl], "cuda")
+    _, obs = O.fhn_synthetic(B, T, seed=2)
+    obs = obs.float().cuda()
+    flat = FlatParams(model)
+
+    def step():
+        flat.zero_grad()
+        smc.generator = torch.Generator(device="cuda").manual_seed(0)
+        z, _ = smc.get_log_ZSMC(obs, None)
+        z.backward()
+        torch.cuda.synchronize()
+        return z.detach().clone(), flat.grad.clone()
+    z, g = step()
+    assert torch.isfinite(z), float(z)
+    assert torch.isfinite(g).all()
+    # which parameters the objective depends on at all: the fp64 oracle's autograd on the same wiring at a tiny size (in the
+    # bootstrap wiring with two proposals, for instance, the X0 encoder feeds nothing and its gradient is exactly zero)
+    tiny = (obj, 1, 4, 8, Dx, Dy, 4, H, 8)
+    F1, m1, _ = bench.build_objective(tiny, "cuda")
+    n1 = O.make_noise(Hh.oracle_flags(F1, obj), 1, 4, seed=3)
+    o1 = torch.randn(1, 4, Dy, generator=torch.Generator().manual_seed(4), dtype=torch.float64)
+    _, r1 = Hh.run_oracle(m1, F1, obj, o1, n1)
+    _, P1 = _oracle_grads(m1, F1, obj, o1, n1, _teacher(r1, obj))
+    used = {name for name, _, ref in _pairs(m1, P1) if ref.grad is not None and float(ref.grad.abs().max()) > 0}
+    pairs = _pairs(model, model.export_reference_layout(torch.float64))
+    assert used and used <= {name for name, _, _ in pairs}
+    for name, p, _ in pairs:
+        gmax = 0.0 if p.grad is None else float(p.grad.abs().max())
+        if name in used:
+            assert gmax > 0, "%s: gradient is zero everywhere" % name
+        else:
+            assert gmax == 0, "%s: the objective does not depend on it, yet its gradient is %g" % (name, gmax)
+    if wl == "C4":
+        z2, g2 = step()
+        assert torch.equal(z2, z)
+        assert torch.equal(g2, g), "flat gradient differs between two eager passes in %d entries" % int((g2 != g).sum())

@@ -116,6 +116,18 @@ def test_training_step_gradients_are_bit_reproducible(built_lib):
     _reproducible(TP._setup("AESMC", 2, 8, 256, 1, 4, 1, 32, False, True, seed=13))
 
 
+
+def test_affine_scan_gradients_are_bit_reproducible(built_lib):
+    """The affine-scan reverse filter (fbs_* kernels) sums in a fixed order: C2's route (AESMC, bootstrap, N = 64: the scan
+    with its 16-step ring, wrapped over T = 40) and the scan with an upstream gradient from the backward simulation (PSVO,
+    N = 128, forced by PSVO_TUNE_FILTER_BWD = 2), eagerly and replayed from the captured hipGraph."""
+    from psvo_amd import _lib
+    from tests import helpers as Hh
+    from tests import test_gpu_parity as TP
+    _reproducible(TP._setup("AESMC", 4, 40, 64, 1, 2, 1, 32, True, True, seed=14))
+    with Hh.tuning(_lib.PSVO_TUNE_FILTER_BWD, 2):
+        _reproducible(TP._setup("PSVO", 2, 30, 128, 8, 2, 1, 32, True, True, seed=15))
+
 def _reproducible(setup):
     import torch
     from tests import helpers as Hh
