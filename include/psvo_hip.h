@@ -115,6 +115,17 @@ const char* psvo_status_string(int status);
  *   per cent of the kernel's estimate of its pair-phase length (default 0 = all workgroups start together: measured, it
  *   changes nothing -- profiles/r03_bsim_bwd_C5_ab.md -- and is kept as an A/B knob). */
 #define PSVO_TUNE_SKEW 4
+/*   PSVO_TUNE_DETERMINISTIC: 0 (default) = the kernels as measured; 1 = fixed-order sums on the reverse paths, so that two runs
+ *   of the same inputs give bit-identical outputs.  Like every key it is process-global and takes effect when an operation is
+ *   LAUNCHED (or captured into a hipGraph: a replay runs the kernels chosen at capture time).  Under 1, psvo_filter_backward and
+ *   psvo_filter_backward_cov run the persistent reverse filter with fixed-order scatter copies where the default adds with float
+ *   atomics in arrival order (N > 256; the cov filter at N > 64); every other route they take already sums in a fixed order.
+ *   The backward simulations with state-dependent scales need a workspace under 1: psvo_bsim_backward_cov_ws /
+ *   psvo_bsimwr_backward_cov_ws with det_ws = psvo_bsim_cov_det_ws_floats(B, N, M, Dx, Dy) floats (per-workgroup slices of
+ *   every cross-workgroup sum, folded in workgroup order after each step: one launch per step in both modes); without it
+ *   (det_ws NULL, or the entry points without _ws) they return PSVO_ERR_INVALID under 1.  With 0, det_ws is ignored.
+ *   Values other than 0 and 1: PSVO_ERR_INVALID. */
+#define PSVO_TUNE_DETERMINISTIC 8
 int psvo_set_tuning(int key, int value);          /* PSVO_OK or PSVO_ERR_INVALID */
 int psvo_get_tuning(int key);
 
@@ -240,7 +251,8 @@ int psvo_bsim_forward_cov(const psvo_desc* desc,
  *            ACCUMULATED with float atomics -- the caller zero-fills them: dFm, dFs (T,B,Dx,N), dlogW (T,B,N), dlse (T,B)
  *            (-> psvo_filter_backward_cov as dFm_ext, dFs_ext, dlogW_ext and added to dlse), dbmu2, dbsig2 (T,B,Dx),
  *            dminit, dsinit, dimean, disig (B,Dx), dsigc_f, dsigc_q1inv (Dx), dsigc_g (Dy).
- *  The summation order of the atomics is not fixed: results are reproducible to rounding, not bit for bit. */
+ *  The summation order of the atomics is not fixed: results are reproducible to rounding, not bit for bit, unless
+ *  PSVO_TUNE_DETERMINISTIC is 1 (psvo_bsim_backward_cov_ws: fixed-order slices and folds instead of the atomics). */
 int psvo_bsim_backward_cov(const psvo_desc* desc,
                            const float* Fm, const float* Fs, const float* logW, const float* lse,
                            const psvo_mlp* f, const psvo_mlp* g, const psvo_mlp* q1_inv,
@@ -269,6 +281,23 @@ int psvo_bsim_backward_cov(const psvo_desc* desc,
  * atomics into zero-filled dFm, dFs, dlogW, dlse, dbmu2, dbsig2, dminit, dsinit, dimean, disig, dsigc_*); the q1_inv rows
  * dmu1 / dmu1s pair with the inputs bwXanc[t+1]; dXs (T,B,Dx,N): zero-filled workspace (d loss / d bwX).
  * ------------------------------------------------------------------------------------------- */
+long long psvo_bsim_cov_det_ws_floats(int B, int N, int M, int Dx, int Dy);
+int psvo_bsim_backward_cov_ws(const psvo_desc* desc,
+                              const float* Fm, const float* Fs, const float* logW, const float* lse,
+                              const psvo_mlp* f, const psvo_mlp* g, const psvo_mlp* q1_inv,
+                              const float* sigc_f, const float* sigc_g, const float* sigc_q1inv,
+                              const float* bmu2, const float* bsig2,
+                              const float* minit, const float* sinit, const float* imean, const float* isig,
+                              const float* obs, const float* eps_b, const float* bwX, const int32_t* sel,
+                              const float* lam_all, const float* om_all, const float* mu1_all, const float* s1_all,
+                              const float* dscore,
+                              float* xt, float* dFt, float* dFts, float* dGt, float* dGts, float* dmu1, float* dmu1s,
+                              float* dFm, float* dFs, float* dlogW, float* dlse,
+                              float* dbmu2, float* dbsig2,
+                              float* dminit, float* dsinit, float* dimean, float* disig,
+                              float* dsigc_f, float* dsigc_g, float* dsigc_q1inv,
+                              float* det_ws, void* stream);
+
 int psvo_bsimwr_forward_cov(const psvo_desc* desc,
                             const float* Fm, const float* Fs, const float* logW, const float* lse,
                             const psvo_mlp* f, const psvo_mlp* g, const psvo_mlp* q1_inv,
@@ -297,6 +326,23 @@ int psvo_bsimwr_backward_cov(const psvo_desc* desc,
                              float* dminit, float* dsinit, float* dimean, float* disig,
                              float* dsigc_f, float* dsigc_g, float* dsigc_q1inv,
                              float* dXs, void* stream);
+int psvo_bsimwr_backward_cov_ws(const psvo_desc* desc,
+                                const float* Fm, const float* Fs, const float* logW, const float* lse,
+                                const psvo_mlp* f, const psvo_mlp* g, const psvo_mlp* q1_inv,
+                                const float* sigc_f, const float* sigc_g, const float* sigc_q1inv,
+                                const float* bmu2, const float* bsig2,
+                                const float* minit, const float* sinit, const float* imean, const float* isig,
+                                const float* obs, const float* eps_b,
+                                const float* bwXanc, const float* bwW, const float* lseW,
+                                const int32_t* sel, const int32_t* anc,
+                                const float* lam_all, const float* om_all, const float* mu1_all, const float* s1_all,
+                                const float* dlseW,
+                                float* xt, float* dFt, float* dFts, float* dGt, float* dGts, float* dmu1, float* dmu1s,
+                                float* dFm, float* dFs, float* dlogW, float* dlse,
+                                float* dbmu2, float* dbsig2,
+                                float* dminit, float* dsinit, float* dimean, float* disig,
+                                float* dsigc_f, float* dsigc_g, float* dsigc_q1inv,
+                                float* dXs, float* det_ws, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Backward simulation with proposal.  Replaces PSVO.backward_simulation_w_proposal

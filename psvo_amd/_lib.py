@@ -19,6 +19,7 @@ PSVO_TUNE_L2_SPLIT = 3
 PSVO_TUNE_SKEW = 4
 PSVO_TUNE_WGRAD2 = 5
 PSVO_TUNE_FILTER_BWD = 6
+PSVO_TUNE_DETERMINISTIC = 8
 
 
 class PsvoHipError(RuntimeError):
@@ -54,6 +55,9 @@ SIGNATURES = {
     "psvo_bsim_backward_cov": (ctypes.c_int, [_DESC] + [_P] * 4 + [_MLP, _MLP, _MLP] + [_P] * 38 + [_P]),
     "psvo_bsimwr_forward_cov": (ctypes.c_int, [_DESC] + [_P] * 4 + [_MLP, _MLP, _MLP] + [_P] * 26 + [_P]),
     "psvo_bsimwr_backward_cov": (ctypes.c_int, [_DESC] + [_P] * 4 + [_MLP, _MLP, _MLP] + [_P] * 42 + [_P]),
+    "psvo_bsim_cov_det_ws_floats": (ctypes.c_longlong, [ctypes.c_int] * 5),
+    "psvo_bsim_backward_cov_ws": (ctypes.c_int, [_DESC] + [_P] * 4 + [_MLP, _MLP, _MLP] + [_P] * 39 + [_P]),
+    "psvo_bsimwr_backward_cov_ws": (ctypes.c_int, [_DESC] + [_P] * 4 + [_MLP, _MLP, _MLP] + [_P] * 43 + [_P]),
     "psvo_mlp_wgrad_blocks": (ctypes.c_int, [ctypes.c_longlong]),
     "psvo_mlp_wgrad": (ctypes.c_int, [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       _P, _P, _MLP, _P, _P, ctypes.c_int, _P]),
@@ -131,6 +135,9 @@ def load():
         v = os.environ.get("PSVO_L2_SPLIT")              # A/B: two-layer backward-simulation kernels with the half-split chains
         if v is not None and lib.psvo_set_tuning(PSVO_TUNE_L2_SPLIT, int(v)) != PSVO_OK:
             raise PsvoHipError("PSVO_L2_SPLIT=%s is not a valid psvo_set_tuning value" % v)
+        v = os.environ.get("PSVO_DETERMINISTIC")         # 1: fixed-order sums on the reverse paths (bit-reproducible gradients)
+        if v is not None and lib.psvo_set_tuning(PSVO_TUNE_DETERMINISTIC, int(v)) != PSVO_OK:
+            raise PsvoHipError("PSVO_DETERMINISTIC=%s is not a valid psvo_set_tuning value" % v)
         _lib = lib
     return _lib
 

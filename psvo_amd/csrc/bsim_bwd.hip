@@ -41,7 +41,7 @@ int set_rows_bwd_rb(int v);     // rows_mlp.hip
 int get_rows_bwd_rb();
 }  // namespace psvo
 
-namespace psvo { int g_tune_l2_split = 0; int g_tune_skew_pct = 0; int g_tune_filter_bwd_scan = 1; }
+namespace psvo { int g_tune_l2_split = 0; int g_tune_skew_pct = 0; int g_tune_filter_bwd_scan = 1; int g_tune_deterministic = 0; }
 
 namespace psvo { extern int g_tune_wgrad2; }
 
@@ -63,6 +63,10 @@ extern "C" int psvo_set_tuning(int key, int value) {
         psvo::g_tune_l2_split = value;
         return PSVO_OK;
     }
+    if (key == PSVO_TUNE_DETERMINISTIC && (value == 0 || value == 1)) {
+        psvo::g_tune_deterministic = value;
+        return PSVO_OK;
+    }
     if (key == PSVO_TUNE_BSIM_BWD && value >= -1 && value <= 4) {
         g_bsim_bwd_variant = value;
         return PSVO_OK;
@@ -76,6 +80,7 @@ extern "C" int psvo_get_tuning(int key) {
     if (key == PSVO_TUNE_SKEW) return psvo::g_tune_skew_pct;
     if (key == PSVO_TUNE_WGRAD2) return psvo::g_tune_wgrad2;
     if (key == PSVO_TUNE_FILTER_BWD) return psvo::g_tune_filter_bwd_scan;
+    if (key == PSVO_TUNE_DETERMINISTIC) return psvo::g_tune_deterministic;
     return key == PSVO_TUNE_BSIM_BWD ? g_bsim_bwd_variant : PSVO_ERR_INVALID;
 }
 

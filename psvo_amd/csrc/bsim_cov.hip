@@ -21,6 +21,7 @@
 #include "common.h"
 
 namespace psvo {
+extern int g_tune_deterministic;   // PSVO_TUNE_DETERMINISTIC (psvo_set_tuning, bsim_bwd.hip): the reverse entry points refuse it
 namespace covb {
 
 __device__ __forceinline__ float head_sigma(float con, float raw) {
@@ -476,6 +477,14 @@ struct BwdArgs {
     const float *bwXanc, *bwW, *lseW, *dlseW;   // (T,B,Dx,N), (T,B,N), (T,B), (T,B)
     const int32_t* anc;                     // (T,B,N)
     float* dXs;                             // (T,B,Dx,N) d loss / d bwX (zero-filled by the caller; float atomics)
+    // DET (PSVO_TUNE_DETERMINISTIC): one launch per step in both modes; every cross-wave and cross-workgroup sum of the step is
+    // written as a slice and folded in a fixed order by bsim_cov_det_fold (psvo_bsim_cov_det_ws_floats sizes the four arrays)
+    float* jpart;                           // (B, nblk, 2Dx+1, N) per-j sums of the step, per workgroup
+    float* cpart;                           // (B, nblk, 4Dx) the step's sums over the workgroup's chains (cacc)
+    float* spart;                           // (B, nblk, waves, 2Dx+Dy) d sigma_con sums of the launch, per wave
+    float* dxc;                             // (B, Dx, N) d loss / d bwX of each chain for the next launch (PSVOwR: before
+                                            //  the gather into the ancestors)
+    int nblk, nwv;                          // workgroups per sequence, waves per workgroup
 };
 
 // WR = false: PSVO, persistent over t = 0 .. T-1 with d loss / d bwX[t] carried in registers.  WR = true: PSVOwR, one launch
@@ -483,7 +492,12 @@ struct BwdArgs {
 //   W = logsumexp_m(omega_raw) - phi_s - log M   =>   d lam_m = d g_m = -d q_m = aw p_m,   d phi_m = aw (p_m - [m == s]),
 // and the chain's x_{t+1} is the RESAMPLED state bwXanc[t+1][n] = bwX[t+1][anc], so its gradient is scatter-added into the
 // ancestor chain's d bwX[t+1] (HBM float atomics; the next launch reads it).
-template <int DX, int DY, int H, int M, bool WR>
+// DET = true (PSVO_TUNE_DETERMINISTIC): one launch per step in BOTH modes (PSVO carries d bwX of each chain through a.dxc), and
+// no float atomics: the per-j sums go to one LDS copy per wave (each (q, j) has one writer lane per wave and step: plain
+// stores), the per-chain sums to one LDS slot per chain, both added in wave / chain order into per-workgroup slices (a.jpart,
+// a.cpart), d sigma_con per wave into a.spart; bsim_cov_det_fold adds the slices in workgroup order after every launch, and
+// PSVOwR's scatter into the ancestor chains is a gather in child order (bsim_cov_det_gather) instead of HBM atomics.
+template <int DX, int DY, int H, int M, bool WR, bool DET = false>
 __global__ void __launch_bounds__(256) bsim_cov_bwd_kernel(const BwdArgs a) {
     using MQ = MlpLds<DX, H, 2 * DX, 1>;
     using MG = MlpLds<DX, H, 2 * DY, 1>;
@@ -510,9 +524,11 @@ __global__ void __launch_bounds__(256) bsim_cov_bwd_kernel(const BwdArgs a) {
     float* wg = wf + MQ::kSize;
     float* wqi = wg + MG::kSize;
     float* tile = wqi + MQ::kSize;            // [NP][TS]   tile of forward step t - 1
-    float* jacc = tile + NP * TS;             // [NJ][NP]   per-j sums of the step over the workgroup
-    float* xch = jacc + NJ * NP;              // [4][64][NI] items of each wave: x~ (DX), lam2, d lam
+    const int nwv = NTB >> 6, wave = tid >> 6;
+    float* jacc = tile + NP * TS;             // [NJ][NP]   per-j sums of the step over the workgroup (DET: [nwv][NJ][NP])
+    float* xch = jacc + (DET ? nwv : 1) * NJ * NP;   // [4][64][NI] items of each wave: x~ (DX), lam2, d lam
     float* cacc = xch + 4 * 64 * NI;             // [4 * DX]   per-step sums over the workgroup's chains: d bmu2, d bsig2 | t = T-1: d minit, d sinit | t = 0: d imean, d isig
+    float* cch = cacc + 4 * DX;               // DET: [cpb][4 * DX] the same per chain
 
     MQ::load(wf, a.f, tid, NTB);
     MG::load(wg, a.g, tid, NTB);
@@ -536,7 +552,12 @@ __global__ void __launch_bounds__(256) bsim_cov_bwd_kernel(const BwdArgs a) {
     }
     float aw = (!WR && valid) ? a.dscore[(size_t)b * N + n] : 0.f;
     const float kap = sqrtf(0.5f * kLog2e);
-    const int t_lo = WR ? a.t_lo : 0, t_hi = WR ? a.t_hi : T - 1;
+    const int t_lo = (WR || DET) ? a.t_lo : 0, t_hi = (WR || DET) ? a.t_hi : T - 1;
+    // plain (non-atomic) adds of the per-chain sums: lead lanes only, one slot per chain (DET), else the LDS atomics
+    auto cadd = [&](int k, float v) {
+        if constexpr (DET) cch[cl * 4 * DX + k] = v;
+        else atomicAdd(&cacc[k], v);
+    };
 
     float acc_f[DX], acc_q[DX], acc_g[DY];    // sums of d sigma over this lane's rows of the f / q1inv / g heads
 #pragma unroll
@@ -555,6 +576,12 @@ __global__ void __launch_bounds__(256) bsim_cov_bwd_kernel(const BwdArgs a) {
             aw = valid ? a.dlseW[tb] * exp2_fast((a.bwW[tb * N + n] - a.lseW[tb]) * kLog2e) : 0.f;
 #pragma unroll
             for (int d = 0; d < DX; ++d) dX[d] = a.dXs[(tb * DX + d) * N + n];
+        } else if constexpr (DET) {     // (PSVO, one launch per step: the previous launch left this chain's d bwX[t])
+#pragma unroll
+            for (int d = 0; d < DX; ++d) dX[d] = tzero ? 0.f : a.dxc[((size_t)b * DX + d) * N + n];
+        }
+        if constexpr (DET) {
+            for (int i = tid; i < cpb * 4 * DX; i += NTB) cch[i] = 0.f;
         }
 
         // ---- stage the tile of forward step t - 1, zero the step's accumulators ---------------------------------------------
@@ -572,7 +599,9 @@ __global__ void __launch_bounds__(256) bsim_cov_bwd_kernel(const BwdArgs a) {
                 raw[2 * DX] = a.logW[pb * N + jc];
                 TL::put(tile, j, N, raw, l);
             }
-            for (int i = tid; i < NJ * NP; i += NTB) jacc[i] = 0.f;
+            if constexpr (!DET) {       // (DET: every wave stores every (q, j) of its copy once per step)
+                for (int i = tid; i < NJ * NP; i += NTB) jacc[i] = 0.f;
+            }
         }
         if (tid < 4 * DX) cacc[tid] = 0.f;
         __syncthreads();
@@ -744,7 +773,11 @@ __global__ void __launch_bounds__(256) bsim_cov_bwd_kernel(const BwdArgs a) {
                     float v = ja[q];
                     v += xor_lane<16>(v);
                     v += xor_lane<32>(v);
-                    if (lane < 16) atomicAdd(&jacc[q * NP + j], v);
+                    if constexpr (DET) {
+                        if (lane < 16) jacc[(wave * NJ + q) * NP + j] = v;
+                    } else {
+                        if (lane < 16) atomicAdd(&jacc[q * NP + j], v);
+                    }
                 }
             }
             // item sums over the row's 16 lanes; item i of the row is owned by the row's lane i, which keeps the sum
@@ -776,8 +809,8 @@ __global__ void __launch_bounds__(256) bsim_cov_bwd_kernel(const BwdArgs a) {
                 dmi = group_sum<M>(g1);
                 dsi = group_sum<M>((valid ? dlam : 0.f) * (z * z - 1.f) * iis);
                 if (lead) {
-                    atomicAdd(&cacc[2 * DX + d], dmi);
-                    atomicAdd(&cacc[3 * DX + d], dsi);
+                    cadd(2 * DX + d, dmi);
+                    cadd(3 * DX + d, dsi);
                 }
             }
         }
@@ -803,8 +836,8 @@ __global__ void __launch_bounds__(256) bsim_cov_bwd_kernel(const BwdArgs a) {
                     acc_q[d] += ds1;
                     a.dmu1[(tb * DX + d) * N + n] = dq[d];
                     a.dmu1s[(tb * DX + d) * N + n] = dq[DX + d];
-                    atomicAdd(&cacc[d], dA * i2[d]);
-                    atomicAdd(&cacc[DX + d], -di2 * i2[d] * i2[d]);
+                    cadd(d, dA * i2[d]);
+                    cadd(DX + d, -di2 * i2[d] * i2[d]);
                 }
             }
             float dxq[DX];
@@ -813,7 +846,12 @@ __global__ void __launch_bounds__(256) bsim_cov_bwd_kernel(const BwdArgs a) {
             MQ::template bwd_input<kRolled>(wqi, xp, dq, dxq);      // (the same in the chain's M lanes)
 #pragma unroll
             for (int d = 0; d < DX; ++d) dX[d] = group_sum<M>(dxp[d]) + dxq[d];
-            if constexpr (WR) {     // x_{t+1} = bwX[t+1][anc]: the gradient goes to the ancestor chain
+            if constexpr (DET) {    // (the next launch reads it; PSVOwR: bsim_cov_det_gather adds it into the ancestor)
+                if (lead) {
+#pragma unroll
+                    for (int d = 0; d < DX; ++d) a.dxc[((size_t)b * DX + d) * N + n] = dX[d];
+                }
+            } else if constexpr (WR) {     // x_{t+1} = bwX[t+1][anc]: the gradient goes to the ancestor chain
                 if (lead) {
                     const int an = a.anc[(tb + B) * N + n];
 #pragma unroll
@@ -826,13 +864,29 @@ __global__ void __launch_bounds__(256) bsim_cov_bwd_kernel(const BwdArgs a) {
                 if (lead) {
                     a.dmu1[(tb * DX + d) * N + n] = 0.f;
                     a.dmu1s[(tb * DX + d) * N + n] = 0.f;
-                    atomicAdd(&cacc[d], dmu[d]);
-                    atomicAdd(&cacc[DX + d], dc[d]);
+                    cadd(d, dmu[d]);
+                    cadd(DX + d, dc[d]);
                 }
             }
         }
         __syncthreads();
         // ---- flush the step's workgroup sums ---------------------------------------------------------------------------------------
+        if constexpr (DET) {        // slices of this workgroup: waves / chains added in order (bsim_cov_det_fold adds the slices)
+            const size_t blk = (size_t)b * a.nblk + blockIdx.x;
+            if (!tzero) {
+                for (int i = tid; i < NJ * N; i += NTB) {
+                    const int q = i / N, j = i - q * N;
+                    float v = 0.f;
+                    for (int w = 0; w < nwv; ++w) v += jacc[(w * NJ + q) * NP + j];
+                    a.jpart[blk * NJ * N + i] = v;
+                }
+            }
+            if (tid < 4 * DX) {
+                float v = 0.f;
+                for (int c = 0; c < cpb; ++c) v += cch[c * 4 * DX + tid];
+                a.cpart[blk * 4 * DX + tid] = v;
+            }
+        } else {
         if (!tzero) {
             const size_t pb = tb - B;
             for (int i = tid; i < NJ * N; i += NTB) {
@@ -861,9 +915,28 @@ __global__ void __launch_bounds__(256) bsim_cov_bwd_kernel(const BwdArgs a) {
                 atomicAdd(&a.disig[b * DX + tid], cacc[3 * DX + tid]);
             }
         }
+        }   // (!DET)
         __syncthreads();
     }
     // ---- d sigma_con of the three heads ------------------------------------------------------------------------------------------------
+    if constexpr (DET) {
+        constexpr int NS = 2 * DX + DY;
+        float* sp = a.spart + (((size_t)b * a.nblk + blockIdx.x) * nwv + wave) * NS;
+#pragma unroll
+        for (int d = 0; d < DX; ++d) {
+            const float sf = wave_sum(acc_f[d]), sq = wave_sum(acc_q[d]);
+            if (lane == 0) {
+                sp[d] = sf;
+                sp[DX + d] = sq;
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < DY; ++e) {
+            const float sg = wave_sum(acc_g[e]);
+            if (lane == 0) sp[2 * DX + e] = sg;
+        }
+        return;
+    }
 #pragma unroll
     for (int d = 0; d < DX; ++d) {
         const float sf = wave_sum(acc_f[d]), sq = wave_sum(acc_q[d]);
@@ -916,6 +989,74 @@ static int launch_fwd_wr(const FwdArgs& a0, float* lseW, hipStream_t stream) {
     return launch_status();
 }
 
+// DET, PSVOwR: d bwX[t+1] of every chain = the sum, over its children in child order, of the values the launch of step t left in
+// a.dxc (the reverse of bwXanc[t+1][n] = bwX[t+1][anc[t+1][n]]; the default scatters with HBM float atomics).  One workgroup per
+// sequence, the ancestor row and the children's values staged in LDS.
+__global__ void __launch_bounds__(256) bsim_cov_det_gather(const BwdArgs a, int t, int DX) {
+    extern __shared__ __attribute__((aligned(16))) float sg[];      // [DX][N] children's values | [N] ancestors
+    const int b = blockIdx.x, N = a.N, tid = threadIdx.x;
+    int* sanc = reinterpret_cast<int*>(sg + DX * N);
+    const size_t tb1 = (size_t)(t + 1) * a.B + b;
+    for (int i = tid; i < DX * N; i += 256) sg[i] = a.dxc[(size_t)b * DX * N + i];
+    for (int n = tid; n < N; n += 256) sanc[n] = a.anc[tb1 * N + n];
+    __syncthreads();
+    for (int i = tid; i < DX * N; i += 256) {
+        const int d = i / N, an = i - d * N;
+        float v = 0.f;
+        for (int n = 0; n < N; ++n) v += (sanc[n] == an) ? sg[d * N + n] : 0.f;
+        a.dXs[(tb1 * DX + d) * N + an] += v;
+    }
+}
+
+// DET: adds the slices the launch of step t wrote, in workgroup order (then wave order for d sigma_con): d Fm / d Fs / d logW
+// and d lse of forward step t - 1, the hoisted-row sums of step t, and (workgroup of sequence 0) d sigma_con
+template <int DX, int DY>
+__global__ void __launch_bounds__(256) bsim_cov_det_fold(const BwdArgs a, int t) {
+    constexpr int NJ = 2 * DX + 1, NS = 2 * DX + DY;
+    __shared__ float red[4];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int B = a.B, T = a.T, N = a.N, nblk = a.nblk;
+    const size_t tb = (size_t)t * B + b;
+    if (t > 0) {
+        const size_t pb = tb - B;
+        float part = 0.f;
+        for (int i = tid; i < NJ * N; i += 256) {
+            const int q = i / N, j = i - q * N;
+            float v = 0.f;
+            for (int k = 0; k < nblk; ++k) v += a.jpart[((size_t)b * nblk + k) * NJ * N + i];
+            if (q < DX) {
+                a.dFm[(pb * DX + q) * N + j] += v;
+            } else if (q < 2 * DX) {
+                a.dFs[(pb * DX + (q - DX)) * N + j] += v;
+            } else {
+                a.dlogW[pb * N + j] += v;
+                part += v;
+            }
+        }
+        part = wave_sum(part);
+        if (lane == 0) red[wave] = part;
+        __syncthreads();
+        if (tid == 0) a.dlse[pb] += -(red[0] + red[1] + red[2] + red[3]);    // (the tile holds logW - lse)
+    }
+    if (tid < 4 * DX) {
+        float v = 0.f;
+        for (int k = 0; k < nblk; ++k) v += a.cpart[((size_t)b * nblk + k) * 4 * DX + tid];
+        const int s = tid / DX, d = tid - s * DX;
+        const bool last = (t == T - 1);
+        if (s == 0) (last ? a.dminit[b * DX + d] : a.dbmu2[tb * DX + d]) += v;
+        else if (s == 1) (last ? a.dsinit[b * DX + d] : a.dbsig2[tb * DX + d]) += v;
+        else if (t == 0) (s == 2 ? a.dimean : a.disig)[b * DX + d] += v;
+    }
+    if (b == 0 && tid < NS) {
+        float v = 0.f;
+        const int slices = B * nblk * a.nwv;
+        for (int k = 0; k < slices; ++k) v += a.spart[(size_t)k * NS + tid];
+        if (tid < DX) a.dsc_f[tid] += v;
+        else if (tid < 2 * DX) a.dsc_q1inv[tid - DX] += v;
+        else a.dsc_g[tid - 2 * DX] += v;
+    }
+}
+
 template <int DX, int DY, int H, int M>
 static int launch_bwd(const BwdArgs& a, hipStream_t stream) {
     using MQ = MlpLds<DX, H, 2 * DX, 1>;
@@ -928,7 +1069,23 @@ static int launch_bwd(const BwdArgs& a, hipStream_t stream) {
                                         4 * 64 * (DX + 2) + 4 * DX + 16);
     dim3 grid((a.N + cpb - 1) / cpb, a.B);
     clear_hip_error();
-    if (a.t_lo < 0) {       // PSVO: persistent over all steps
+    if (a.jpart) {          // PSVO_TUNE_DETERMINISTIC: one launch per step, then the gather (PSVOwR) and the fold of the step
+        BwdArgs w = a;
+        w.nblk = (int)grid.x;
+        w.nwv = NTB / 64;
+        const size_t ldsd = lds + sizeof(float) * ((size_t)(w.nwv - 1) * NP * (2 * DX + 1) + (size_t)cpb * 4 * DX);
+        if (ldsd > 160 * 1024) return PSVO_ERR_UNSUPPORTED;
+        const bool wr = a.t_lo >= 0;
+        for (int t = 0; t < a.T; ++t) {
+            w.t_lo = w.t_hi = t;
+            if (wr) hipLaunchKernelGGL((bsim_cov_bwd_kernel<DX, DY, H, M, true, true>), grid, dim3(NTB), ldsd, stream, w);
+            else hipLaunchKernelGGL((bsim_cov_bwd_kernel<DX, DY, H, M, false, true>), grid, dim3(NTB), ldsd, stream, w);
+            if (wr && t + 1 < a.T)
+                hipLaunchKernelGGL(bsim_cov_det_gather, dim3(a.B), dim3(256), sizeof(float) * (size_t)(DX + 1) * a.N, stream, w,
+                                   t, DX);
+            hipLaunchKernelGGL((bsim_cov_det_fold<DX, DY>), dim3(a.B), dim3(256), 0, stream, w, t);
+        }
+    } else if (a.t_lo < 0) {       // PSVO: persistent over all steps
         hipLaunchKernelGGL((bsim_cov_bwd_kernel<DX, DY, H, M, false>), grid, dim3(NTB), lds, stream, a);
     } else {                // PSVOwR: one launch per time step, 0 .. T-1
         BwdArgs w = a;
@@ -976,8 +1133,39 @@ static int launch_bwd(const BwdArgs& a, hipStream_t stream) {
 
 static bool desc_ok(const psvo_desc* d) { return d && d->B > 0 && d->T >= 2 && d->N > 0 && d->M > 0; }
 
+// workgroups per sequence and waves per workgroup of bsim_cov_bwd_kernel (launch_bwd)
+static void bwd_geometry(int N, int M, int& nblk, int& nwv, int& cpb) {
+    int NTB = ((N * M + 63) / 64) * 64;
+    if (NTB > 256) NTB = 256;
+    cpb = NTB / M;
+    nblk = (N + cpb - 1) / cpb;
+    nwv = NTB / 64;
+}
+
+// the four DET arrays of BwdArgs, carved from the caller's workspace (psvo_bsim_cov_det_ws_floats); null when the mode is off
+static void set_det(BwdArgs& a, const psvo_desc* d, float* ws) {
+    a.jpart = a.cpart = a.spart = a.dxc = nullptr;
+    a.nblk = a.nwv = 0;
+    if (!g_tune_deterministic) return;
+    int nblk, nwv, cpb;
+    bwd_geometry(d->N, d->M, nblk, nwv, cpb);
+    const size_t s = (size_t)d->B * nblk;
+    a.jpart = ws;
+    a.cpart = a.jpart + s * (2 * d->Dx + 1) * d->N;
+    a.spart = a.cpart + s * 4 * d->Dx;
+    a.dxc = a.spart + s * nwv * (2 * d->Dx + d->Dy);
+}
+
 }  // namespace covb
 }  // namespace psvo
+
+extern "C" long long psvo_bsim_cov_det_ws_floats(int B, int N, int M, int Dx, int Dy) {
+    if (B <= 0 || N <= 0 || M <= 0 || Dx <= 0 || Dy <= 0) return 0;
+    int nblk, nwv, cpb;
+    psvo::covb::bwd_geometry(N, M, nblk, nwv, cpb);
+    const long long s = (long long)B * nblk;
+    return s * (2 * Dx + 1) * N + s * 4 * Dx + s * nwv * (2 * Dx + Dy) + (long long)B * Dx * N;
+}
 
 extern "C" int psvo_bsim_forward_cov(const psvo_desc* desc, const float* Fm, const float* Fs, const float* logW,
                                      const float* lse, const psvo_mlp* f, const psvo_mlp* g, const psvo_mlp* q1_inv,
@@ -1013,7 +1201,7 @@ extern "C" int psvo_bsim_forward_cov(const psvo_desc* desc, const float* Fm, con
     PSVO_COVB_DISPATCH(launch_fwd, a, s);
 }
 
-extern "C" int psvo_bsim_backward_cov(
+extern "C" int psvo_bsim_backward_cov_ws(
     const psvo_desc* desc, const float* Fm, const float* Fs, const float* logW, const float* lse, const psvo_mlp* f,
     const psvo_mlp* g, const psvo_mlp* q1_inv, const float* sigc_f, const float* sigc_g, const float* sigc_q1inv,
     const float* bmu2, const float* bsig2, const float* minit, const float* sinit, const float* imean, const float* isig,
@@ -1021,12 +1209,13 @@ extern "C" int psvo_bsim_backward_cov(
     const float* mu1_all, const float* s1_all, const float* dscore, float* xt, float* dFt, float* dFts, float* dGt,
     float* dGts, float* dmu1, float* dmu1s, float* dFm, float* dFs, float* dlogW, float* dlse, float* dbmu2, float* dbsig2,
     float* dminit, float* dsinit, float* dimean, float* disig, float* dsigc_f, float* dsigc_g, float* dsigc_q1inv,
-    void* stream) {
+    float* det_ws, void* stream) {
     using namespace psvo;
     using namespace psvo::covb;
     if (!desc) return PSVO_ERR_INVALID;
     if (desc->layers > 1 || desc->layers < 0) return PSVO_ERR_UNSUPPORTED;
     if (!desc_ok(desc)) return PSVO_ERR_INVALID;
+    if (g_tune_deterministic && !det_ws) return PSVO_ERR_INVALID;      // (the fixed-order route needs its workspace)
     if (!Fm || !Fs || !logW || !lse || !f || !g || !q1_inv || !sigc_f || !sigc_g || !sigc_q1inv || !bmu2 || !bsig2 || !minit ||
         !sinit || !imean || !isig || !obs || !eps_b || !bwX || !sel || !lam_all || !om_all || !mu1_all || !s1_all || !dscore ||
         !xt || !dFt || !dFts || !dGt || !dGts || !dmu1 || !dmu1s || !dFm || !dFs || !dlogW || !dlse || !dbmu2 || !dbsig2 ||
@@ -1047,8 +1236,24 @@ extern "C" int psvo_bsim_backward_cov(
     a.dsc_f = dsigc_f; a.dsc_g = dsigc_g; a.dsc_q1inv = dsigc_q1inv;
     a.t_lo = a.t_hi = -1;       // persistent over all steps
     a.bwXanc = a.bwW = a.lseW = a.dlseW = nullptr; a.anc = nullptr; a.dXs = nullptr;
+    set_det(a, desc, det_ws);
     hipStream_t s = static_cast<hipStream_t>(stream);
     PSVO_COVB_DISPATCH(launch_bwd, a, s);
+}
+
+extern "C" int psvo_bsim_backward_cov(
+    const psvo_desc* desc, const float* Fm, const float* Fs, const float* logW, const float* lse, const psvo_mlp* f,
+    const psvo_mlp* g, const psvo_mlp* q1_inv, const float* sigc_f, const float* sigc_g, const float* sigc_q1inv,
+    const float* bmu2, const float* bsig2, const float* minit, const float* sinit, const float* imean, const float* isig,
+    const float* obs, const float* eps_b, const float* bwX, const int32_t* sel, const float* lam_all, const float* om_all,
+    const float* mu1_all, const float* s1_all, const float* dscore, float* xt, float* dFt, float* dFts, float* dGt,
+    float* dGts, float* dmu1, float* dmu1s, float* dFm, float* dFs, float* dlogW, float* dlse, float* dbmu2, float* dbsig2,
+    float* dminit, float* dsinit, float* dimean, float* disig, float* dsigc_f, float* dsigc_g, float* dsigc_q1inv,
+    void* stream) {
+    return psvo_bsim_backward_cov_ws(desc, Fm, Fs, logW, lse, f, g, q1_inv, sigc_f, sigc_g, sigc_q1inv, bmu2, bsig2, minit,
+                                     sinit, imean, isig, obs, eps_b, bwX, sel, lam_all, om_all, mu1_all, s1_all, dscore, xt,
+                                     dFt, dFts, dGt, dGts, dmu1, dmu1s, dFm, dFs, dlogW, dlse, dbmu2, dbsig2, dminit, dsinit,
+                                     dimean, disig, dsigc_f, dsigc_g, dsigc_q1inv, nullptr, stream);
 }
 
 /* PSVOwR with state-dependent scales: see include/psvo_hip.h */
@@ -1085,7 +1290,7 @@ extern "C" int psvo_bsimwr_forward_cov(
     PSVO_COVB_DISPATCH(launch_fwd_wr, a, lseW, s);
 }
 
-extern "C" int psvo_bsimwr_backward_cov(
+extern "C" int psvo_bsimwr_backward_cov_ws(
     const psvo_desc* desc, const float* Fm, const float* Fs, const float* logW, const float* lse, const psvo_mlp* f,
     const psvo_mlp* g, const psvo_mlp* q1_inv, const float* sigc_f, const float* sigc_g, const float* sigc_q1inv,
     const float* bmu2, const float* bsig2, const float* minit, const float* sinit, const float* imean, const float* isig,
@@ -1093,12 +1298,13 @@ extern "C" int psvo_bsimwr_backward_cov(
     const int32_t* anc, const float* lam_all, const float* om_all, const float* mu1_all, const float* s1_all,
     const float* dlseW, float* xt, float* dFt, float* dFts, float* dGt, float* dGts, float* dmu1, float* dmu1s, float* dFm,
     float* dFs, float* dlogW, float* dlse, float* dbmu2, float* dbsig2, float* dminit, float* dsinit, float* dimean,
-    float* disig, float* dsigc_f, float* dsigc_g, float* dsigc_q1inv, float* dXs, void* stream) {
+    float* disig, float* dsigc_f, float* dsigc_g, float* dsigc_q1inv, float* dXs, float* det_ws, void* stream) {
     using namespace psvo;
     using namespace psvo::covb;
     if (!desc) return PSVO_ERR_INVALID;
     if (desc->layers > 1 || desc->layers < 0) return PSVO_ERR_UNSUPPORTED;
     if (!desc_ok(desc)) return PSVO_ERR_INVALID;
+    if (g_tune_deterministic && !det_ws) return PSVO_ERR_INVALID;      // (the fixed-order route needs its workspace)
     if (!Fm || !Fs || !logW || !lse || !f || !g || !q1_inv || !sigc_f || !sigc_g || !sigc_q1inv || !bmu2 || !bsig2 || !minit ||
         !sinit || !imean || !isig || !obs || !eps_b || !bwXanc || !bwW || !lseW || !sel || !anc || !lam_all || !om_all ||
         !mu1_all || !s1_all || !dlseW || !xt || !dFt || !dFts || !dGt || !dGts || !dmu1 || !dmu1s || !dFm || !dFs || !dlogW ||
@@ -1119,6 +1325,22 @@ extern "C" int psvo_bsimwr_backward_cov(
     a.dsc_f = dsigc_f; a.dsc_g = dsigc_g; a.dsc_q1inv = dsigc_q1inv;
     a.t_lo = a.t_hi = 0;        // (>= 0: one launch per time step)
     a.bwXanc = bwXanc; a.bwW = bwW; a.lseW = lseW; a.dlseW = dlseW; a.anc = anc; a.dXs = dXs;
+    set_det(a, desc, det_ws);
     hipStream_t s = static_cast<hipStream_t>(stream);
     PSVO_COVB_DISPATCH(launch_bwd, a, s);
+}
+
+extern "C" int psvo_bsimwr_backward_cov(
+    const psvo_desc* desc, const float* Fm, const float* Fs, const float* logW, const float* lse, const psvo_mlp* f,
+    const psvo_mlp* g, const psvo_mlp* q1_inv, const float* sigc_f, const float* sigc_g, const float* sigc_q1inv,
+    const float* bmu2, const float* bsig2, const float* minit, const float* sinit, const float* imean, const float* isig,
+    const float* obs, const float* eps_b, const float* bwXanc, const float* bwW, const float* lseW, const int32_t* sel,
+    const int32_t* anc, const float* lam_all, const float* om_all, const float* mu1_all, const float* s1_all,
+    const float* dlseW, float* xt, float* dFt, float* dFts, float* dGt, float* dGts, float* dmu1, float* dmu1s, float* dFm,
+    float* dFs, float* dlogW, float* dlse, float* dbmu2, float* dbsig2, float* dminit, float* dsinit, float* dimean,
+    float* disig, float* dsigc_f, float* dsigc_g, float* dsigc_q1inv, float* dXs, void* stream) {
+    return psvo_bsimwr_backward_cov_ws(desc, Fm, Fs, logW, lse, f, g, q1_inv, sigc_f, sigc_g, sigc_q1inv, bmu2, bsig2, minit,
+                                       sinit, imean, isig, obs, eps_b, bwXanc, bwW, lseW, sel, anc, lam_all, om_all, mu1_all,
+                                       s1_all, dlseW, xt, dFt, dFts, dGt, dGts, dmu1, dmu1s, dFm, dFs, dlogW, dlse, dbmu2, dbsig2,
+                                       dminit, dsinit, dimean, disig, dsigc_f, dsigc_g, dsigc_q1inv, dXs, nullptr, stream);
 }

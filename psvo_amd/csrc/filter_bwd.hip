@@ -16,6 +16,7 @@
 #include "common.h"
 
 namespace psvo {
+extern int g_tune_deterministic;   // PSVO_TUNE_DETERMINISTIC (psvo_set_tuning, bsim_bwd.hip)
 inline namespace PSVO_LNS {   // l1 / l2: hidden layers of the per-particle MLPs (common.h)
 PSVO_TIMERS_DEFINE(filter_bwd)
 
@@ -38,6 +39,7 @@ struct FilterBwdArgs {
     int wave_copies;         // filter_bwd_kernel: one scatter-target copy per wave (set by the launcher when LDS has room)
     float* scanAB;           // affine-scan path: (T,B,N,REC) records (16-byte aligned); part: (T,B,NACC) per-step partial sums
     float* scanPart;
+    int det_copies;          // filter_bwd_kernel<.., DET = true>: scatter-target copies, 1 .. waves (see there)
 };
 
 template <int DX, int DY>
@@ -90,13 +92,20 @@ __device__ __forceinline__ float block_sum(float v, float* red, int wave, int la
     return s;
 }
 
-template <int DX, int DY, int H, int MAXT>
+// DET (PSVO_TUNE_DETERMINISTIC, where the launcher finds no room for a double-buffered copy per wave: N > 256): ONE buffer of
+// c = a.det_copies copies (1 <= c <= waves, the most that fit).  Every lane reads and clears its own entries of all copies (in
+// copy order), a barrier, then wave w adds into copy w % c in phase w / c, ceil(waves / c) phases separated by barriers --
+// inside a phase each copy has one adding wave (lane order), across phases the phase order: every sum has a fixed order.  At
+// N = 512, Dx = 4 without bootstrap eight double-buffered copies of both arrays would take 256 KB of LDS; one buffer of all
+// eight takes 128 KB (+ the weights: 131 KB at H = 32, one phase).
+template <int DX, int DY, int H, int MAXT, bool DET = false>
 __global__ void __launch_bounds__(MAXT) filter_bwd_kernel(const FilterBwdArgs a) {
     using MQ = MlpLds<DX, H, DX, PSVO_L>;
     using MG = MlpLds<DX, H, DY, PSVO_L>;
     using AC = FAcc<DX, DY>;
     // one wave per SIMD (<= 256 lanes): let the compiler keep the loop-invariant MLP weights in VGPRs
     constexpr bool kRolled = (MAXT > 256) || (MlpLds<DX, H, DX, PSVO_L>::kSize + MlpLds<DX, H, DY, PSVO_L>::kSize > 330);
+    constexpr int NBUF = DET ? 1 : 2;     // scatter-target buffers (double-buffered over t; DET: one, behind a barrier)
     extern __shared__ __attribute__((aligned(16))) float smem[];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -110,17 +119,17 @@ __global__ void __launch_bounds__(MAXT) filter_bwd_kernel(const FilterBwdArgs a)
     float* wg = wf + MQ::kSize;
     // scatter targets: one copy per wave when the launcher found room for them (a.wave_copies; see filter_bwd_lpp_kernel) --
     // fixed summation order --, else one shared copy and float atomics across the waves
-    const int nc = a.wave_copies ? nw : 1;
+    const int nc = DET ? a.det_copies : (a.wave_copies ? nw : 1);
     const int CP = DX * NT;               // floats of one copy
     float* accP = wg + MG::kSize;         // [2][nc][DX][NT] scatter targets d P1 (+ d Fm when bootstrap)
-    float* accF = accP + 2 * nc * CP;     // [2][nc][DX][NT] d Fm (allocated only when !bootstrap)
-    float* red = accF + (a.bootstrap ? 0 : 2 * nc * CP);      // 16 floats
+    float* accF = accP + NBUF * nc * CP;  // [2][nc][DX][NT] d Fm (allocated only when !bootstrap)
+    float* red = accF + (a.bootstrap ? 0 : NBUF * nc * CP);   // 16 floats
 
     MQ::load(wq1, a.q1, tid, NT);
     if (!a.bootstrap) MQ::load(wf, a.f, tid, NT);
     MG::load(wg, a.g, tid, NT);
     const float* wfm = a.bootstrap ? wq1 : wf;
-    for (int i = tid; i < (a.bootstrap ? 2 : 4) * nc * CP; i += NT) accP[i] = 0.f;
+    for (int i = tid; i < (a.bootstrap ? 1 : 2) * NBUF * nc * CP; i += NT) accP[i] = 0.f;
 
     float sq1[DX], sq2[DX], sfv[DX], s0[DX], fs0[DX], isg[DY];
 #pragma unroll
@@ -213,11 +222,11 @@ __global__ void __launch_bounds__(MAXT) filter_bwd_kernel(const FilterBwdArgs a)
         float inc[AC::kSet];  // this step's contribution to the per-dimension sums (set chosen below)
 #pragma unroll
         for (int i = 0; i < AC::kSet; ++i) inc[i] = 0.f;
-        const int mine = a.wave_copies ? wave * CP : 0;
-        float* curP = accP + (t & 1) * nc * CP;                     // all copies of this step's targets
-        float* nxtP = accP + ((t + 1) & 1) * nc * CP + mine;        // this wave's copy (or the shared one) for step t - 1
-        float* curF = accF + (t & 1) * nc * CP;
-        float* nxtF = accF + ((t + 1) & 1) * nc * CP + mine;
+        const int mine = DET ? (wave % nc) * CP : a.wave_copies ? wave * CP : 0;
+        float* curP = accP + (DET ? 0 : (t & 1) * nc * CP);                     // all copies of this step's targets
+        float* nxtP = accP + (DET ? 0 : ((t + 1) & 1) * nc * CP) + mine;        // this wave's copy (or the shared one) for t - 1
+        float* curF = accF + (DET ? 0 : (t & 1) * nc * CP);
+        float* nxtF = accF + (DET ? 0 : ((t + 1) & 1) * nc * CP) + mine;
 
         // ---- forward quantities of this step (prefetched) ----------------------------------------------
         float n_x[DX], n_e[DX], n_m2[DX], n_y[DY], n_mean1[DX], n_fmean[DX], n_dfm[DX], n_sc[4];
@@ -378,7 +387,23 @@ __global__ void __launch_bounds__(MAXT) filter_bwd_kernel(const FilterBwdArgs a)
         SEC(6);   // PoG gradient, block sums of d mu2
         // ---- gather backward: scatter-add into the parents (SVO.py:255-257) ------------------------------
         if (!first) {
-            if (valid) {
+            if constexpr (DET) {
+                __syncthreads();      // (one buffer: every lane has read and cleared this step's targets)
+                for (int ph = 0; ph < (nw + nc - 1) / nc; ++ph) {
+                    if (ph > 0) __syncthreads();
+                    if (valid && wave / nc == ph) {
+#pragma unroll
+                        for (int d = 0; d < DX; ++d) {
+                            if (a.bootstrap) {
+                                atomicAdd(&nxtP[d * NT + anc], dmean1[d] + dfmean[d]);
+                            } else {
+                                atomicAdd(&nxtP[d * NT + anc], dmean1[d]);
+                                atomicAdd(&nxtF[d * NT + anc], dfmean[d]);
+                            }
+                        }
+                    }
+                }
+            } else if (valid) {
 #pragma unroll
                 for (int d = 0; d < DX; ++d) {
                     if (a.bootstrap) {
@@ -1259,6 +1284,17 @@ static int launch_filter_bwd(const FilterBwdArgs& a, const FilterBwdOut& o, hipS
         }
     }
     if (lpp) {
+    } else if (g_tune_deterministic && !aw.wave_copies) {
+        // fixed-order scatter (see filter_bwd_kernel): the most copies, down to one, whose single buffer fits
+        const size_t arrays1 = a.bootstrap ? 1 : 2;
+        auto lds_det = [&](int nc) { return sizeof(float) * (2 * MQ::kSize + MG::kSize + arrays1 * nc * DX * (size_t)NT + 16); };
+        int nc = NT / 64;
+        while (nc > 1 && lds_det(nc) > 150 * 1024) --nc;
+        aw.det_copies = nc;
+        if (NT <= 256)
+            hipLaunchKernelGGL((filter_bwd_kernel<DX, DY, H, 256, true>), dim3(a.B), dim3(NT), lds_det(nc), stream, aw);
+        else
+            hipLaunchKernelGGL((filter_bwd_kernel<DX, DY, H, 512, true>), dim3(a.B), dim3(NT), lds_det(nc), stream, aw);
     } else if (NT <= 256)
         hipLaunchKernelGGL((filter_bwd_kernel<DX, DY, H, 256>), dim3(a.B), dim3(NT), lds, stream, aw);
     else
@@ -1338,6 +1374,7 @@ PSVO_ENTRY(psvo_filter_backward)(
 
     FilterBwdArgs a;
     a.wave_copies = 0;
+    a.det_copies = 1;
     a.B = desc->B; a.T = desc->T; a.N = desc->N;
     a.resample = desc->resample; a.two_q = desc->two_q; a.bootstrap = desc->bootstrap; a.emission = desc->emission;
     a.q1 = *q1; a.f = desc->bootstrap ? *q1 : *f; a.g = *g;

@@ -20,6 +20,7 @@
 #include "common.h"
 
 namespace psvo {
+extern int g_tune_deterministic;   // PSVO_TUNE_DETERMINISTIC (psvo_set_tuning, bsim_bwd.hip)
 namespace cov {
 
 // sigma_con + 0.1 * (exp(raw) + 1e-6)
@@ -296,6 +297,7 @@ struct BwdArgs {
     float* ds2_rows;   // (T,B,Dx,N) per-particle d sig2
     float* scanRec;    // affine-scan path: float4 planes [(t, b), float4 index, particle] of the step records; scanPart (T,B,2Dx+Dy)
     float* scanPart;
+    int det_copies;    // filter_cov_bwd_kernel<.., DET = true>: scatter-target copies, 1 .. waves (filter_bwd.hip)
 };
 
 __device__ __forceinline__ float block_sum(float v, float* red, int wave, int lane, int nw) {
@@ -309,11 +311,14 @@ __device__ __forceinline__ float block_sum(float v, float* red, int wave, int la
     return s;
 }
 
-template <int DX, int DY, int H, int MAXT>
+// DET (PSVO_TUNE_DETERMINISTIC): the scatter targets in ONE buffer of a.det_copies copies instead of one double-buffered shared
+// copy, added into in phases -- the scheme of psvo::l1::filter_bwd_kernel<.., DET = true> (filter_bwd.hip), which see.
+template <int DX, int DY, int H, int MAXT, bool DET = false>
 __global__ void __launch_bounds__(MAXT) filter_cov_bwd_kernel(const BwdArgs a) {
     using MQ = MlpLds<DX, H, 2 * DX, 1>;
     using MG = MlpLds<DX, H, 2 * DY, 1>;
     constexpr bool kRolled = (MAXT > 256) || (2 * MQ::kSize + MG::kSize > 330);
+    constexpr int NBUF = DET ? 1 : 2;
     extern __shared__ __attribute__((aligned(16))) float smem[];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -327,15 +332,16 @@ __global__ void __launch_bounds__(MAXT) filter_cov_bwd_kernel(const BwdArgs a) {
     float* wf = wq1 + MQ::kSize;
     float* wg = wf + MQ::kSize;
     const int CP = 2 * DX * NT;            // one buffer of scatter targets: d mean | d scale
+    const int nc = DET ? a.det_copies : 1;
     float* accP = wg + MG::kSize;          // [2][2 DX][NT] into MLP_q1's outputs (+ MLP_f's == the same when bootstrap)
-    float* accF = accP + 2 * CP;           // [2][2 DX][NT] into MLP_f's outputs (only when !bootstrap)
-    float* red = accF + (boot ? 0 : 2 * CP);   // 16
+    float* accF = accP + NBUF * nc * CP;   // [2][2 DX][NT] into MLP_f's outputs (only when !bootstrap)
+    float* red = accF + (boot ? 0 : NBUF * nc * CP);   // 16
 
     MQ::load(wq1, a.q1, tid, NT);
     if (!boot) MQ::load(wf, a.f, tid, NT);
     MG::load(wg, a.g, tid, NT);
     const float* wfm = boot ? wq1 : wf;
-    for (int i = tid; i < (boot ? 2 : 4) * CP; i += NT) accP[i] = 0.f;
+    for (int i = tid; i < (boot ? 1 : 2) * NBUF * nc * CP; i += NT) accP[i] = 0.f;
 
     float cq1[DX], cf[DX], cg[DY];
 #pragma unroll
@@ -407,10 +413,11 @@ __global__ void __launch_bounds__(MAXT) filter_cov_bwd_kernel(const BwdArgs a) {
     for (int t = T - 1; t >= 0; --t) {
         const size_t tb = (size_t)t * B + b;
         const bool first = (t == 0);
-        float* curP = accP + (t & 1) * CP;
-        float* nxtP = accP + ((t + 1) & 1) * CP;
-        float* curF = accF + (t & 1) * CP;
-        float* nxtF = accF + ((t + 1) & 1) * CP;
+        const int mine = DET ? (wave % nc) * CP : 0;
+        float* curP = accP + (DET ? 0 : (t & 1) * CP);
+        float* nxtP = accP + (DET ? 0 : ((t + 1) & 1) * CP) + mine;
+        float* curF = accF + (DET ? 0 : (t & 1) * CP);
+        float* nxtF = accF + (DET ? 0 : ((t + 1) & 1) * CP) + mine;
 
         float n_x[DX], n_e[DX], n_m2[DX], n_s2[DX], n_y[DY], n_pm[DX], n_ps[DX], n_qm[DX], n_qs[DX], n_ofs[DX], n_ops[DX],
             n_dfm[DX], n_dfs[DX], n_sc[4];
@@ -506,6 +513,14 @@ __global__ void __launch_bounds__(MAXT) filter_cov_bwd_kernel(const BwdArgs a) {
             float dpm = curP[d * NT + tid], dps = curP[(DX + d) * NT + tid];
             curP[d * NT + tid] = 0.f;
             curP[(DX + d) * NT + tid] = 0.f;
+            if constexpr (DET) {      // the other copies, in copy order
+                for (int w = 1; w < nc; ++w) {
+                    dpm += curP[w * CP + d * NT + tid];
+                    dps += curP[w * CP + (DX + d) * NT + tid];
+                    curP[w * CP + d * NT + tid] = 0.f;
+                    curP[w * CP + (DX + d) * NT + tid] = 0.f;
+                }
+            }
             if (boot) {
                 dpm += c_dfm[d];
                 dps += c_dfs[d];
@@ -515,9 +530,18 @@ __global__ void __launch_bounds__(MAXT) filter_cov_bwd_kernel(const BwdArgs a) {
                 dPo[d] = dpm;
                 dPo[DX + d] = dps * (c_ofs[d] - cq1[d] - 1e-7f);       // 0.1 exp(raw) of this particle's own head
             } else {
-                float dfm = curF[d * NT + tid] + c_dfm[d], dfs = curF[(DX + d) * NT + tid] + c_dfs[d];
+                float sfm = curF[d * NT + tid], sfs = curF[(DX + d) * NT + tid];
                 curF[d * NT + tid] = 0.f;
                 curF[(DX + d) * NT + tid] = 0.f;
+                if constexpr (DET) {
+                    for (int w = 1; w < nc; ++w) {
+                        sfm += curF[w * CP + d * NT + tid];
+                        sfs += curF[w * CP + (DX + d) * NT + tid];
+                        curF[w * CP + d * NT + tid] = 0.f;
+                        curF[w * CP + (DX + d) * NT + tid] = 0.f;
+                    }
+                }
+                float dfm = sfm + c_dfm[d], dfs = sfs + c_dfs[d];
                 if (!valid) dpm = dps = dfm = dfs = 0.f;
                 acc_q[d] += dps;
                 acc_f[d] += dfs;
@@ -563,20 +587,29 @@ __global__ void __launch_bounds__(MAXT) filter_cov_bwd_kernel(const BwdArgs a) {
             }
         }
         // ---- gather backward: scatter-add into the parents (SVO.py:255-257) ---------------------------------------------------
-        if (!first) {
-            if (valid) {
+        auto scatter = [&]() {
 #pragma unroll
-                for (int d = 0; d < DX; ++d) {
-                    if (boot) {
-                        atomicAdd(&nxtP[d * NT + anc], dmean1[d] + dfmean[d]);
-                        atomicAdd(&nxtP[(DX + d) * NT + anc], ds1[d] + dfsc[d]);
-                    } else {
-                        atomicAdd(&nxtP[d * NT + anc], dmean1[d]);
-                        atomicAdd(&nxtP[(DX + d) * NT + anc], ds1[d]);
-                        atomicAdd(&nxtF[d * NT + anc], dfmean[d]);
-                        atomicAdd(&nxtF[(DX + d) * NT + anc], dfsc[d]);
-                    }
+            for (int d = 0; d < DX; ++d) {
+                if (boot) {
+                    atomicAdd(&nxtP[d * NT + anc], dmean1[d] + dfmean[d]);
+                    atomicAdd(&nxtP[(DX + d) * NT + anc], ds1[d] + dfsc[d]);
+                } else {
+                    atomicAdd(&nxtP[d * NT + anc], dmean1[d]);
+                    atomicAdd(&nxtP[(DX + d) * NT + anc], ds1[d]);
+                    atomicAdd(&nxtF[d * NT + anc], dfmean[d]);
+                    atomicAdd(&nxtF[(DX + d) * NT + anc], dfsc[d]);
                 }
+            }
+        };
+        if (!first) {
+            if constexpr (DET) {
+                __syncthreads();      // (one buffer: every lane has read and cleared this step's targets)
+                for (int ph = 0; ph < (nw + nc - 1) / nc; ++ph) {
+                    if (ph > 0) __syncthreads();
+                    if (valid && wave / nc == ph) scatter();
+                }
+            } else if (valid) {
+                scatter();
             }
         } else {
 #pragma unroll
@@ -1072,7 +1105,19 @@ static int launch_bwd(const BwdArgs& a, const BwdOut& o, hipStream_t stream) {
     clear_hip_error();
     // the affine scan wherever it applies (this path is one stream: the reverse filter is always on its critical path)
     if (g_tune_filter_bwd_scan && a.bootstrap && a.resample && a.scanRec && a.scanPart) launch_bwd_scan<DX, DY, H>(a, stream);
-    else if (NT <= 256) hipLaunchKernelGGL((filter_cov_bwd_kernel<DX, DY, H, 256>), dim3(a.B), dim3(NT), lds, stream, a);
+    else if (g_tune_deterministic && NT > 64) {
+        // fixed-order scatter (one wave, N <= 64, adds in lane order already): the most copies whose single buffer fits
+        const size_t arrays1 = a.bootstrap ? 1 : 2;
+        auto lds_det = [&](int nc) { return sizeof(float) * (2 * MQ::kSize + MG::kSize + arrays1 * nc * 2 * DX * (size_t)NT + 16); };
+        int nc = NT / 64;
+        while (nc > 1 && lds_det(nc) > 150 * 1024) --nc;
+        BwdArgs ad = a;
+        ad.det_copies = nc;
+        if (NT <= 256)
+            hipLaunchKernelGGL((filter_cov_bwd_kernel<DX, DY, H, 256, true>), dim3(a.B), dim3(NT), lds_det(nc), stream, ad);
+        else
+            hipLaunchKernelGGL((filter_cov_bwd_kernel<DX, DY, H, 512, true>), dim3(a.B), dim3(NT), lds_det(nc), stream, ad);
+    } else if (NT <= 256) hipLaunchKernelGGL((filter_cov_bwd_kernel<DX, DY, H, 256>), dim3(a.B), dim3(NT), lds, stream, a);
     else hipLaunchKernelGGL((filter_cov_bwd_kernel<DX, DY, H, 512>), dim3(a.B), dim3(NT), lds, stream, a);
     if (a.two_q) {
         const long long rows = (long long)a.T * a.B * DX;
@@ -1173,6 +1218,7 @@ extern "C" int psvo_filter_backward_cov(
     if (desc->resample && !idx) return PSVO_ERR_INVALID;
     if (desc->N > 512) return PSVO_ERR_UNSUPPORTED;
     BwdArgs a;
+    a.det_copies = 1;
     a.B = desc->B; a.T = desc->T; a.N = desc->N;
     a.resample = desc->resample; a.two_q = desc->two_q; a.bootstrap = desc->bootstrap; a.emission = desc->emission;
     a.q1 = *q1; a.f = desc->bootstrap ? *q1 : *f; a.g = *g;

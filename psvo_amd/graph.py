@@ -11,6 +11,8 @@ import os
 
 import torch
 
+from . import ops
+
 
 class GraphedStep(object):
     # Replays the host may have in flight.  A replay costs the launching thread ~20 us; a small step (the reference notebook's
@@ -38,12 +40,17 @@ class GraphedStep(object):
         for g in generators:
             if g is not None:
                 self.graph.register_generator_state(g)
+        # the kernels are chosen when captured: the deterministic mode (ops.deterministic) of the capture is the graph's
+        self.deterministic = ops.deterministic()
         with torch.cuda.graph(self.graph):
             self.out = fn()
         self._mark = None
         self._n = 0
 
     def __call__(self):
+        if ops.deterministic() != self.deterministic:
+            raise RuntimeError("GraphedStep was captured with the deterministic mode %s and is replayed with it %s: capture "
+                               "the step again" % (("off", "on")[self.deterministic], ("off", "on")[not self.deterministic]))
         self.graph.replay()
         self._n += 1
         if self.PERIOD > 0 and self._n % self.PERIOD == 0:

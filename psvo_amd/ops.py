@@ -4,11 +4,50 @@ All tensors use the library's particle-minor HBM layout (include/psvo_hip.h):
 particles (T, B, Dx, N), log-weights (T, B, N), features (T, B, D), bsim noise (T, B, Dx, N, M).
 PyTorch is only the allocator / stream provider here.
 """
+import contextlib
 import ctypes
+import threading
 
 import torch
 
 from . import _lib
+
+
+# Deterministic mode (PSVO_TUNE_DETERMINISTIC, include/psvo_hip.h): on when the library switch is 1 (psvo_set_tuning or the
+# PSVO_DETERMINISTIC environment variable) or when torch.use_deterministic_algorithms(True) is in force.  Under torch's flag
+# the reverse wrappers hold the switch at 1 around their own launch (counted, so that launches from several threads share
+# one setting and the last one out restores it).
+def deterministic():
+    """True when the reverse launches issued now take their fixed-order routes"""
+    return (torch.are_deterministic_algorithms_enabled()
+            or _lib.load().psvo_get_tuning(_lib.PSVO_TUNE_DETERMINISTIC) == 1)
+
+
+_FIXED_LOCK = threading.Lock()
+_FIXED_HOLD = [0, False]        # _fixed_order blocks open under torch's flag; whether they set the switch
+
+
+@contextlib.contextmanager
+def _fixed_order():
+    """the enclosed launch runs under PSVO_TUNE_DETERMINISTIC = 1 when torch's flag is on; yields whether the switch is 1"""
+    lib = _lib.load()
+    key = _lib.PSVO_TUNE_DETERMINISTIC
+    if not torch.are_deterministic_algorithms_enabled():
+        yield lib.psvo_get_tuning(key) == 1
+        return
+    with _FIXED_LOCK:
+        if _FIXED_HOLD[0] == 0 and lib.psvo_get_tuning(key) == 0:
+            _lib.check(lib.psvo_set_tuning(key, 1), "psvo_set_tuning")
+            _FIXED_HOLD[1] = True
+        _FIXED_HOLD[0] += 1
+    try:
+        yield True
+    finally:
+        with _FIXED_LOCK:
+            _FIXED_HOLD[0] -= 1
+            if _FIXED_HOLD[0] == 0 and _FIXED_HOLD[1]:
+                _FIXED_HOLD[1] = False
+                lib.psvo_set_tuning(key, 0)
 
 
 # Optional side stream for the native launches of one wrapper call.  Buffers the wrapper allocates come from
@@ -413,14 +452,15 @@ def filter_backward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0,
     sacc = z(lib.psvo_filter_ws_floats(B, T, N, Dx, Dy))
     nparts = 1 if (dFm is not None or dlogW is not None) else 0
     _mark("psvo_filter_backward", 0)
-    st = lib.psvo_filter_backward(
-        ctypes.byref(desc), ctypes.byref(q1s), ctypes.byref(fs) if fs is not None else None, ctypes.byref(gs),
-        _ptr(sig_q1), _ptr(sig_q2), _ptr(sig_f), _ptr(sig_g), _ptr(mu2), _ptr(m0), _ptr(sig0), _ptr(fm0), _ptr(fsig0),
-        _ptr(obs), _ptr(eps), _ptr(filt["X"]), _ptr(filt["Fm"]), _ptr(filt["P1"]), _ptr(filt["logW"]),
-        _ptr(filt["lse"]), _ptr(filt["idx"]), _ptr(dlse), nparts, _ptr(dFm), _ptr(dlogW),
-        _ptr(out["dP"]), _ptr(out["dF"]), _ptr(out["dG"]), _ptr(out["dmu2"]), _ptr(out["dm0"]), _ptr(out["dfm0"]),
-        _ptr(out["dsig_q1"]), _ptr(out["dsig_q2"]), _ptr(out["dsig_f"]), _ptr(out["dsig_g"]), _ptr(out["dsig0"]),
-        _ptr(out["dfsig0"]), _ptr(sacc), _stream())
+    with _fixed_order():
+        st = lib.psvo_filter_backward(
+            ctypes.byref(desc), ctypes.byref(q1s), ctypes.byref(fs) if fs is not None else None, ctypes.byref(gs),
+            _ptr(sig_q1), _ptr(sig_q2), _ptr(sig_f), _ptr(sig_g), _ptr(mu2), _ptr(m0), _ptr(sig0), _ptr(fm0), _ptr(fsig0),
+            _ptr(obs), _ptr(eps), _ptr(filt["X"]), _ptr(filt["Fm"]), _ptr(filt["P1"]), _ptr(filt["logW"]),
+            _ptr(filt["lse"]), _ptr(filt["idx"]), _ptr(dlse), nparts, _ptr(dFm), _ptr(dlogW),
+            _ptr(out["dP"]), _ptr(out["dF"]), _ptr(out["dG"]), _ptr(out["dmu2"]), _ptr(out["dm0"]), _ptr(out["dfm0"]),
+            _ptr(out["dsig_q1"]), _ptr(out["dsig_q2"]), _ptr(out["dsig_f"]), _ptr(out["dsig_g"]), _ptr(out["dsig0"]),
+            _ptr(out["dfsig0"]), _ptr(sacc), _stream())
     _mark("psvo_filter_backward", 1)
     _lib.check(st, "psvo_filter_backward")
     # weight gradients from rows; gbufs = (q1, f, g) slices of the flat gradient buffer to accumulate into
@@ -525,14 +565,16 @@ def filter_backward_cov(desc, q1, f, g, sigc_q1, sigc_f, sigc_g, mu2, sig2, m0, 
            "dsigc_q1": z(Dx), "dsigc_f": None if boot else z(Dx), "dsigc_g": z(Dy)}
     ws = z(lib.psvo_filter_cov_ws_floats(B, T, N, Dx, Dy))
     _mark("psvo_filter_backward_cov", 0)
-    st = lib.psvo_filter_backward_cov(
-        ctypes.byref(desc), ctypes.byref(q1s), ctypes.byref(fs) if fs is not None else None, ctypes.byref(gs),
-        _ptr(sigc_q1), _ptr(sigc_f), _ptr(sigc_g), _ptr(mu2), _ptr(sig2), _ptr(m0), _ptr(sig0), _ptr(fm0), _ptr(fsig0),
-        _ptr(obs), _ptr(eps), _ptr(filt["X"]), _ptr(filt["Fm"]), _ptr(filt["Fs"]), _ptr(filt["P1"]), _ptr(filt["P1s"]),
-        _ptr(filt["logW"]), _ptr(filt["lse"]), _ptr(filt["idx"]), _ptr(dlse), _ptr(dFm), _ptr(dFs), _ptr(dlogW),
-        _ptr(out["dP"][0]), _ptr(out["dP"][1]), _ptr(out["dF"][0]), _ptr(out["dF"][1]), _ptr(out["dG"][0]),
-        _ptr(out["dG"][1]), _ptr(out["dmu2"]), _ptr(out["dsig2"]), _ptr(out["dm0"]), _ptr(out["dsig0"]), _ptr(out["dfm0"]),
-        _ptr(out["dfsig0"]), _ptr(out["dsigc_q1"]), _ptr(out["dsigc_f"]), _ptr(out["dsigc_g"]), _ptr(ws), _stream())
+    with _fixed_order():
+        st = lib.psvo_filter_backward_cov(
+            ctypes.byref(desc), ctypes.byref(q1s), ctypes.byref(fs) if fs is not None else None, ctypes.byref(gs),
+            _ptr(sigc_q1), _ptr(sigc_f), _ptr(sigc_g), _ptr(mu2), _ptr(sig2), _ptr(m0), _ptr(sig0), _ptr(fm0), _ptr(fsig0),
+            _ptr(obs), _ptr(eps), _ptr(filt["X"]), _ptr(filt["Fm"]), _ptr(filt["Fs"]), _ptr(filt["P1"]), _ptr(filt["P1s"]),
+            _ptr(filt["logW"]), _ptr(filt["lse"]), _ptr(filt["idx"]), _ptr(dlse), _ptr(dFm), _ptr(dFs), _ptr(dlogW),
+            _ptr(out["dP"][0]), _ptr(out["dP"][1]), _ptr(out["dF"][0]), _ptr(out["dF"][1]), _ptr(out["dG"][0]),
+            _ptr(out["dG"][1]), _ptr(out["dmu2"]), _ptr(out["dsig2"]), _ptr(out["dm0"]), _ptr(out["dsig0"]),
+            _ptr(out["dfm0"]), _ptr(out["dfsig0"]), _ptr(out["dsigc_q1"]), _ptr(out["dsigc_f"]), _ptr(out["dsigc_g"]),
+            _ptr(ws), _stream())
     _mark("psvo_filter_backward_cov", 1)
     _lib.check(st, "psvo_filter_backward_cov")
     del k1, k2, k3
@@ -613,15 +655,19 @@ def bsim_backward_cov(desc, filt, f, g, q1_inv, sigc_f, sigc_g, sigc_q1inv, bmu2
            "dimean": zeros(B, Dx), "disig": zeros(B, Dx), "dsigc_f": zeros(Dx), "dsigc_g": zeros(Dy),
            "dsigc_q1inv": zeros(Dx)}
     _mark("psvo_bsim_backward_cov", 0)
-    st = lib.psvo_bsim_backward_cov(
-        ctypes.byref(desc), _ptr(filt["Fm"]), _ptr(filt["Fs"]), _ptr(filt["logW"]), _ptr(filt["lse"]),
-        ctypes.byref(fs), ctypes.byref(gs), ctypes.byref(qs), _ptr(sigc_f), _ptr(sigc_g), _ptr(sigc_q1inv),
-        _ptr(bmu2), _ptr(bsig2), _ptr(minit), _ptr(sinit), _ptr(imean), _ptr(isig), _ptr(obs), _ptr(eps_b),
-        _ptr(bs["bwX"]), _ptr(bs["sel"]), _ptr(bs["lam"]), _ptr(bs["om"]), _ptr(bs["mu1"]), _ptr(bs["s1"]), _ptr(dscore),
-        _ptr(out["xt"]), _ptr(out["dFt"]), _ptr(out["dFts"]), _ptr(out["dGt"]), _ptr(out["dGts"]), _ptr(out["dmu1"]),
-        _ptr(out["dmu1s"]), _ptr(out["dFm"]), _ptr(out["dFs"]), _ptr(out["dlogW"]), _ptr(out["dlse"]), _ptr(out["dbmu2"]),
-        _ptr(out["dbsig2"]), _ptr(out["dminit"]), _ptr(out["dsinit"]), _ptr(out["dimean"]), _ptr(out["disig"]),
-        _ptr(out["dsigc_f"]), _ptr(out["dsigc_g"]), _ptr(out["dsigc_q1inv"]), _stream())
+    with _fixed_order() as det:
+        # (the fixed-order route's per-workgroup slices; allocated only in the mode)
+        det_ws = z(lib.psvo_bsim_cov_det_ws_floats(B, N, M, Dx, Dy)) if det else None
+        st = lib.psvo_bsim_backward_cov_ws(
+            ctypes.byref(desc), _ptr(filt["Fm"]), _ptr(filt["Fs"]), _ptr(filt["logW"]), _ptr(filt["lse"]),
+            ctypes.byref(fs), ctypes.byref(gs), ctypes.byref(qs), _ptr(sigc_f), _ptr(sigc_g), _ptr(sigc_q1inv),
+            _ptr(bmu2), _ptr(bsig2), _ptr(minit), _ptr(sinit), _ptr(imean), _ptr(isig), _ptr(obs), _ptr(eps_b),
+            _ptr(bs["bwX"]), _ptr(bs["sel"]), _ptr(bs["lam"]), _ptr(bs["om"]), _ptr(bs["mu1"]), _ptr(bs["s1"]), _ptr(dscore),
+            _ptr(out["xt"]), _ptr(out["dFt"]), _ptr(out["dFts"]), _ptr(out["dGt"]), _ptr(out["dGts"]), _ptr(out["dmu1"]),
+            _ptr(out["dmu1s"]), _ptr(out["dFm"]), _ptr(out["dFs"]), _ptr(out["dlogW"]), _ptr(out["dlse"]),
+            _ptr(out["dbmu2"]), _ptr(out["dbsig2"]), _ptr(out["dminit"]), _ptr(out["dsinit"]), _ptr(out["dimean"]),
+            _ptr(out["disig"]), _ptr(out["dsigc_f"]), _ptr(out["dsigc_g"]), _ptr(out["dsigc_q1inv"]), _ptr(det_ws),
+            _stream())
     _mark("psvo_bsim_backward_cov", 1)
     _lib.check(st, "psvo_bsim_backward_cov")
     del k1, k2, k3
@@ -704,16 +750,19 @@ def bsimwr_backward_cov(desc, filt, f, g, q1_inv, sigc_f, sigc_g, sigc_q1inv, bm
            "dsigc_q1inv": zeros(Dx)}
     dXs = zeros(T, B, Dx, N)
     _mark("psvo_bsimwr_backward_cov", 0)
-    st = lib.psvo_bsimwr_backward_cov(
-        ctypes.byref(desc), _ptr(filt["Fm"]), _ptr(filt["Fs"]), _ptr(filt["logW"]), _ptr(filt["lse"]),
-        ctypes.byref(fs), ctypes.byref(gs), ctypes.byref(qs), _ptr(sigc_f), _ptr(sigc_g), _ptr(sigc_q1inv),
-        _ptr(bmu2), _ptr(bsig2), _ptr(minit), _ptr(sinit), _ptr(imean), _ptr(isig), _ptr(obs), _ptr(eps_b),
-        _ptr(bs["bwXanc"]), _ptr(bs["bwW"]), _ptr(bs["lseW"]), _ptr(bs["sel"]), _ptr(bs["anc"]), _ptr(bs["lam"]),
-        _ptr(bs["om"]), _ptr(bs["mu1"]), _ptr(bs["s1"]), _ptr(dlseW),
-        _ptr(out["xt"]), _ptr(out["dFt"]), _ptr(out["dFts"]), _ptr(out["dGt"]), _ptr(out["dGts"]), _ptr(out["dmu1"]),
-        _ptr(out["dmu1s"]), _ptr(out["dFm"]), _ptr(out["dFs"]), _ptr(out["dlogW"]), _ptr(out["dlse"]), _ptr(out["dbmu2"]),
-        _ptr(out["dbsig2"]), _ptr(out["dminit"]), _ptr(out["dsinit"]), _ptr(out["dimean"]), _ptr(out["disig"]),
-        _ptr(out["dsigc_f"]), _ptr(out["dsigc_g"]), _ptr(out["dsigc_q1inv"]), _ptr(dXs), _stream())
+    with _fixed_order() as det:
+        det_ws = z(lib.psvo_bsim_cov_det_ws_floats(B, N, M, Dx, Dy)) if det else None
+        st = lib.psvo_bsimwr_backward_cov_ws(
+            ctypes.byref(desc), _ptr(filt["Fm"]), _ptr(filt["Fs"]), _ptr(filt["logW"]), _ptr(filt["lse"]),
+            ctypes.byref(fs), ctypes.byref(gs), ctypes.byref(qs), _ptr(sigc_f), _ptr(sigc_g), _ptr(sigc_q1inv),
+            _ptr(bmu2), _ptr(bsig2), _ptr(minit), _ptr(sinit), _ptr(imean), _ptr(isig), _ptr(obs), _ptr(eps_b),
+            _ptr(bs["bwXanc"]), _ptr(bs["bwW"]), _ptr(bs["lseW"]), _ptr(bs["sel"]), _ptr(bs["anc"]), _ptr(bs["lam"]),
+            _ptr(bs["om"]), _ptr(bs["mu1"]), _ptr(bs["s1"]), _ptr(dlseW),
+            _ptr(out["xt"]), _ptr(out["dFt"]), _ptr(out["dFts"]), _ptr(out["dGt"]), _ptr(out["dGts"]), _ptr(out["dmu1"]),
+            _ptr(out["dmu1s"]), _ptr(out["dFm"]), _ptr(out["dFs"]), _ptr(out["dlogW"]), _ptr(out["dlse"]),
+            _ptr(out["dbmu2"]), _ptr(out["dbsig2"]), _ptr(out["dminit"]), _ptr(out["dsinit"]), _ptr(out["dimean"]),
+            _ptr(out["disig"]), _ptr(out["dsigc_f"]), _ptr(out["dsigc_g"]), _ptr(out["dsigc_q1inv"]), _ptr(dXs),
+            _ptr(det_ws), _stream())
     _mark("psvo_bsimwr_backward_cov", 1)
     _lib.check(st, "psvo_bsimwr_backward_cov")
     del k1, k2, k3
