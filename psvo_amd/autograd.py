@@ -405,6 +405,27 @@ class BsimFunction(torch.autograd.Function):
             r["dminit"], r["dsig_init"], r["dimean"], r["disig"]) + gextra
 
 
+def _bsim_cov_forward(ctx, op, desc, obs_TB, eps_b, Fm, Fs, logW, lse, t, **draws):
+    """a cov backward-simulation node's forward: op (ops.bsim_forward_cov / ops.bsimwr_forward_cov) on the filter's outputs and
+    the node's 27 positional tensors `t`; keeps on ctx what the reverse pass needs and returns op's dict"""
+    t = [_cf(v) for v in t]
+    f, g, q1_inv, rest = tuple(t[0:6]), tuple(t[6:12]), tuple(t[12:18]), t[18:27]
+    filt = {"Fm": _cf(Fm), "Fs": _cf(Fs), "logW": _cf(logW), "lse": _cf(lse)}
+    bs = op(desc, filt, f, g, q1_inv, *rest, obs_TB, eps_b, save=any(ctx.needs_input_grad), **draws)
+    ctx.desc, ctx.filt, ctx.bs = desc, filt, _aliases(bs)
+    ctx.saved = (f, g, q1_inv, rest, obs_TB, eps_b)
+    return bs
+
+
+def _bsim_cov_backward(ctx, op, dout, lead):
+    """its reverse (op: ops.bsim_backward_cov / ops.bsimwr_backward_cov): None for `lead` inputs, then Fm, Fs, logW, lse and `t`"""
+    f, g, q1_inv, rest, obs_TB, eps_b = ctx.saved
+    r = op(ctx.desc, ctx.filt, f, g, q1_inv, *rest, obs_TB, eps_b, ctx.bs, _cg(dout).float())
+    return (None,) * lead + (r["dFm"], r["dFs"], r["dlogW"], r["dlse"]) + r["gf"] + r["gg"] + r["gq1inv"] + (
+        r["dsigc_f"], r["dsigc_g"], r["dsigc_q1inv"], r["dbmu2"], r["dbsig2"], r["dminit"], r["dsinit"], r["dimean"],
+        r["disig"])
+
+
 class BsimCovFunction(torch.autograd.Function):
     """psvo_bsim_forward_cov / psvo_bsim_backward_cov: the backward simulation with state-dependent diagonal scales.
 
@@ -416,25 +437,13 @@ class BsimCovFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, desc, obs_TB, eps_b, u_b, sel_in, Fm, Fs, logW, lse, *t):
-        t = [_cf(v) for v in t]
-        f, g, q1_inv = tuple(t[0:6]), tuple(t[6:12]), tuple(t[12:18])
-        rest = t[18:27]
-        filt = {"Fm": _cf(Fm), "Fs": _cf(Fs), "logW": _cf(logW), "lse": _cf(lse)}
-        bs = ops.bsim_forward_cov(desc, filt, f, g, q1_inv, *rest, obs_TB, eps_b, u_b, sel_in,
-                                  save=any(ctx.needs_input_grad))
-        ctx.desc, ctx.filt, ctx.bs = desc, filt, _aliases(bs)
-        ctx.saved = (f, g, q1_inv, rest, obs_TB, eps_b)
+        bs = _bsim_cov_forward(ctx, ops.bsim_forward_cov, desc, obs_TB, eps_b, Fm, Fs, logW, lse, t, u_b=u_b, sel_in=sel_in)
         ctx.mark_non_differentiable(bs["bwX"], bs["flp"], bs["glp"], bs["Omega"], bs["sel"])
         return bs["score"], bs["bwX"], bs["flp"], bs["glp"], bs["Omega"], bs["sel"]
 
     @staticmethod
     def backward(ctx, dscore, *_):
-        desc = ctx.desc
-        f, g, q1_inv, rest, obs_TB, eps_b = ctx.saved
-        r = ops.bsim_backward_cov(desc, ctx.filt, f, g, q1_inv, *rest, obs_TB, eps_b, ctx.bs, _cg(dscore).float())
-        return (None, None, None, None, None, r["dFm"], r["dFs"], r["dlogW"], r["dlse"]) + r["gf"] + r["gg"] + r["gq1inv"] + (
-            r["dsigc_f"], r["dsigc_g"], r["dsigc_q1inv"], r["dbmu2"], r["dbsig2"], r["dminit"], r["dsinit"], r["dimean"],
-            r["disig"])
+        return _bsim_cov_backward(ctx, ops.bsim_backward_cov, dscore, 5)
 
 
 class BsimWRCovFunction(torch.autograd.Function):
@@ -446,28 +455,17 @@ class BsimWRCovFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, desc, obs_TB, eps_b, u_b, u_r, sel_in, anc_in, Fm, Fs, logW, lse, *t):
-        t = [_cf(v) for v in t]
-        f, g, q1_inv = tuple(t[0:6]), tuple(t[6:12]), tuple(t[12:18])
-        rest = t[18:27]
-        filt = {"Fm": _cf(Fm), "Fs": _cf(Fs), "logW": _cf(logW), "lse": _cf(lse)}
-        bs = ops.bsimwr_forward_cov(desc, filt, f, g, q1_inv, *rest, obs_TB, eps_b, u_b=u_b, u_r=u_r, sel_in=sel_in,
-                                    anc_in=anc_in, save=any(ctx.needs_input_grad))
-        ctx.desc, ctx.filt, ctx.bs = desc, filt, _aliases(bs)
-        ctx.saved = (f, g, q1_inv, rest, obs_TB, eps_b)
+        bs = _bsim_cov_forward(ctx, ops.bsimwr_forward_cov, desc, obs_TB, eps_b, Fm, Fs, logW, lse, t, u_b=u_b, u_r=u_r,
+                               sel_in=sel_in, anc_in=anc_in)
         ctx.mark_non_differentiable(bs["bwXanc"], bs["bwX"], bs["bwW"], bs["sel"], bs["anc"])
         ctx.set_materialize_grads(False)
         return bs["lseW"], bs["bwXanc"], bs["bwX"], bs["bwW"], bs["sel"], bs["anc"]
 
     @staticmethod
     def backward(ctx, dlseW, *_):
-        desc = ctx.desc
         if dlseW is None:
-            dlseW = torch.zeros(desc.T, desc.B, device=ctx.filt["Fm"].device)
-        f, g, q1_inv, rest, obs_TB, eps_b = ctx.saved
-        r = ops.bsimwr_backward_cov(desc, ctx.filt, f, g, q1_inv, *rest, obs_TB, eps_b, ctx.bs, _cg(dlseW).float())
-        return (None,) * 7 + (r["dFm"], r["dFs"], r["dlogW"], r["dlse"]) + r["gf"] + r["gg"] + r["gq1inv"] + (
-            r["dsigc_f"], r["dsigc_g"], r["dsigc_q1inv"], r["dbmu2"], r["dbsig2"], r["dminit"], r["dsinit"], r["dimean"],
-            r["disig"])
+            dlseW = torch.zeros(ctx.desc.T, ctx.desc.B, device=ctx.filt["Fm"].device)
+        return _bsim_cov_backward(ctx, ops.bsimwr_backward_cov, dlseW, 7)
 
 
 def _note_exchange(desc, ws, bit):

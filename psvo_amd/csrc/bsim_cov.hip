@@ -952,18 +952,28 @@ __global__ void __launch_bounds__(256) bsim_cov_bwd_kernel(const BwdArgs a) {
     }
 }
 
+// Launch geometry of bsim_cov_fwd_kernel and bsim_cov_bwd_kernel (a chain is M lanes; the grid is (nblk, B)): threads and chains
+// per workgroup, workgroups per sequence, waves per workgroup.  The DET workspace is sized and carved from the same figures (det_ws).
+struct Geom {
+    int ntb, cpb, nblk, nwv;
+};
+static Geom geometry(int N, int M) {
+    int NTB = ((N * M + 63) / 64) * 64;
+    if (NTB > 256) NTB = 256;
+    const int cpb = NTB / M;
+    return {NTB, cpb, (N + cpb - 1) / cpb, NTB / 64};
+}
+
 template <int DX, int DY, int H, int M>
 static int launch_fwd(const FwdArgs& a, hipStream_t stream) {
     using MQ = MlpLds<DX, H, 2 * DX, 1>;
     using MG = MlpLds<DX, H, 2 * DY, 1>;
     const int NP = (a.N + 7) & ~7;
-    int NTB = ((a.N * M + 63) / 64) * 64;
-    if (NTB > 256) NTB = 256;
-    const int cpb = NTB / M;
+    const Geom ge = geometry(a.N, M);
     const size_t lds = sizeof(float) * (2 * MQ::kSize + MG::kSize + 2 * (size_t)NP * Tile<DX>::TS);
-    dim3 grid((a.N + cpb - 1) / cpb, a.B);
+    dim3 grid(ge.nblk, a.B);
     clear_hip_error();
-    hipLaunchKernelGGL((bsim_cov_fwd_kernel<DX, DY, H, M, false>), grid, dim3(NTB), lds, stream, a);
+    hipLaunchKernelGGL((bsim_cov_fwd_kernel<DX, DY, H, M, false>), grid, dim3(ge.ntb), lds, stream, a);
     return launch_status();
 }
 
@@ -973,16 +983,14 @@ static int launch_fwd_wr(const FwdArgs& a0, float* lseW, hipStream_t stream) {
     using MQ = MlpLds<DX, H, 2 * DX, 1>;
     using MG = MlpLds<DX, H, 2 * DY, 1>;
     const int NP = (a0.N + 7) & ~7;
-    int NTB = ((a0.N * M + 63) / 64) * 64;
-    if (NTB > 256) NTB = 256;
-    const int cpb = NTB / M;
+    const Geom ge = geometry(a0.N, M);
     const size_t lds = sizeof(float) * (2 * MQ::kSize + MG::kSize + 2 * (size_t)NP * Tile<DX>::TS + 1024 + 32);
-    dim3 grid((a0.N + cpb - 1) / cpb, a0.B);
+    dim3 grid(ge.nblk, a0.B);
     clear_hip_error();
     FwdArgs a = a0;
     for (int t = a0.T - 1; t >= -1; --t) {
         a.t_hi = a.t_lo = t;
-        hipLaunchKernelGGL((bsim_cov_fwd_kernel<DX, DY, H, M, true>), grid, dim3(NTB), lds, stream, a);
+        hipLaunchKernelGGL((bsim_cov_fwd_kernel<DX, DY, H, M, true>), grid, dim3(ge.ntb), lds, stream, a);
     }
     const long long rows = (long long)a0.T * a0.B;
     hipLaunchKernelGGL(wr_lse_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, a0.bwW, rows, a0.N, lseW);
@@ -1062,36 +1070,34 @@ static int launch_bwd(const BwdArgs& a, hipStream_t stream) {
     using MQ = MlpLds<DX, H, 2 * DX, 1>;
     using MG = MlpLds<DX, H, 2 * DY, 1>;
     const int NP = (a.N + 15) & ~15;
-    int NTB = ((a.N * M + 63) / 64) * 64;
-    if (NTB > 256) NTB = 256;
-    const int cpb = NTB / M;
+    const Geom ge = geometry(a.N, M);
     const size_t lds = sizeof(float) * (2 * MQ::kSize + MG::kSize + (size_t)NP * (Tile<DX>::TS + 2 * DX + 1) +
                                         4 * 64 * (DX + 2) + 4 * DX + 16);
-    dim3 grid((a.N + cpb - 1) / cpb, a.B);
+    dim3 grid(ge.nblk, a.B);
     clear_hip_error();
     if (a.jpart) {          // PSVO_TUNE_DETERMINISTIC: one launch per step, then the gather (PSVOwR) and the fold of the step
         BwdArgs w = a;
-        w.nblk = (int)grid.x;
-        w.nwv = NTB / 64;
-        const size_t ldsd = lds + sizeof(float) * ((size_t)(w.nwv - 1) * NP * (2 * DX + 1) + (size_t)cpb * 4 * DX);
+        w.nblk = ge.nblk;
+        w.nwv = ge.nwv;
+        const size_t ldsd = lds + sizeof(float) * ((size_t)(w.nwv - 1) * NP * (2 * DX + 1) + (size_t)ge.cpb * 4 * DX);
         if (ldsd > 160 * 1024) return PSVO_ERR_UNSUPPORTED;
         const bool wr = a.t_lo >= 0;
         for (int t = 0; t < a.T; ++t) {
             w.t_lo = w.t_hi = t;
-            if (wr) hipLaunchKernelGGL((bsim_cov_bwd_kernel<DX, DY, H, M, true, true>), grid, dim3(NTB), ldsd, stream, w);
-            else hipLaunchKernelGGL((bsim_cov_bwd_kernel<DX, DY, H, M, false, true>), grid, dim3(NTB), ldsd, stream, w);
+            if (wr) hipLaunchKernelGGL((bsim_cov_bwd_kernel<DX, DY, H, M, true, true>), grid, dim3(ge.ntb), ldsd, stream, w);
+            else hipLaunchKernelGGL((bsim_cov_bwd_kernel<DX, DY, H, M, false, true>), grid, dim3(ge.ntb), ldsd, stream, w);
             if (wr && t + 1 < a.T)
                 hipLaunchKernelGGL(bsim_cov_det_gather, dim3(a.B), dim3(256), sizeof(float) * (size_t)(DX + 1) * a.N, stream, w,
                                    t, DX);
             hipLaunchKernelGGL((bsim_cov_det_fold<DX, DY>), dim3(a.B), dim3(256), 0, stream, w, t);
         }
     } else if (a.t_lo < 0) {       // PSVO: persistent over all steps
-        hipLaunchKernelGGL((bsim_cov_bwd_kernel<DX, DY, H, M, false>), grid, dim3(NTB), lds, stream, a);
+        hipLaunchKernelGGL((bsim_cov_bwd_kernel<DX, DY, H, M, false>), grid, dim3(ge.ntb), lds, stream, a);
     } else {                // PSVOwR: one launch per time step, 0 .. T-1
         BwdArgs w = a;
         for (int t = 0; t < a.T; ++t) {
             w.t_lo = w.t_hi = t;
-            hipLaunchKernelGGL((bsim_cov_bwd_kernel<DX, DY, H, M, true>), grid, dim3(NTB), lds, stream, w);
+            hipLaunchKernelGGL((bsim_cov_bwd_kernel<DX, DY, H, M, true>), grid, dim3(ge.ntb), lds, stream, w);
         }
     }
     return launch_status();
@@ -1131,29 +1137,86 @@ static int launch_bwd(const BwdArgs& a, hipStream_t stream) {
         }                                                                           \
     } while (0)
 
-static bool desc_ok(const psvo_desc* d) { return d && d->B > 0 && d->T >= 2 && d->N > 0 && d->M > 0; }
-
-// workgroups per sequence and waves per workgroup of bsim_cov_bwd_kernel (launch_bwd)
-static void bwd_geometry(int N, int M, int& nblk, int& nwv, int& cpb) {
-    int NTB = ((N * M + 63) / 64) * 64;
-    if (NTB > 256) NTB = 256;
-    cpb = NTB / M;
-    nblk = (N + cpb - 1) / cpb;
-    nwv = NTB / 64;
+// The DET workspace (psvo_bsim_cov_det_ws_floats): the four DET arrays of BwdArgs one after the other, sizes in floats
+struct DetWs {
+    size_t jpart, cpart, spart, dxc;
+};
+static DetWs det_ws(int B, int N, int M, int Dx, int Dy) {
+    const Geom ge = geometry(N, M);
+    const size_t s = (size_t)B * ge.nblk;
+    return {s * (2 * Dx + 1) * N, s * 4 * Dx, s * ge.nwv * (2 * Dx + Dy), (size_t)B * Dx * N};
 }
 
-// the four DET arrays of BwdArgs, carved from the caller's workspace (psvo_bsim_cov_det_ws_floats); null when the mode is off
-static void set_det(BwdArgs& a, const psvo_desc* d, float* ws) {
-    a.jpart = a.cpart = a.spart = a.dxc = nullptr;
-    a.nblk = a.nwv = 0;
-    if (!g_tune_deterministic) return;
-    int nblk, nwv, cpb;
-    bwd_geometry(d->N, d->M, nblk, nwv, cpb);
-    const size_t s = (size_t)d->B * nblk;
-    a.jpart = ws;
-    a.cpart = a.jpart + s * (2 * d->Dx + 1) * d->N;
-    a.spart = a.cpart + s * 4 * d->Dx;
-    a.dxc = a.spart + s * nwv * (2 * d->Dx + d->Dy);
+// What the four entry points take ahead of their own arguments, in the header's order
+struct Inputs {
+    const float *Fm, *Fs, *logW, *lse;
+    const psvo_mlp *f, *g, *q1_inv;
+    const float *sigc_f, *sigc_g, *sigc_q1inv, *bmu2, *bsig2, *minit, *sinit, *imean, *isig, *obs, *eps_b;
+};
+static bool all_set(const Inputs& p) {
+    return p.Fm && p.Fs && p.logW && p.lse && p.f && p.g && p.q1_inv && p.sigc_f && p.sigc_g && p.sigc_q1inv && p.bmu2 && p.bsig2 &&
+           p.minit && p.sinit && p.imean && p.isig && p.obs && p.eps_b;
+}
+
+// The saves and the gradient outputs both reverse entry points take, in the header's order
+struct BwdIo {
+    const int32_t* sel;
+    const float *lam_all, *om_all, *mu1_all, *s1_all;
+    float *xt, *dFt, *dFts, *dGt, *dGts, *dmu1, *dmu1s, *dFm, *dFs, *dlogW, *dlse, *dbmu2, *dbsig2, *dminit, *dsinit, *dimean,
+        *disig, *dsigc_f, *dsigc_g, *dsigc_q1inv;
+};
+static bool all_set(const BwdIo& p) {
+    return p.sel && p.lam_all && p.om_all && p.mu1_all && p.s1_all && p.xt && p.dFt && p.dFts && p.dGt && p.dGts && p.dmu1 &&
+           p.dmu1s && p.dFm && p.dFs && p.dlogW && p.dlse && p.dbmu2 && p.dbsig2 && p.dminit && p.dsinit && p.dimean && p.disig &&
+           p.dsigc_f && p.dsigc_g && p.dsigc_q1inv;
+}
+
+// Status of the arguments every entry point checks, in the order tests/test_abi.py pins.  ptrs_ok: its required pointers are set
+static int check_args(const psvo_desc* desc, bool ptrs_ok) {
+    if (!desc) return PSVO_ERR_INVALID;
+    if (desc->layers > 1 || desc->layers < 0) return PSVO_ERR_UNSUPPORTED;
+    if (desc->B <= 0 || desc->T < 2 || desc->N <= 0 || desc->M <= 0 || !ptrs_ok) return PSVO_ERR_INVALID;
+    if (desc->N > 1024 || desc->B > 65535) return PSVO_ERR_UNSUPPORTED;
+    return PSVO_OK;
+}
+
+template <class Args>       // FwdArgs or BwdArgs
+static void set_common(Args& a, const psvo_desc* desc, const Inputs& in) {
+    a.B = desc->B; a.T = desc->T; a.N = desc->N; a.emission = desc->emission;
+    a.f = *in.f; a.g = *in.g; a.q1inv = *in.q1_inv;
+    a.Fm = in.Fm; a.Fs = in.Fs; a.logW = in.logW; a.lse = in.lse;
+    a.sc_f = in.sigc_f; a.sc_g = in.sigc_g; a.sc_q1inv = in.sigc_q1inv;
+    a.bmu2 = in.bmu2; a.bsig2 = in.bsig2; a.minit = in.minit; a.sinit = in.sinit; a.imean = in.imean; a.isig = in.isig;
+    a.obs = in.obs; a.eps_b = in.eps_b;
+}
+
+// the checks and the fields both forward entry points share; own_ok: the caller's own required pointers are set
+static int set_fwd(FwdArgs& a, const psvo_desc* desc, const Inputs& in, const float* u_b, const int32_t* sel_in, float* bwX,
+                   int32_t* sel_out, float* lam_all, float* om_all, float* mu1_all, float* s1_all, bool own_ok) {
+    const int st = check_args(desc, all_set(in) && bwX && sel_out && own_ok && (u_b || sel_in) &&
+                                        (mu1_all != nullptr) == (s1_all != nullptr));
+    if (st != PSVO_OK) return st;
+    set_common(a, desc, in);
+    a.u_b = u_b; a.sel_in = sel_in; a.bwX = bwX; a.sel_out = sel_out;
+    a.lam_all = lam_all; a.om_all = om_all; a.mu1_all = mu1_all; a.s1_all = s1_all;
+    return PSVO_OK;
+}
+
+// the checks and the fields both reverse entry points share; the DET arrays carved from the caller's workspace, null in default mode
+static int set_bwd(BwdArgs& a, const psvo_desc* desc, const Inputs& in, const BwdIo& io, float* ws, bool own_ok) {
+    const int st = check_args(desc, !(g_tune_deterministic && !ws) && all_set(in) && all_set(io) && own_ok);
+    if (st != PSVO_OK) return st;
+    set_common(a, desc, in);
+    a.sel = io.sel; a.lam_all = io.lam_all; a.om_all = io.om_all; a.mu1_all = io.mu1_all; a.s1_all = io.s1_all;
+    a.xt = io.xt; a.dFt = io.dFt; a.dFts = io.dFts; a.dGt = io.dGt; a.dGts = io.dGts; a.dmu1 = io.dmu1; a.dmu1s = io.dmu1s;
+    a.dFm = io.dFm; a.dFs = io.dFs; a.dlogW = io.dlogW; a.dlse = io.dlse; a.dbmu2 = io.dbmu2; a.dbsig2 = io.dbsig2;
+    a.dminit = io.dminit; a.dsinit = io.dsinit; a.dimean = io.dimean; a.disig = io.disig;
+    a.dsc_f = io.dsigc_f; a.dsc_g = io.dsigc_g; a.dsc_q1inv = io.dsigc_q1inv;
+    a.jpart = a.cpart = a.spart = a.dxc = nullptr; a.nblk = a.nwv = 0;     // (launch_bwd sets the two for the DET launches)
+    if (!g_tune_deterministic) return PSVO_OK;
+    const DetWs l = det_ws(desc->B, desc->N, desc->M, desc->Dx, desc->Dy);
+    a.jpart = ws; a.cpart = a.jpart + l.jpart; a.spart = a.cpart + l.cpart; a.dxc = a.spart + l.spart;
+    return PSVO_OK;
 }
 
 }  // namespace covb
@@ -1161,10 +1224,8 @@ static void set_det(BwdArgs& a, const psvo_desc* d, float* ws) {
 
 extern "C" long long psvo_bsim_cov_det_ws_floats(int B, int N, int M, int Dx, int Dy) {
     if (B <= 0 || N <= 0 || M <= 0 || Dx <= 0 || Dy <= 0) return 0;
-    int nblk, nwv, cpb;
-    psvo::covb::bwd_geometry(N, M, nblk, nwv, cpb);
-    const long long s = (long long)B * nblk;
-    return s * (2 * Dx + 1) * N + s * 4 * Dx + s * nwv * (2 * Dx + Dy) + (long long)B * Dx * N;
+    const psvo::covb::DetWs l = psvo::covb::det_ws(B, N, M, Dx, Dy);
+    return (long long)(l.jpart + l.cpart + l.spart + l.dxc);
 }
 
 extern "C" int psvo_bsim_forward_cov(const psvo_desc* desc, const float* Fm, const float* Fs, const float* logW,
@@ -1175,30 +1236,15 @@ extern "C" int psvo_bsim_forward_cov(const psvo_desc* desc, const float* Fm, con
                                      const int32_t* sel_in, float* bwX, float* flp, float* glp, float* Omega,
                                      int32_t* sel_out, float* score, float* lam_all, float* om_all, float* mu1_all,
                                      float* s1_all, void* stream) {
-    using namespace psvo;
     using namespace psvo::covb;
-    if (!desc) return PSVO_ERR_INVALID;
-    if (desc->layers > 1 || desc->layers < 0) return PSVO_ERR_UNSUPPORTED;
-    if (!desc_ok(desc)) return PSVO_ERR_INVALID;
-    if (!Fm || !Fs || !logW || !lse || !f || !g || !q1_inv || !sigc_f || !sigc_g || !sigc_q1inv || !bmu2 || !bsig2 || !minit ||
-        !sinit || !imean || !isig || !obs || !eps_b || !bwX || !flp || !glp || !Omega || !sel_out || !score)
-        return PSVO_ERR_INVALID;
-    if (!u_b && !sel_in) return PSVO_ERR_INVALID;
-    if ((mu1_all != nullptr) != (s1_all != nullptr)) return PSVO_ERR_INVALID;
-    if (desc->N > 1024 || desc->B > 65535) return PSVO_ERR_UNSUPPORTED;
+    Inputs in{Fm, Fs, logW, lse, f, g, q1_inv, sigc_f, sigc_g, sigc_q1inv, bmu2, bsig2, minit, sinit, imean, isig, obs, eps_b};
     FwdArgs a;
-    a.B = desc->B; a.T = desc->T; a.N = desc->N; a.emission = desc->emission;
-    a.f = *f; a.g = *g; a.q1inv = *q1_inv;
-    a.Fm = Fm; a.Fs = Fs; a.logW = logW; a.lse = lse;
-    a.sc_f = sigc_f; a.sc_g = sigc_g; a.sc_q1inv = sigc_q1inv;
-    a.bmu2 = bmu2; a.bsig2 = bsig2; a.minit = minit; a.sinit = sinit; a.imean = imean; a.isig = isig;
-    a.obs = obs; a.eps_b = eps_b; a.u_b = u_b; a.sel_in = sel_in;
-    a.bwX = bwX; a.flp = flp; a.glp = glp; a.Omega = Omega; a.sel_out = sel_out; a.score = score;
-    a.lam_all = lam_all; a.om_all = om_all; a.mu1_all = mu1_all; a.s1_all = s1_all;
+    const int st = set_fwd(a, desc, in, u_b, sel_in, bwX, sel_out, lam_all, om_all, mu1_all, s1_all, flp && glp && Omega && score);
+    if (st != PSVO_OK) return st;
+    a.flp = flp; a.glp = glp; a.Omega = Omega; a.score = score;
     a.t_hi = desc->T - 1; a.t_lo = 0; a.u_r = nullptr; a.anc_in = nullptr;
     a.bwXanc = a.bwW = a.omsel = nullptr; a.anc_out = nullptr;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    PSVO_COVB_DISPATCH(launch_fwd, a, s);
+    PSVO_COVB_DISPATCH(launch_fwd, a, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int psvo_bsim_backward_cov_ws(
@@ -1210,35 +1256,17 @@ extern "C" int psvo_bsim_backward_cov_ws(
     float* dGts, float* dmu1, float* dmu1s, float* dFm, float* dFs, float* dlogW, float* dlse, float* dbmu2, float* dbsig2,
     float* dminit, float* dsinit, float* dimean, float* disig, float* dsigc_f, float* dsigc_g, float* dsigc_q1inv,
     float* det_ws, void* stream) {
-    using namespace psvo;
     using namespace psvo::covb;
-    if (!desc) return PSVO_ERR_INVALID;
-    if (desc->layers > 1 || desc->layers < 0) return PSVO_ERR_UNSUPPORTED;
-    if (!desc_ok(desc)) return PSVO_ERR_INVALID;
-    if (g_tune_deterministic && !det_ws) return PSVO_ERR_INVALID;      // (the fixed-order route needs its workspace)
-    if (!Fm || !Fs || !logW || !lse || !f || !g || !q1_inv || !sigc_f || !sigc_g || !sigc_q1inv || !bmu2 || !bsig2 || !minit ||
-        !sinit || !imean || !isig || !obs || !eps_b || !bwX || !sel || !lam_all || !om_all || !mu1_all || !s1_all || !dscore ||
-        !xt || !dFt || !dFts || !dGt || !dGts || !dmu1 || !dmu1s || !dFm || !dFs || !dlogW || !dlse || !dbmu2 || !dbsig2 ||
-        !dminit || !dsinit || !dimean || !disig || !dsigc_f || !dsigc_g || !dsigc_q1inv)
-        return PSVO_ERR_INVALID;
-    if (desc->N > 1024 || desc->B > 65535) return PSVO_ERR_UNSUPPORTED;
+    Inputs in{Fm, Fs, logW, lse, f, g, q1_inv, sigc_f, sigc_g, sigc_q1inv, bmu2, bsig2, minit, sinit, imean, isig, obs, eps_b};
+    BwdIo io{sel, lam_all, om_all, mu1_all, s1_all, xt, dFt, dFts, dGt, dGts, dmu1, dmu1s, dFm, dFs, dlogW, dlse, dbmu2, dbsig2,
+             dminit, dsinit, dimean, disig, dsigc_f, dsigc_g, dsigc_q1inv};
     BwdArgs a;
-    a.B = desc->B; a.T = desc->T; a.N = desc->N; a.emission = desc->emission;
-    a.f = *f; a.g = *g; a.q1inv = *q1_inv;
-    a.Fm = Fm; a.Fs = Fs; a.logW = logW; a.lse = lse;
-    a.sc_f = sigc_f; a.sc_g = sigc_g; a.sc_q1inv = sigc_q1inv;
-    a.bmu2 = bmu2; a.bsig2 = bsig2; a.minit = minit; a.sinit = sinit; a.imean = imean; a.isig = isig;
-    a.obs = obs; a.eps_b = eps_b; a.bwX = bwX; a.sel = sel;
-    a.lam_all = lam_all; a.om_all = om_all; a.mu1_all = mu1_all; a.s1_all = s1_all; a.dscore = dscore;
-    a.xt = xt; a.dFt = dFt; a.dFts = dFts; a.dGt = dGt; a.dGts = dGts; a.dmu1 = dmu1; a.dmu1s = dmu1s;
-    a.dFm = dFm; a.dFs = dFs; a.dlogW = dlogW; a.dlse = dlse; a.dbmu2 = dbmu2; a.dbsig2 = dbsig2;
-    a.dminit = dminit; a.dsinit = dsinit; a.dimean = dimean; a.disig = disig;
-    a.dsc_f = dsigc_f; a.dsc_g = dsigc_g; a.dsc_q1inv = dsigc_q1inv;
+    const int st = set_bwd(a, desc, in, io, det_ws, bwX && dscore);
+    if (st != PSVO_OK) return st;
+    a.bwX = bwX; a.dscore = dscore;
     a.t_lo = a.t_hi = -1;       // persistent over all steps
     a.bwXanc = a.bwW = a.lseW = a.dlseW = nullptr; a.anc = nullptr; a.dXs = nullptr;
-    set_det(a, desc, det_ws);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    PSVO_COVB_DISPATCH(launch_bwd, a, s);
+    PSVO_COVB_DISPATCH(launch_bwd, a, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int psvo_bsim_backward_cov(
@@ -1264,30 +1292,16 @@ extern "C" int psvo_bsimwr_forward_cov(
     const float* obs, const float* eps_b, const float* u_b, const float* u_r, const int32_t* sel_in, const int32_t* anc_in,
     float* bwX, float* bwXanc, float* bwW, float* lseW, int32_t* sel_out, int32_t* anc_out, float* omsel, float* lam_all,
     float* om_all, float* mu1_all, float* s1_all, void* stream) {
-    using namespace psvo;
     using namespace psvo::covb;
-    if (!desc) return PSVO_ERR_INVALID;
-    if (desc->layers > 1 || desc->layers < 0) return PSVO_ERR_UNSUPPORTED;
-    if (!desc_ok(desc)) return PSVO_ERR_INVALID;
-    if (!Fm || !Fs || !logW || !lse || !f || !g || !q1_inv || !sigc_f || !sigc_g || !sigc_q1inv || !bmu2 || !bsig2 || !minit ||
-        !sinit || !imean || !isig || !obs || !eps_b || !bwX || !bwXanc || !bwW || !lseW || !sel_out || !anc_out || !omsel)
-        return PSVO_ERR_INVALID;
-    if ((!u_b && !sel_in) || (!u_r && !anc_in)) return PSVO_ERR_INVALID;
-    if ((mu1_all != nullptr) != (s1_all != nullptr)) return PSVO_ERR_INVALID;
-    if (desc->N > 1024 || desc->B > 65535) return PSVO_ERR_UNSUPPORTED;
+    Inputs in{Fm, Fs, logW, lse, f, g, q1_inv, sigc_f, sigc_g, sigc_q1inv, bmu2, bsig2, minit, sinit, imean, isig, obs, eps_b};
     FwdArgs a;
-    a.B = desc->B; a.T = desc->T; a.N = desc->N; a.emission = desc->emission;
-    a.f = *f; a.g = *g; a.q1inv = *q1_inv;
-    a.Fm = Fm; a.Fs = Fs; a.logW = logW; a.lse = lse;
-    a.sc_f = sigc_f; a.sc_g = sigc_g; a.sc_q1inv = sigc_q1inv;
-    a.bmu2 = bmu2; a.bsig2 = bsig2; a.minit = minit; a.sinit = sinit; a.imean = imean; a.isig = isig;
-    a.obs = obs; a.eps_b = eps_b; a.u_b = u_b; a.sel_in = sel_in;
-    a.bwX = bwX; a.flp = nullptr; a.glp = nullptr; a.Omega = nullptr; a.sel_out = sel_out; a.score = nullptr;
-    a.lam_all = lam_all; a.om_all = om_all; a.mu1_all = mu1_all; a.s1_all = s1_all;
+    const int st = set_fwd(a, desc, in, u_b, sel_in, bwX, sel_out, lam_all, om_all, mu1_all, s1_all,
+                           bwXanc && bwW && lseW && anc_out && omsel && (u_r || anc_in));
+    if (st != PSVO_OK) return st;
+    a.flp = nullptr; a.glp = nullptr; a.Omega = nullptr; a.score = nullptr;
     a.t_hi = a.t_lo = 0; a.u_r = u_r; a.anc_in = anc_in;
     a.bwXanc = bwXanc; a.bwW = bwW; a.omsel = omsel; a.anc_out = anc_out;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    PSVO_COVB_DISPATCH(launch_fwd_wr, a, lseW, s);
+    PSVO_COVB_DISPATCH(launch_fwd_wr, a, lseW, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int psvo_bsimwr_backward_cov_ws(
@@ -1299,35 +1313,17 @@ extern "C" int psvo_bsimwr_backward_cov_ws(
     const float* dlseW, float* xt, float* dFt, float* dFts, float* dGt, float* dGts, float* dmu1, float* dmu1s, float* dFm,
     float* dFs, float* dlogW, float* dlse, float* dbmu2, float* dbsig2, float* dminit, float* dsinit, float* dimean,
     float* disig, float* dsigc_f, float* dsigc_g, float* dsigc_q1inv, float* dXs, float* det_ws, void* stream) {
-    using namespace psvo;
     using namespace psvo::covb;
-    if (!desc) return PSVO_ERR_INVALID;
-    if (desc->layers > 1 || desc->layers < 0) return PSVO_ERR_UNSUPPORTED;
-    if (!desc_ok(desc)) return PSVO_ERR_INVALID;
-    if (g_tune_deterministic && !det_ws) return PSVO_ERR_INVALID;      // (the fixed-order route needs its workspace)
-    if (!Fm || !Fs || !logW || !lse || !f || !g || !q1_inv || !sigc_f || !sigc_g || !sigc_q1inv || !bmu2 || !bsig2 || !minit ||
-        !sinit || !imean || !isig || !obs || !eps_b || !bwXanc || !bwW || !lseW || !sel || !anc || !lam_all || !om_all ||
-        !mu1_all || !s1_all || !dlseW || !xt || !dFt || !dFts || !dGt || !dGts || !dmu1 || !dmu1s || !dFm || !dFs || !dlogW ||
-        !dlse || !dbmu2 || !dbsig2 || !dminit || !dsinit || !dimean || !disig || !dsigc_f || !dsigc_g || !dsigc_q1inv || !dXs)
-        return PSVO_ERR_INVALID;
-    if (desc->N > 1024 || desc->B > 65535) return PSVO_ERR_UNSUPPORTED;
+    Inputs in{Fm, Fs, logW, lse, f, g, q1_inv, sigc_f, sigc_g, sigc_q1inv, bmu2, bsig2, minit, sinit, imean, isig, obs, eps_b};
+    BwdIo io{sel, lam_all, om_all, mu1_all, s1_all, xt, dFt, dFts, dGt, dGts, dmu1, dmu1s, dFm, dFs, dlogW, dlse, dbmu2, dbsig2,
+             dminit, dsinit, dimean, disig, dsigc_f, dsigc_g, dsigc_q1inv};
     BwdArgs a;
-    a.B = desc->B; a.T = desc->T; a.N = desc->N; a.emission = desc->emission;
-    a.f = *f; a.g = *g; a.q1inv = *q1_inv;
-    a.Fm = Fm; a.Fs = Fs; a.logW = logW; a.lse = lse;
-    a.sc_f = sigc_f; a.sc_g = sigc_g; a.sc_q1inv = sigc_q1inv;
-    a.bmu2 = bmu2; a.bsig2 = bsig2; a.minit = minit; a.sinit = sinit; a.imean = imean; a.isig = isig;
-    a.obs = obs; a.eps_b = eps_b; a.bwX = nullptr; a.sel = sel;
-    a.lam_all = lam_all; a.om_all = om_all; a.mu1_all = mu1_all; a.s1_all = s1_all; a.dscore = nullptr;
-    a.xt = xt; a.dFt = dFt; a.dFts = dFts; a.dGt = dGt; a.dGts = dGts; a.dmu1 = dmu1; a.dmu1s = dmu1s;
-    a.dFm = dFm; a.dFs = dFs; a.dlogW = dlogW; a.dlse = dlse; a.dbmu2 = dbmu2; a.dbsig2 = dbsig2;
-    a.dminit = dminit; a.dsinit = dsinit; a.dimean = dimean; a.disig = disig;
-    a.dsc_f = dsigc_f; a.dsc_g = dsigc_g; a.dsc_q1inv = dsigc_q1inv;
+    const int st = set_bwd(a, desc, in, io, det_ws, bwXanc && bwW && lseW && anc && dlseW && dXs);
+    if (st != PSVO_OK) return st;
+    a.bwX = nullptr; a.dscore = nullptr;
     a.t_lo = a.t_hi = 0;        // (>= 0: one launch per time step)
     a.bwXanc = bwXanc; a.bwW = bwW; a.lseW = lseW; a.dlseW = dlseW; a.anc = anc; a.dXs = dXs;
-    set_det(a, desc, det_ws);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    PSVO_COVB_DISPATCH(launch_bwd, a, s);
+    PSVO_COVB_DISPATCH(launch_bwd, a, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int psvo_bsimwr_backward_cov(

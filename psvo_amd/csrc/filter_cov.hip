@@ -1160,13 +1160,23 @@ static bool desc_ok(const psvo_desc* d) {
     return d && d->B > 0 && d->T > 0 && d->N > 0;
 }
 
+// The reverse pass's workspace (psvo_filter_cov_ws_floats), offsets and size in floats: per-sequence sums (at 0) | d mu2 rows |
+// d sig2 rows | (16-byte aligned) affine-scan records | per-step partial sums.  The size allows 4 floats for the alignment.
+struct WsLayout {
+    long long dm2, ds2, rec, part, total;
+};
+static WsLayout ws_layout(int B, int T, int N, int Dx, int Dy) {
+    const long long R = Dx == 2 ? CovRec<2>::REC : Dx == 3 ? CovRec<3>::REC : Dx == 4 ? CovRec<4>::REC : 0;     // (else: no scan)
+    const long long sums = (long long)B * (2 * Dx + Dy), rows = (long long)T * B * Dx * N, recs = (long long)T * B * R * N;
+    const long long end = sums + 2 * rows, rec = (end + 3) & ~3LL;
+    return {sums, sums + rows, rec, rec + recs, end + 4 + recs + (long long)T * B * (2 * Dx + Dy)};
+}
+
 }  // namespace cov
 }  // namespace psvo
 
 extern "C" long long psvo_filter_cov_ws_floats(int B, int T, int N, int Dx, int Dy) {
-    // per-sequence sums | d mu2 rows | d sig2 rows | (16-byte aligned) affine-scan records | per-step partial sums
-    const long long rec = (4 * Dx * Dx + 4 * Dx + 1 + 3) / 4 * 4;      // CovRec<Dx>::REC
-    return (long long)B * (2 * Dx + Dy) + 2LL * T * B * Dx * N + 4 + (long long)T * B * rec * N + (long long)T * B * (2 * Dx + Dy);
+    return psvo::cov::ws_layout(B, T, N, Dx, Dy).total;
 }
 
 extern "C" int psvo_filter_forward_cov(const psvo_desc* desc, const psvo_mlp* q1, const psvo_mlp* f, const psvo_mlp* g,
@@ -1194,8 +1204,7 @@ extern "C" int psvo_filter_forward_cov(const psvo_desc* desc, const psvo_mlp* q1
     a.mu2 = mu2; a.sig2 = sig2; a.m0 = m0; a.sig0 = sig0; a.fm0 = fm0; a.fsig0 = fsig0;
     a.obs = obs; a.eps = eps; a.u = u; a.idx_in = idx_in;
     a.X = X; a.Xanc = Xanc; a.Fm = Fm; a.Fs = Fs; a.P1 = P1; a.P1s = P1s; a.logW = logW; a.idx_out = idx_out; a.lse = lse;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    PSVO_COV_DISPATCH(launch_fwd, a, s);
+    PSVO_COV_DISPATCH(launch_fwd, a, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int psvo_filter_backward_cov(
@@ -1228,16 +1237,10 @@ extern "C" int psvo_filter_backward_cov(
     a.dlse = dlse; a.dFm_ext = dFm_ext; a.dFs_ext = dFs_ext; a.dlogW_ext = dlogW_ext;
     a.dP = dP; a.dPs = dPs; a.dF = dF; a.dFs = dFs; a.dG = dG; a.dGs = dGs;
     a.dm0 = dm0; a.dsig0 = dsig0; a.dfm0 = dfm0; a.dfsig0 = dfsig0;
-    a.sacc = ws;
-    a.dm2_rows = ws + (size_t)desc->B * (2 * desc->Dx + desc->Dy);
-    a.ds2_rows = a.dm2_rows + (size_t)desc->T * desc->B * desc->Dx * desc->N;
-    {
-        const size_t off = (size_t)desc->B * (2 * desc->Dx + desc->Dy) + 2 * (size_t)desc->T * desc->B * desc->Dx * desc->N;
-        a.scanRec = ws + ((off + 3) & ~(size_t)3);
-        a.scanPart = a.scanRec + (size_t)desc->T * desc->B * ((4 * desc->Dx * desc->Dx + 4 * desc->Dx + 1 + 3) / 4 * 4) * desc->N;
-        if (reinterpret_cast<uintptr_t>(a.scanRec) & 15) a.scanRec = nullptr;
-    }
+    const WsLayout l = ws_layout(desc->B, desc->T, desc->N, desc->Dx, desc->Dy);
+    const bool scan = (reinterpret_cast<uintptr_t>(ws + l.rec) & 15) == 0;      // (a misaligned workspace: no affine scan)
+    a.sacc = ws; a.dm2_rows = ws + l.dm2; a.ds2_rows = ws + l.ds2;
+    a.scanRec = scan ? ws + l.rec : nullptr; a.scanPart = scan ? ws + l.part : nullptr;
     BwdOut o{dmu2, dsig2, dsigc_q1, dsigc_f, dsigc_g};
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    PSVO_COV_DISPATCH(launch_bwd, a, o, s);
+    PSVO_COV_DISPATCH(launch_bwd, a, o, static_cast<hipStream_t>(stream));
 }

@@ -59,11 +59,23 @@ def _fixed_order():
 _LAUNCH_STREAM = None
 
 
+_NO_STREAM = contextlib.nullcontext()
+
+
+def _on_launch_stream():
+    """with _on_launch_stream(): torch's own work in the block (allocations, copies, fills) goes to the launch stream, if one is set"""
+    return torch.cuda.stream(_LAUNCH_STREAM) if _LAUNCH_STREAM is not None else _NO_STREAM
+
+
 def _empty(*shape, **kw):
-    if _LAUNCH_STREAM is not None:
-        with torch.cuda.stream(_LAUNCH_STREAM):
-            return torch.empty(*shape, **kw)
-    return torch.empty(*shape, **kw)
+    with _on_launch_stream():
+        return torch.empty(*shape, **kw)
+
+
+def _zeros(*shape, **kw):
+    """zero-filled where it was allocated (for what a kernel accumulates into)"""
+    with _on_launch_stream():
+        return torch.empty(*shape, **kw).zero_()
 
 
 class launch_on(object):
@@ -499,12 +511,17 @@ def _cov_struct(p, Din, H, Dout, name):
     W1, b1, Wm, bm, Ws, bs = p
     _chk(Wm, (H, Dout), name + ".W_mu"); _chk(bm, (Dout,), name + ".b_mu")
     _chk(Ws, (H, Dout), name + ".W_sigma"); _chk(bs, (Dout,), name + ".b_sigma")
-    if _LAUNCH_STREAM is not None:
-        with torch.cuda.stream(_LAUNCH_STREAM):
-            W2, b2 = torch.cat([Wm, Ws], dim=1).contiguous(), torch.cat([bm, bs]).contiguous()
-    else:
+    with _on_launch_stream():
         W2, b2 = torch.cat([Wm, Ws], dim=1).contiguous(), torch.cat([bm, bs]).contiguous()
     return _mlp_struct((W1, b1, W2, b2), Din, H, 2 * Dout, name), (W2, b2)
+
+
+def _head_grads(p, X, rows_mu, rows_sig, Din, H, Dout, axis=2):
+    """[W1 | b1 | W_head | b_head] of each head from its rows -> (dW1, db1, dW_mu, db_mu, dW_sigma, db_sigma)"""
+    W1, b1, Wm, bm, Ws, bs = p
+    gm = split_mlp_grad(mlp_wgrad(X, rows_mu, (W1, b1, Wm, bm), Din, H, Dout, axis=axis), Din, H, Dout)
+    gs = split_mlp_grad(mlp_wgrad(X, rows_sig, (W1, b1, Ws, bs), Din, H, Dout, axis=axis), Din, H, Dout)
+    return (gm[0] + gs[0], gm[1] + gs[1], gm[2], gm[3], gs[2], gs[3])
 
 
 def filter_forward_cov(desc, q1, f, g, sigc_q1, sigc_f, sigc_g, mu2, sig2, m0, sig0, fm0, fsig0, obs, eps,
@@ -578,28 +595,25 @@ def filter_backward_cov(desc, q1, f, g, sigc_q1, sigc_f, sigc_g, mu2, sig2, m0, 
     _mark("psvo_filter_backward_cov", 1)
     _lib.check(st, "psvo_filter_backward_cov")
     del k1, k2, k3
-
-    def head_grads(p, rows_pair, Dout):
-        """[W1 | b1 | W_head | b_head] of each head from its rows -> (dW1, db1, dW_mu, db_mu, dW_sigma, db_sigma)"""
-        W1, b1, Wm, bm, Ws, bs = p
-        gm = split_mlp_grad(mlp_wgrad(filt["X"], rows_pair[0], (W1, b1, Wm, bm), Dx, H, Dout), Dx, H, Dout)
-        gs_ = split_mlp_grad(mlp_wgrad(filt["X"], rows_pair[1], (W1, b1, Ws, bs), Dx, H, Dout), Dx, H, Dout)
-        return (gm[0] + gs_[0], gm[1] + gs_[1], gm[2], gm[3], gs_[2], gs_[3])
-    out["gq1"] = head_grads(q1, out["dP"], Dx)
-    out["gf"] = None if boot else head_grads(f, out["dF"], Dx)
-    out["gg"] = head_grads(g, out["dG"], Dy)
+    out["gq1"] = _head_grads(q1, filt["X"], *out["dP"], Dx, H, Dx)
+    out["gf"] = None if boot else _head_grads(f, filt["X"], *out["dF"], Dx, H, Dx)
+    out["gg"] = _head_grads(g, filt["X"], *out["dG"], Dx, H, Dy)
     return out
 
 
-def bsim_forward_cov(desc, filt, f, g, q1_inv, sigc_f, sigc_g, sigc_q1inv, bmu2, bsig2, minit, sinit, imean, isig,
-                     obs, eps_b, u_b=None, sel_in=None, save=False):
-    """psvo_bsim_forward_cov.  Returns dict(bwX, flp, glp, Omega, sel, score[, lam, om, mu1, s1])."""
-    lib = _lib.load()
-    B, T, N, M, Dx, Dy, H = desc.B, desc.T, desc.N, desc.M, desc.Dx, desc.Dy, desc.H
-    dev = eps_b.device
+# The cov backward simulations (PSVO: bsim_*_cov, PSVOwR: bsimwr_*_cov) take the same inputs ahead of their own and their reverse
+# launches write the same outputs: what the four wrappers share is below; the argument lists mirror include/psvo_hip.h in each.
+def _bsim_cov_structs(desc, f, g, q1_inv):
+    """the psvo_mlp structs of f, g, q1_inv, and their concatenated heads: keep those until the launch has been issued"""
+    Dx, Dy, H = desc.Dx, desc.Dy, desc.H
     fs, k1 = _cov_struct(f, Dx, H, Dx, "f")
     gs, k2 = _cov_struct(g, Dx, H, Dy, "g")
     qs, k3 = _cov_struct(q1_inv, Dx, H, Dx, "q1_inv")
+    return fs, gs, qs, (k1, k2, k3)
+
+
+def _bsim_cov_chk(desc, filt, sigc_f, sigc_g, sigc_q1inv, bmu2, bsig2, minit, sinit, imean, isig, obs, eps_b, u_b, sel_in):
+    B, T, N, M, Dx, Dy = desc.B, desc.T, desc.N, desc.M, desc.Dx, desc.Dy
     _chk(filt["Fm"], (T, B, Dx, N), "Fm"); _chk(filt["Fs"], (T, B, Dx, N), "Fs")
     _chk(filt["logW"], (T, B, N), "logW"); _chk(filt["lse"], (T, B), "lse")
     _chk(sigc_f, (Dx,), "sigc_f"); _chk(sigc_g, (Dy,), "sigc_g"); _chk(sigc_q1inv, (Dx,), "sigc_q1inv")
@@ -608,13 +622,55 @@ def bsim_forward_cov(desc, filt, f, g, q1_inv, sigc_f, sigc_g, sigc_q1inv, bmu2,
         _chk(t, (B, Dx), nm)
     _chk(obs, (T, B, Dy), "obs"); _chk(eps_b, (T, B, Dx, N, M), "eps_b")
     _chk(u_b, (T, B, N), "u_b"); _chk(sel_in, (T, B, N), "sel_in", torch.int32)
+
+
+def _bsim_cov_saves(desc, dev, save):
+    """what the reverse launch reads back (allocated when a reverse pass will follow)"""
+    B, T, N, M, Dx = desc.B, desc.T, desc.N, desc.M, desc.Dx
+    z = lambda *s: _empty(*s, device=dev) if save else None
+    return {"lam": z(T, B, N, M), "om": z(T, B, N, M), "mu1": z(T, B, Dx, N), "s1": z(T, B, Dx, N)}
+
+
+def _bsim_cov_grads(desc, dev):
+    """the outputs of both reverse launches: the rows for psvo_mlp_wgrad, and the gradients the kernel accumulates into"""
+    B, T, N, M, Dx, Dy = desc.B, desc.T, desc.N, desc.M, desc.Dx, desc.Dy
+    z = lambda *s: _empty(*s, device=dev)
+    zeros = lambda *s: _zeros(*s, device=dev)
+    return {"xt": z(T, B, Dx, N, M), "dFt": z(T, B, Dx, N, M), "dFts": z(T, B, Dx, N, M), "dGt": z(T, B, Dy, N, M),
+            "dGts": z(T, B, Dy, N, M), "dmu1": z(T, B, Dx, N), "dmu1s": z(T, B, Dx, N),
+            # accumulated with float atomics by the kernel
+            "dFm": zeros(T, B, Dx, N), "dFs": zeros(T, B, Dx, N), "dlogW": zeros(T, B, N), "dlse": zeros(T, B),
+            "dbmu2": zeros(T, B, Dx), "dbsig2": zeros(T, B, Dx), "dminit": zeros(B, Dx), "dsinit": zeros(B, Dx),
+            "dimean": zeros(B, Dx), "disig": zeros(B, Dx), "dsigc_f": zeros(Dx), "dsigc_g": zeros(Dy),
+            "dsigc_q1inv": zeros(Dx)}
+
+
+def _bsim_cov_det_ws(lib, desc, dev, det):
+    """the fixed-order route's per-workgroup slices; allocated only in the mode"""
+    return _empty(lib.psvo_bsim_cov_det_ws_floats(desc.B, desc.N, desc.M, desc.Dx, desc.Dy), device=dev) if det else None
+
+
+def _bsim_cov_head_grads(out, desc, f, g, q1_inv, x_next):
+    """gf / gg / gq1inv (6-tuples in the order of the MLP tuples) from the rows; x_next: what MLP_q1inv was evaluated at"""
+    T, Dx, Dy, H = desc.T, desc.Dx, desc.Dy, desc.H
+    out["gf"] = _head_grads(f, out["xt"][:T - 1], out["dFt"][:T - 1], out["dFts"][:T - 1], Dx, H, Dx)
+    out["gg"] = _head_grads(g, out["xt"], out["dGt"], out["dGts"], Dx, H, Dy)
+    out["gq1inv"] = _head_grads(q1_inv, x_next[1:], out["dmu1"][:T - 1], out["dmu1s"][:T - 1], Dx, H, Dx)
+
+
+def bsim_forward_cov(desc, filt, f, g, q1_inv, sigc_f, sigc_g, sigc_q1inv, bmu2, bsig2, minit, sinit, imean, isig,
+                     obs, eps_b, u_b=None, sel_in=None, save=False):
+    """psvo_bsim_forward_cov.  Returns dict(bwX, flp, glp, Omega, sel, score[, lam, om, mu1, s1])."""
+    lib = _lib.load()
+    B, T, N, Dx = desc.B, desc.T, desc.N, desc.Dx
+    dev = eps_b.device
+    fs, gs, qs, keep = _bsim_cov_structs(desc, f, g, q1_inv)
+    _bsim_cov_chk(desc, filt, sigc_f, sigc_g, sigc_q1inv, bmu2, bsig2, minit, sinit, imean, isig, obs, eps_b, u_b, sel_in)
     if u_b is None and sel_in is None:
         raise ValueError("the backward simulation needs uniforms `u_b` or teacher-forced `sel_in`")
     z = lambda *s: _empty(*s, device=dev)
     out = {"bwX": z(T, B, Dx, N), "flp": z(T, B, N), "glp": z(T, B, N), "Omega": z(T, B, N),
-           "sel": _empty(T, B, N, device=dev, dtype=torch.int32), "score": z(B, N),
-           "lam": z(T, B, N, M) if save else None, "om": z(T, B, N, M) if save else None,
-           "mu1": z(T, B, Dx, N) if save else None, "s1": z(T, B, Dx, N) if save else None}
+           "sel": _empty(T, B, N, device=dev, dtype=torch.int32), "score": z(B, N), **_bsim_cov_saves(desc, dev, save)}
     _mark("psvo_bsim_forward_cov", 0)
     st = lib.psvo_bsim_forward_cov(
         ctypes.byref(desc), _ptr(filt["Fm"]), _ptr(filt["Fs"]), _ptr(filt["logW"]), _ptr(filt["lse"]),
@@ -624,7 +680,7 @@ def bsim_forward_cov(desc, filt, f, g, q1_inv, sigc_f, sigc_g, sigc_q1inv, bmu2,
         _ptr(out["score"]), _ptr(out["lam"]), _ptr(out["om"]), _ptr(out["mu1"]), _ptr(out["s1"]), _stream())
     _mark("psvo_bsim_forward_cov", 1)
     _lib.check(st, "psvo_bsim_forward_cov")
-    del k1, k2, k3
+    del keep
     return out
 
 
@@ -633,31 +689,13 @@ def bsim_backward_cov(desc, filt, f, g, q1_inv, sigc_f, sigc_g, sigc_q1inv, bmu2
     """psvo_bsim_backward_cov + two psvo_mlp_wgrad launches per MLP (one per head).  `bs` = the forward call's outputs with
     its saves.  Returns a dict of gradients; gf / gg / gq1inv are 6-tuples in the order of the MLP tuples."""
     lib = _lib.load()
-    B, T, N, M, Dx, Dy, H = desc.B, desc.T, desc.N, desc.M, desc.Dx, desc.Dy, desc.H
     dev = eps_b.device
-    fs, k1 = _cov_struct(f, Dx, H, Dx, "f")
-    gs, k2 = _cov_struct(g, Dx, H, Dy, "g")
-    qs, k3 = _cov_struct(q1_inv, Dx, H, Dx, "q1_inv")
-    _chk(dscore, (B, N), "dscore")
-    z = lambda *s: _empty(*s, device=dev)
-
-    def zeros(*s):
-        t = _empty(*s, device=dev)
-        if _LAUNCH_STREAM is not None:
-            with torch.cuda.stream(_LAUNCH_STREAM):
-                return t.zero_()
-        return t.zero_()
-    out = {"xt": z(T, B, Dx, N, M), "dFt": z(T, B, Dx, N, M), "dFts": z(T, B, Dx, N, M), "dGt": z(T, B, Dy, N, M),
-           "dGts": z(T, B, Dy, N, M), "dmu1": z(T, B, Dx, N), "dmu1s": z(T, B, Dx, N),
-           # accumulated with float atomics by the kernel
-           "dFm": zeros(T, B, Dx, N), "dFs": zeros(T, B, Dx, N), "dlogW": zeros(T, B, N), "dlse": zeros(T, B),
-           "dbmu2": zeros(T, B, Dx), "dbsig2": zeros(T, B, Dx), "dminit": zeros(B, Dx), "dsinit": zeros(B, Dx),
-           "dimean": zeros(B, Dx), "disig": zeros(B, Dx), "dsigc_f": zeros(Dx), "dsigc_g": zeros(Dy),
-           "dsigc_q1inv": zeros(Dx)}
+    fs, gs, qs, keep = _bsim_cov_structs(desc, f, g, q1_inv)
+    _chk(dscore, (desc.B, desc.N), "dscore")
+    out = _bsim_cov_grads(desc, dev)
     _mark("psvo_bsim_backward_cov", 0)
     with _fixed_order() as det:
-        # (the fixed-order route's per-workgroup slices; allocated only in the mode)
-        det_ws = z(lib.psvo_bsim_cov_det_ws_floats(B, N, M, Dx, Dy)) if det else None
+        det_ws = _bsim_cov_det_ws(lib, desc, dev, det)
         st = lib.psvo_bsim_backward_cov_ws(
             ctypes.byref(desc), _ptr(filt["Fm"]), _ptr(filt["Fs"]), _ptr(filt["logW"]), _ptr(filt["lse"]),
             ctypes.byref(fs), ctypes.byref(gs), ctypes.byref(qs), _ptr(sigc_f), _ptr(sigc_g), _ptr(sigc_q1inv),
@@ -670,16 +708,8 @@ def bsim_backward_cov(desc, filt, f, g, q1_inv, sigc_f, sigc_g, sigc_q1inv, bmu2
             _stream())
     _mark("psvo_bsim_backward_cov", 1)
     _lib.check(st, "psvo_bsim_backward_cov")
-    del k1, k2, k3
-
-    def head_grads(p, X, rows_mu, rows_sig, Dout, axis=2):
-        W1, b1, Wm, bm, Ws, bs_ = p
-        gm = split_mlp_grad(mlp_wgrad(X, rows_mu, (W1, b1, Wm, bm), Dx, H, Dout, axis=axis), Dx, H, Dout)
-        gs_ = split_mlp_grad(mlp_wgrad(X, rows_sig, (W1, b1, Ws, bs_), Dx, H, Dout, axis=axis), Dx, H, Dout)
-        return (gm[0] + gs_[0], gm[1] + gs_[1], gm[2], gm[3], gs_[2], gs_[3])
-    out["gf"] = head_grads(f, out["xt"][:T - 1], out["dFt"][:T - 1], out["dFts"][:T - 1], Dx)
-    out["gg"] = head_grads(g, out["xt"], out["dGt"], out["dGts"], Dy)
-    out["gq1inv"] = head_grads(q1_inv, bs["bwX"][1:], out["dmu1"][:T - 1], out["dmu1s"][:T - 1], Dx)
+    del keep
+    _bsim_cov_head_grads(out, desc, f, g, q1_inv, bs["bwX"])
     return out
 
 
@@ -688,28 +718,17 @@ def bsimwr_forward_cov(desc, filt, f, g, q1_inv, sigc_f, sigc_g, sigc_q1inv, bmu
     """psvo_bsimwr_forward_cov (PSVOwR, state-dependent scales).  Returns dict(bwX, bwXanc, bwW, lseW, sel, anc, omsel
     [, lam, om, mu1, s1])."""
     lib = _lib.load()
-    B, T, N, M, Dx, Dy, H = desc.B, desc.T, desc.N, desc.M, desc.Dx, desc.Dy, desc.H
+    B, T, N, Dx = desc.B, desc.T, desc.N, desc.Dx
     dev = eps_b.device
-    fs, k1 = _cov_struct(f, Dx, H, Dx, "f")
-    gs, k2 = _cov_struct(g, Dx, H, Dy, "g")
-    qs, k3 = _cov_struct(q1_inv, Dx, H, Dx, "q1_inv")
-    _chk(filt["Fm"], (T, B, Dx, N), "Fm"); _chk(filt["Fs"], (T, B, Dx, N), "Fs")
-    _chk(filt["logW"], (T, B, N), "logW"); _chk(filt["lse"], (T, B), "lse")
-    _chk(sigc_f, (Dx,), "sigc_f"); _chk(sigc_g, (Dy,), "sigc_g"); _chk(sigc_q1inv, (Dx,), "sigc_q1inv")
-    _chk(bmu2, (T, B, Dx), "bmu2"); _chk(bsig2, (T, B, Dx), "bsig2")
-    for t, nm in ((minit, "minit"), (sinit, "sinit"), (imean, "imean"), (isig, "isig")):
-        _chk(t, (B, Dx), nm)
-    _chk(obs, (T, B, Dy), "obs"); _chk(eps_b, (T, B, Dx, N, M), "eps_b")
-    _chk(u_b, (T, B, N), "u_b"); _chk(sel_in, (T, B, N), "sel_in", torch.int32)
+    fs, gs, qs, keep = _bsim_cov_structs(desc, f, g, q1_inv)
+    _bsim_cov_chk(desc, filt, sigc_f, sigc_g, sigc_q1inv, bmu2, bsig2, minit, sinit, imean, isig, obs, eps_b, u_b, sel_in)
     _chk(u_r, (T, B, N), "u_r"); _chk(anc_in, (T, B, N), "anc_in", torch.int32)
     if (u_b is None and sel_in is None) or (u_r is None and anc_in is None):
         raise ValueError("PSVOwR needs uniforms (`u_b`, `u_r`) or teacher-forced indices (`sel_in`, `anc_in`)")
     z = lambda *s: _empty(*s, device=dev)
     zi = lambda *s: _empty(*s, device=dev, dtype=torch.int32)
     out = {"bwX": z(T, B, Dx, N), "bwXanc": z(T, B, Dx, N), "bwW": z(T, B, N), "lseW": z(T, B), "sel": zi(T, B, N),
-           "anc": zi(T, B, N), "omsel": z(T, B, N),
-           "lam": z(T, B, N, M) if save else None, "om": z(T, B, N, M) if save else None,
-           "mu1": z(T, B, Dx, N) if save else None, "s1": z(T, B, Dx, N) if save else None}
+           "anc": zi(T, B, N), "omsel": z(T, B, N), **_bsim_cov_saves(desc, dev, save)}
     _mark("psvo_bsimwr_forward_cov", 0)
     st = lib.psvo_bsimwr_forward_cov(
         ctypes.byref(desc), _ptr(filt["Fm"]), _ptr(filt["Fs"]), _ptr(filt["logW"]), _ptr(filt["lse"]),
@@ -720,7 +739,7 @@ def bsimwr_forward_cov(desc, filt, f, g, q1_inv, sigc_f, sigc_g, sigc_q1inv, bmu
         _ptr(out["s1"]), _stream())
     _mark("psvo_bsimwr_forward_cov", 1)
     _lib.check(st, "psvo_bsimwr_forward_cov")
-    del k1, k2, k3
+    del keep
     return out
 
 
@@ -728,30 +747,14 @@ def bsimwr_backward_cov(desc, filt, f, g, q1_inv, sigc_f, sigc_g, sigc_q1inv, bm
                         obs, eps_b, bs, dlseW):
     """psvo_bsimwr_backward_cov + two psvo_mlp_wgrad launches per MLP.  `bs` = the forward call's outputs with its saves."""
     lib = _lib.load()
-    B, T, N, M, Dx, Dy, H = desc.B, desc.T, desc.N, desc.M, desc.Dx, desc.Dy, desc.H
     dev = eps_b.device
-    fs, k1 = _cov_struct(f, Dx, H, Dx, "f")
-    gs, k2 = _cov_struct(g, Dx, H, Dy, "g")
-    qs, k3 = _cov_struct(q1_inv, Dx, H, Dx, "q1_inv")
-    _chk(dlseW, (T, B), "dlseW")
-    z = lambda *s: _empty(*s, device=dev)
-
-    def zeros(*s):
-        t = _empty(*s, device=dev)
-        if _LAUNCH_STREAM is not None:
-            with torch.cuda.stream(_LAUNCH_STREAM):
-                return t.zero_()
-        return t.zero_()
-    out = {"xt": z(T, B, Dx, N, M), "dFt": z(T, B, Dx, N, M), "dFts": z(T, B, Dx, N, M), "dGt": z(T, B, Dy, N, M),
-           "dGts": z(T, B, Dy, N, M), "dmu1": z(T, B, Dx, N), "dmu1s": z(T, B, Dx, N),
-           "dFm": zeros(T, B, Dx, N), "dFs": zeros(T, B, Dx, N), "dlogW": zeros(T, B, N), "dlse": zeros(T, B),
-           "dbmu2": zeros(T, B, Dx), "dbsig2": zeros(T, B, Dx), "dminit": zeros(B, Dx), "dsinit": zeros(B, Dx),
-           "dimean": zeros(B, Dx), "disig": zeros(B, Dx), "dsigc_f": zeros(Dx), "dsigc_g": zeros(Dy),
-           "dsigc_q1inv": zeros(Dx)}
-    dXs = zeros(T, B, Dx, N)
+    fs, gs, qs, keep = _bsim_cov_structs(desc, f, g, q1_inv)
+    _chk(dlseW, (desc.T, desc.B), "dlseW")
+    out = _bsim_cov_grads(desc, dev)
+    dXs = _zeros(desc.T, desc.B, desc.Dx, desc.N, device=dev)
     _mark("psvo_bsimwr_backward_cov", 0)
     with _fixed_order() as det:
-        det_ws = z(lib.psvo_bsim_cov_det_ws_floats(B, N, M, Dx, Dy)) if det else None
+        det_ws = _bsim_cov_det_ws(lib, desc, dev, det)
         st = lib.psvo_bsimwr_backward_cov_ws(
             ctypes.byref(desc), _ptr(filt["Fm"]), _ptr(filt["Fs"]), _ptr(filt["logW"]), _ptr(filt["lse"]),
             ctypes.byref(fs), ctypes.byref(gs), ctypes.byref(qs), _ptr(sigc_f), _ptr(sigc_g), _ptr(sigc_q1inv),
@@ -765,16 +768,8 @@ def bsimwr_backward_cov(desc, filt, f, g, q1_inv, sigc_f, sigc_g, sigc_q1inv, bm
             _ptr(det_ws), _stream())
     _mark("psvo_bsimwr_backward_cov", 1)
     _lib.check(st, "psvo_bsimwr_backward_cov")
-    del k1, k2, k3
-
-    def head_grads(p, X, rows_mu, rows_sig, Dout):
-        W1, b1, Wm, bm, Ws, bs_ = p
-        gm = split_mlp_grad(mlp_wgrad(X, rows_mu, (W1, b1, Wm, bm), Dx, H, Dout), Dx, H, Dout)
-        gs_ = split_mlp_grad(mlp_wgrad(X, rows_sig, (W1, b1, Ws, bs_), Dx, H, Dout), Dx, H, Dout)
-        return (gm[0] + gs_[0], gm[1] + gs_[1], gm[2], gm[3], gs_[2], gs_[3])
-    out["gf"] = head_grads(f, out["xt"][:T - 1], out["dFt"][:T - 1], out["dFts"][:T - 1], Dx)
-    out["gg"] = head_grads(g, out["xt"], out["dGt"], out["dGts"], Dy)
-    out["gq1inv"] = head_grads(q1_inv, bs["bwXanc"][1:], out["dmu1"][:T - 1], out["dmu1s"][:T - 1], Dx)
+    del keep
+    _bsim_cov_head_grads(out, desc, f, g, q1_inv, bs["bwXanc"])
     return out
 
 

@@ -27,6 +27,42 @@ def test_header_symbols_are_exported_and_bound(built_lib):
         assert n in names, "%s is bound but not declared in include/psvo_hip.h" % n
 
 
+def _declared_parameters():
+    """{function: [parameter declarations]} of include/psvo_hip.h, comments stripped as in _declared_symbols()"""
+    txt = open(os.path.join(ROOT, "include", "psvo_hip.h")).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    out = {}
+    for name, params in re.findall(r"\b(psvo_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", txt):
+        params = " ".join(params.split())
+        out[name] = [] if params in ("", "void") else [q.strip() for q in params.split(",")]
+    return out
+
+
+def test_bound_signatures_match_the_header():
+    """the hand-counted ctypes argument lists of psvo_amd/_lib.py: as many parameters as include/psvo_hip.h declares for the
+    function, each of the matching ctypes type (a miscount would be silent stack garbage at the call)"""
+    from psvo_amd import _lib
+    declared = _declared_parameters()
+    assert sorted(declared) == _declared_symbols()
+    assert sorted(declared) == sorted(_lib.SIGNATURES)
+
+    def ctype_of(decl):
+        ty = re.sub(r"\bconst\b", " ", decl)
+        ty = " ".join(re.sub(r"[A-Za-z_][A-Za-z0-9_]*$", "", ty.strip()).split()).replace(" *", "*")    # (drop the name)
+        if ty == "psvo_desc*":
+            return ctypes.POINTER(_lib.psvo_desc)
+        if ty == "psvo_mlp*":
+            return ctypes.POINTER(_lib.psvo_mlp)
+        if ty.endswith("*"):
+            return ctypes.c_void_p
+        return {"int": ctypes.c_int, "long long": ctypes.c_longlong, "float": ctypes.c_float}[ty]
+    for name, params in declared.items():
+        bound = _lib.SIGNATURES[name][1]
+        assert len(bound) == len(params), "%s: the header declares %d parameters, _lib.py binds %d" % (name, len(params), len(bound))
+        for i, (decl, ty) in enumerate(zip(params, bound)):
+            assert ty is ctype_of(decl), "%s: parameter %d (`%s`) is bound as %s" % (name, i, decl, ty.__name__)
+
+
 def test_version_and_status_strings(built_lib):
     from psvo_amd import _lib
     lib = _lib.load()
