@@ -112,7 +112,7 @@ extern "C" int psvo_bsim_backward(
         !dminit_rows || !dimean_rows || !sacc_part)
         return PSVO_ERR_INVALID;
     if (desc->B <= 0 || desc->T < 2 || desc->N <= 0 || desc->M <= 0) return PSVO_ERR_INVALID;
-    if (desc->N > 1024 || desc->B > 65535 || !desc_layers_ok(desc)) return PSVO_ERR_UNSUPPORTED;
+    if (desc->N > 1024 || desc->B > 65535) return PSVO_ERR_UNSUPPORTED;
 
     BsimBwdArgs a;
     a.skew = 0;
@@ -129,43 +129,13 @@ extern "C" int psvo_bsim_backward(
     BsimBwdOut o{};      // (the folds are psvo_bsim_backward_fold's)
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int variant = bsim_bwd_variant(desc->B, desc->T, desc->N, desc->M, desc->Dx, desc->Dy, desc->layers);
-    if (variant != 0) {
-        switch (desc->Dx) {
-            case 2: return bb2_dispatch_dy<2>(a, o, desc->Dy, desc->H, desc->M, variant - 1, s);
-            case 3: return bb2_dispatch_dy<3>(a, o, desc->Dy, desc->H, desc->M, variant - 1, s);
-            case 4: return bb2_dispatch_dy<4>(a, o, desc->Dy, desc->H, desc->M, variant - 1, s);
-            default: return PSVO_ERR_UNSUPPORTED;
-        }
-    }
-    if (desc->layers == 2) {
-        if (!f->Wh || !f->bh || !g->Wh || !g->bh || !q1_inv->Wh || !q1_inv->bh) return PSVO_ERR_INVALID;
-        switch (desc->Dx) {
-            case 2: return l2::bb_dispatch_dy<2>(a, o, desc->Dy, desc->H, desc->M, s);
-            case 3: return l2::bb_dispatch_dy<3>(a, o, desc->Dy, desc->H, desc->M, s);
-            case 4: return l2::bb_dispatch_dy<4>(a, o, desc->Dy, desc->H, desc->M, s);
-            default: return PSVO_ERR_UNSUPPORTED;
-        }
-    }
-    switch (desc->Dx) {
-        case 2: return bb_dispatch_dy<2>(a, o, desc->Dy, desc->H, desc->M, s);
-        case 3: return bb_dispatch_dy<3>(a, o, desc->Dy, desc->H, desc->M, s);
-        case 4: return bb_dispatch_dy<4>(a, o, desc->Dy, desc->H, desc->M, s);
-        default: return PSVO_ERR_UNSUPPORTED;
-    }
+    if (desc->layers == 2 && (!f->Wh || !f->bh || !g->Wh || !g->bh || !q1_inv->Wh || !q1_inv->bh)) return PSVO_ERR_INVALID;
+    return pick_dx(desc->Dx, [&](auto dx) {
+        if (variant != 0) return bb2_dispatch_dy<dx()>(a, o, desc->Dy, desc->H, desc->M, variant - 1, s);
+        if (desc->layers == 2) return l2::bb_dispatch_dy<dx()>(a, o, desc->Dy, desc->H, desc->M, s);
+        return bb_dispatch_dy<dx()>(a, o, desc->Dy, desc->H, desc->M, s);
+    });
 }
-
-namespace psvo {
-template <int DX>
-static int fold_dispatch_dy(const BsimBwdArgs& a, const BsimBwdOut& o, int Dy, int nblk, hipStream_t s) {
-    clear_hip_error();
-    switch (Dy) {
-        case 1: launch_bsim_fold_finalize<DX, 1>(a, o, nblk, s); break;
-        case 2: launch_bsim_fold_finalize<DX, 2>(a, o, nblk, s); break;
-        default: return PSVO_ERR_UNSUPPORTED;
-    }
-    return launch_status();
-}
-}  // namespace psvo
 
 extern "C" int psvo_bsim_backward_fold(const psvo_desc* desc, const float* dFm_part, const float* dlogW_part,
                                        const float* sacc_part, const float* sig_q1inv, const float* sig_bq2, float* dFm,
@@ -184,10 +154,11 @@ extern "C" int psvo_bsim_backward_fold(const psvo_desc* desc, const float* dFm_p
     BsimBwdOut o{dsig_f, dsig_g, dsig_q1inv, dsig_bq2, dsig_init, disig, dFm, dlogW, dlse};
     const int nblk = psvo_bsim_blocks(desc);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (desc->Dx) {
-        case 2: return fold_dispatch_dy<2>(a, o, desc->Dy, nblk, s);
-        case 3: return fold_dispatch_dy<3>(a, o, desc->Dy, nblk, s);
-        case 4: return fold_dispatch_dy<4>(a, o, desc->Dy, nblk, s);
-        default: return PSVO_ERR_UNSUPPORTED;
-    }
+    return pick_dx(desc->Dx, [&](auto dx) {
+        return pick_dy(desc->Dy, [&](auto dy) {
+            clear_hip_error();
+            launch_bsim_fold_finalize<decltype(dx)::value, dy()>(a, o, nblk, s);
+            return launch_status();
+        });
+    });
 }

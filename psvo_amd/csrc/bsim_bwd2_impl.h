@@ -1005,9 +1005,9 @@ static inline void bsim2_geometry(int N, int M, int& cpb, int& nblk) {
     nblk = (N + cpb - 1) / cpb;
 }
 
-// v2 covers M in {4, 8, 16, 32} and arrays below 4 GiB (32-bit byte offsets)
+// v2 covers the M of the envelope (common.h) and arrays below 4 GiB (32-bit byte offsets)
 static inline bool bsim2_supported(int B, int T, int N, int M, int Dx, int Dy) {
-    if (!(M == 4 || M == 8 || M == 16 || M == 32)) return false;
+    if (pick_m(M, [](auto) { return PSVO_OK; }) != PSVO_OK) return false;
     const long long big = (long long)T * B * (Dx > Dy ? Dx : Dy) * N * M * 4;
     return big < (1ll << 32);
 }
@@ -1045,35 +1045,12 @@ static int launch_bsim_bwd2(const BsimBwdArgs& a, const BsimBwdOut& o, int jm, h
     return launch_status();
 }
 
-template <int DX, int DY, int H>
-static int bb2_dispatch_m(const BsimBwdArgs& a, const BsimBwdOut& o, int M, int jm, hipStream_t s) {
-    switch (M) {
-        case 4: return launch_bsim_bwd2<DX, DY, H, 4>(a, o, jm, s);
-        case 8: return launch_bsim_bwd2<DX, DY, H, 8>(a, o, jm, s);
-        case 16: return launch_bsim_bwd2<DX, DY, H, 16>(a, o, jm, s);
-        case 32: return launch_bsim_bwd2<DX, DY, H, 32>(a, o, jm, s);
-        default: return PSVO_ERR_UNSUPPORTED;
-    }
-}
-
-template <int DX, int DY>
-static int bb2_dispatch_h(const BsimBwdArgs& a, const BsimBwdOut& o, int H, int M, int jm, hipStream_t s) {
-    switch (H) {
-        case 16: return bb2_dispatch_m<DX, DY, 16>(a, o, M, jm, s);
-        case 32: return bb2_dispatch_m<DX, DY, 32>(a, o, M, jm, s);
-        case 64: return bb2_dispatch_m<DX, DY, 64>(a, o, M, jm, s);
-        default: return PSVO_ERR_UNSUPPORTED;
-    }
-}
-
 // external linkage: explicitly instantiated once per DX in bsim_bwd2_dx{2,3,4}.hip
 template <int DX>
 int bb2_dispatch_dy(const BsimBwdArgs& a, const BsimBwdOut& o, int Dy, int H, int M, int jm, hipStream_t s) {
-    switch (Dy) {
-        case 1: return bb2_dispatch_h<DX, 1>(a, o, H, M, jm, s);
-        case 2: return bb2_dispatch_h<DX, 2>(a, o, H, M, jm, s);
-        default: return PSVO_ERR_UNSUPPORTED;
-    }
+    // (hidden: the closure of a template with external linkage would otherwise be a symbol of the library)
+    return dispatch_dy_h_m(Dy, H, M, [&](auto dy, auto h, auto m) __attribute__((visibility("hidden"))) {
+        return launch_bsim_bwd2<DX, dy(), h(), m()>(a, o, jm, s); });
 }
 
 }  // namespace psvo

@@ -781,37 +781,12 @@ static int launch_bsim_bwd(const BsimBwdArgs& a, const BsimBwdOut& o, hipStream_
     return launch_status();
 }
 
-template <int DX, int DY, int H>
-static int bb_dispatch_m(const BsimBwdArgs& a, const BsimBwdOut& o, int M, hipStream_t s) {
-    switch (M) {
-        case 4: return launch_bsim_bwd<DX, DY, H, 4>(a, o, s);
-        case 8: return launch_bsim_bwd<DX, DY, H, 8>(a, o, s);
-        case 16: return launch_bsim_bwd<DX, DY, H, 16>(a, o, s);
-        case 32: return launch_bsim_bwd<DX, DY, H, 32>(a, o, s);
-        default: return PSVO_ERR_UNSUPPORTED;
-    }
-}
-
-template <int DX, int DY>
-static int bb_dispatch_h(const BsimBwdArgs& a, const BsimBwdOut& o, int H, int M, hipStream_t s) {
-    switch (H) {
-#if PSVO_L == 1   // (two hidden layers: widths 32 and 64; narrower ones are zero-padded upstream)
-        case 16: return bb_dispatch_m<DX, DY, 16>(a, o, M, s);
-#endif
-        case 32: return bb_dispatch_m<DX, DY, 32>(a, o, M, s);
-        case 64: return bb_dispatch_m<DX, DY, 64>(a, o, M, s);
-        default: return PSVO_ERR_UNSUPPORTED;
-    }
-}
-
 // external linkage: explicitly instantiated once per DX in bsim_bwd_dx{2,3,4}.hip (compiled in parallel)
 template <int DX>
 int bb_dispatch_dy(const BsimBwdArgs& a, const BsimBwdOut& o, int Dy, int H, int M, hipStream_t s) {
-    switch (Dy) {
-        case 1: return bb_dispatch_h<DX, 1>(a, o, H, M, s);
-        case 2: return bb_dispatch_h<DX, 2>(a, o, H, M, s);
-        default: return PSVO_ERR_UNSUPPORTED;
-    }
+    // (hidden: the closure of a template with external linkage would otherwise be a symbol of the library)
+    return dispatch_dy_h_m(Dy, H, M, [&](auto dy, auto h, auto m) __attribute__((visibility("hidden"))) {
+        return launch_bsim_bwd<DX, dy(), h(), m()>(a, o, s); });
 }
 }  // inline namespace PSVO_LNS
 

@@ -1103,40 +1103,6 @@ static int launch_bwd(const BwdArgs& a, hipStream_t stream) {
     return launch_status();
 }
 
-#define PSVO_COVB_M(LAUNCH, DX_, DY_, H_, ...)                                      \
-    switch (desc->M) {                                                              \
-        case 4: return LAUNCH<DX_, DY_, H_, 4>(__VA_ARGS__);                        \
-        case 8: return LAUNCH<DX_, DY_, H_, 8>(__VA_ARGS__);                        \
-        case 16: return LAUNCH<DX_, DY_, H_, 16>(__VA_ARGS__);                      \
-        case 32: return LAUNCH<DX_, DY_, H_, 32>(__VA_ARGS__);                      \
-        default: return PSVO_ERR_UNSUPPORTED;                                       \
-    }
-#define PSVO_COVB_DISPATCH(LAUNCH, ...)                                             \
-    do {                                                                            \
-        const int key = desc->Dx * 1000 + desc->Dy * 100 + desc->H;                 \
-        switch (key) {                                                              \
-            case 2116: PSVO_COVB_M(LAUNCH, 2, 1, 16, __VA_ARGS__)                   \
-            case 2132: PSVO_COVB_M(LAUNCH, 2, 1, 32, __VA_ARGS__)                   \
-            case 2164: PSVO_COVB_M(LAUNCH, 2, 1, 64, __VA_ARGS__)                   \
-            case 2216: PSVO_COVB_M(LAUNCH, 2, 2, 16, __VA_ARGS__)                   \
-            case 2232: PSVO_COVB_M(LAUNCH, 2, 2, 32, __VA_ARGS__)                   \
-            case 2264: PSVO_COVB_M(LAUNCH, 2, 2, 64, __VA_ARGS__)                   \
-            case 3116: PSVO_COVB_M(LAUNCH, 3, 1, 16, __VA_ARGS__)                   \
-            case 3132: PSVO_COVB_M(LAUNCH, 3, 1, 32, __VA_ARGS__)                   \
-            case 3164: PSVO_COVB_M(LAUNCH, 3, 1, 64, __VA_ARGS__)                   \
-            case 3216: PSVO_COVB_M(LAUNCH, 3, 2, 16, __VA_ARGS__)                   \
-            case 3232: PSVO_COVB_M(LAUNCH, 3, 2, 32, __VA_ARGS__)                   \
-            case 3264: PSVO_COVB_M(LAUNCH, 3, 2, 64, __VA_ARGS__)                   \
-            case 4116: PSVO_COVB_M(LAUNCH, 4, 1, 16, __VA_ARGS__)                   \
-            case 4132: PSVO_COVB_M(LAUNCH, 4, 1, 32, __VA_ARGS__)                   \
-            case 4164: PSVO_COVB_M(LAUNCH, 4, 1, 64, __VA_ARGS__)                   \
-            case 4216: PSVO_COVB_M(LAUNCH, 4, 2, 16, __VA_ARGS__)                   \
-            case 4232: PSVO_COVB_M(LAUNCH, 4, 2, 32, __VA_ARGS__)                   \
-            case 4264: PSVO_COVB_M(LAUNCH, 4, 2, 64, __VA_ARGS__)                   \
-            default: return PSVO_ERR_UNSUPPORTED;                                   \
-        }                                                                           \
-    } while (0)
-
 // The DET workspace (psvo_bsim_cov_det_ws_floats): the four DET arrays of BwdArgs one after the other, sizes in floats
 struct DetWs {
     size_t jpart, cpart, spart, dxc;
@@ -1244,7 +1210,9 @@ extern "C" int psvo_bsim_forward_cov(const psvo_desc* desc, const float* Fm, con
     a.flp = flp; a.glp = glp; a.Omega = Omega; a.score = score;
     a.t_hi = desc->T - 1; a.t_lo = 0; a.u_r = nullptr; a.anc_in = nullptr;
     a.bwXanc = a.bwW = a.omsel = nullptr; a.anc_out = nullptr;
-    PSVO_COVB_DISPATCH(launch_fwd, a, static_cast<hipStream_t>(stream));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return psvo::dispatch_shape_m(desc->Dx, desc->Dy, desc->H, desc->M, [&](auto dx, auto dy, auto h, auto m) {
+        return launch_fwd<dx(), dy(), h(), m()>(a, s); });
 }
 
 extern "C" int psvo_bsim_backward_cov_ws(
@@ -1266,7 +1234,9 @@ extern "C" int psvo_bsim_backward_cov_ws(
     a.bwX = bwX; a.dscore = dscore;
     a.t_lo = a.t_hi = -1;       // persistent over all steps
     a.bwXanc = a.bwW = a.lseW = a.dlseW = nullptr; a.anc = nullptr; a.dXs = nullptr;
-    PSVO_COVB_DISPATCH(launch_bwd, a, static_cast<hipStream_t>(stream));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return psvo::dispatch_shape_m(desc->Dx, desc->Dy, desc->H, desc->M, [&](auto dx, auto dy, auto h, auto m) {
+        return launch_bwd<dx(), dy(), h(), m()>(a, s); });
 }
 
 extern "C" int psvo_bsim_backward_cov(
@@ -1301,7 +1271,9 @@ extern "C" int psvo_bsimwr_forward_cov(
     a.flp = nullptr; a.glp = nullptr; a.Omega = nullptr; a.score = nullptr;
     a.t_hi = a.t_lo = 0; a.u_r = u_r; a.anc_in = anc_in;
     a.bwXanc = bwXanc; a.bwW = bwW; a.omsel = omsel; a.anc_out = anc_out;
-    PSVO_COVB_DISPATCH(launch_fwd_wr, a, lseW, static_cast<hipStream_t>(stream));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return psvo::dispatch_shape_m(desc->Dx, desc->Dy, desc->H, desc->M, [&](auto dx, auto dy, auto h, auto m) {
+        return launch_fwd_wr<dx(), dy(), h(), m()>(a, lseW, s); });
 }
 
 extern "C" int psvo_bsimwr_backward_cov_ws(
@@ -1323,7 +1295,9 @@ extern "C" int psvo_bsimwr_backward_cov_ws(
     a.bwX = nullptr; a.dscore = nullptr;
     a.t_lo = a.t_hi = 0;        // (>= 0: one launch per time step)
     a.bwXanc = bwXanc; a.bwW = bwW; a.lseW = lseW; a.dlseW = dlseW; a.anc = anc; a.dXs = dXs;
-    PSVO_COVB_DISPATCH(launch_bwd, a, static_cast<hipStream_t>(stream));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return psvo::dispatch_shape_m(desc->Dx, desc->Dy, desc->H, desc->M, [&](auto dx, auto dy, auto h, auto m) {
+        return launch_bwd<dx(), dy(), h(), m()>(a, s); });
 }
 
 extern "C" int psvo_bsimwr_backward_cov(

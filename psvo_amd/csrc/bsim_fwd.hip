@@ -486,38 +486,6 @@ static int launch_bsim(const BsimArgs& a, hipStream_t stream) {
     return launch_status();
 }
 
-template <int DX, int DY, int H>
-static int bsim_dispatch_m(const BsimArgs& a, int M, hipStream_t s) {
-    switch (M) {
-        case 4: return launch_bsim<DX, DY, H, 4>(a, s);
-        case 8: return launch_bsim<DX, DY, H, 8>(a, s);
-        case 16: return launch_bsim<DX, DY, H, 16>(a, s);
-        case 32: return launch_bsim<DX, DY, H, 32>(a, s);
-        default: return PSVO_ERR_UNSUPPORTED;
-    }
-}
-
-template <int DX, int DY>
-static int bsim_dispatch_h(const BsimArgs& a, int H, int M, hipStream_t s) {
-    switch (H) {
-#if PSVO_L == 1   // (two hidden layers: widths 32 and 64; narrower ones are zero-padded upstream)
-        case 16: return bsim_dispatch_m<DX, DY, 16>(a, M, s);
-#endif
-        case 32: return bsim_dispatch_m<DX, DY, 32>(a, M, s);
-        case 64: return bsim_dispatch_m<DX, DY, 64>(a, M, s);
-        default: return PSVO_ERR_UNSUPPORTED;
-    }
-}
-
-template <int DX>
-static int bsim_dispatch_dy(const BsimArgs& a, int Dy, int H, int M, hipStream_t s) {
-    switch (Dy) {
-        case 1: return bsim_dispatch_h<DX, 1>(a, H, M, s);
-        case 2: return bsim_dispatch_h<DX, 2>(a, H, M, s);
-        default: return PSVO_ERR_UNSUPPORTED;
-    }
-}
-
 }  // inline namespace PSVO_LNS
 }  // namespace psvo
 
@@ -559,10 +527,6 @@ PSVO_ENTRY(psvo_bsim_forward)(const psvo_desc* desc, const float* X, const float
     a.bwX = bwX; a.flp = flp; a.glp = glp; a.Omega = Omega; a.sel_out = sel_out; a.score = score;
     a.lam2_all = lam2_all; a.om_all = om_all; a.mu1_all = mu1_all;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (desc->Dx) {
-        case 2: return bsim_dispatch_dy<2>(a, desc->Dy, desc->H, desc->M, s);
-        case 3: return bsim_dispatch_dy<3>(a, desc->Dy, desc->H, desc->M, s);
-        case 4: return bsim_dispatch_dy<4>(a, desc->Dy, desc->H, desc->M, s);
-        default: return PSVO_ERR_UNSUPPORTED;
-    }
+    return dispatch_shape_m(desc->Dx, desc->Dy, desc->H, desc->M, [&](auto dx, auto dy, auto h, auto m) {
+        return launch_bsim<dx(), dy(), h(), m()>(a, s); });
 }

@@ -79,6 +79,47 @@ __device__ __forceinline__ void phase_skew(int cycles) {
 // an MLP argument carries the second hidden layer when this unit is compiled for two (NULL arguments pass: optional MLPs)
 inline bool mlp_layers_ok(const psvo_mlp* m) { return PSVO_L == 1 || !m || (m->Wh && m->bh); }
 
+// ---------------------------------------------------------------------------------------------
+// The shape envelope (host only).  The shapes the library runs are the four lists below, written here and nowhere else:
+// every entry point turns its run-time (Dx, Dy, H, M) into template arguments through dispatch_shape / dispatch_shape_m,
+// and a value outside the lists returns PSVO_ERR_UNSUPPORTED without launching anything.  (static: instantiated with the
+// callers' lambdas, these are no symbols of the library.)
+// ---------------------------------------------------------------------------------------------
+// pick<Vs...>(v, f): f(std::integral_constant<int, V>{}) for the V among Vs that equals v
+template <int V, int... Vs, class F>
+static inline int pick(int v, F&& f) {
+    if (v == V) return f(std::integral_constant<int, V>{});
+    if constexpr (sizeof...(Vs) > 0) return pick<Vs...>(v, f);
+    else return PSVO_ERR_UNSUPPORTED;
+}
+template <class F> static inline int pick_dx(int Dx, F&& f) { return pick<2, 3, 4>(Dx, f); }
+template <class F> static inline int pick_dy(int Dy, F&& f) { return pick<1, 2>(Dy, f); }
+template <class F> static inline int pick_m(int M, F&& f) { return pick<4, 8, 16, 32>(M, f); }
+inline namespace PSVO_LNS {   // (the H list follows the unit's MLP depth: distinct symbols per depth)
+template <class F> static inline int pick_h(int H, F&& f) {
+#if PSVO_L == 1
+    return pick<16, 32, 64>(H, f);
+#else   // (two hidden layers: widths 32 and 64; narrower ones are zero-padded upstream)
+    return pick<32, 64>(H, f);
+#endif
+}
+
+// f(dy, h) / f(dy, h, m) / f(dx, dy, h) / f(dx, dy, h, m) with compile-time constants: `launch<dx(), dy(), h(), m()>(...)`.
+// Whatever else the launch needs (argument structs, stream, run-time switches) the callable captures by reference.
+template <class F> static inline int dispatch_dy_h(int Dy, int H, F&& f) {
+    return pick_dy(Dy, [&](auto dy) { return pick_h(H, [&](auto h) { return f(dy, h); }); });
+}
+template <class F> static inline int dispatch_dy_h_m(int Dy, int H, int M, F&& f) {
+    return dispatch_dy_h(Dy, H, [&](auto dy, auto h) { return pick_m(M, [&](auto m) { return f(dy, h, m); }); });
+}
+template <class F> static inline int dispatch_shape(int Dx, int Dy, int H, F&& f) {
+    return pick_dx(Dx, [&](auto dx) { return dispatch_dy_h(Dy, H, [&](auto dy, auto h) { return f(dx, dy, h); }); });
+}
+template <class F> static inline int dispatch_shape_m(int Dx, int Dy, int H, int M, F&& f) {
+    return pick_dx(Dx, [&](auto dx) { return dispatch_dy_h_m(Dy, H, M, [&](auto dy, auto h, auto m) { return f(dx, dy, h, m); }); });
+}
+}  // inline namespace PSVO_LNS
+
 // PSVOwR: workgroups per sequence (cluster size) -- as many as keep every workgroup busy and the whole
 // cooperative grid resident (one workgroup per CU)
 static inline int wr_cluster(int B, int N, int M) {

@@ -42,6 +42,20 @@ struct FilterBwdArgs {
     int det_copies;          // filter_bwd_kernel<.., DET = true>: scatter-target copies, 1 .. waves (see there)
 };
 
+// floats of one affine-scan record (ScanRec<DX>::REC): A (Dx x Dx) | b (Dx) | ext (Dx) | ancestor, padded to float4s
+constexpr int scan_rec_floats(int Dx) { return (Dx * Dx + 2 * Dx + 1 + 3) & ~3; }
+
+// The reverse pass's workspace (psvo_filter_ws_floats), offsets and size in floats: per-sequence sums (at 0) | d mu2 rows |
+// (16-byte aligned) affine-scan records (T,B,N,REC) | per-step partial sums (T,B,NACC).  The size allows 4 floats for the alignment.
+struct FilterWsLayout {
+    long long dm2, rec, part, total;
+};
+static FilterWsLayout filter_ws_layout(int B, int T, int N, int Dx, int Dy) {
+    const long long nacc = psvo_filter_acc_size(Dx, Dy), sums = B * nacc, rows = (long long)T * B * Dx * N;
+    const long long recs = (long long)T * B * scan_rec_floats(Dx) * N, end = sums + rows, rec = (end + 3) & ~3LL;
+    return {sums, rec, rec + recs, end + 4 + recs + (long long)T * B * nacc};
+}
+
 template <int DX, int DY>
 struct FAcc {
     // per-dimension sums, one set for t >= 1 and one for t = 0
@@ -899,7 +913,7 @@ template <int DX>
 struct ScanRec {
     static constexpr int NC = DX * DX + DX;
     static constexpr int kExt = NC, kAnc = NC + DX;
-    static constexpr int REC = (NC + DX + 1 + 3) & ~3;
+    static constexpr int REC = scan_rec_floats(DX);
 };
 
 template <int DX, int DY, int H>
@@ -1309,27 +1323,6 @@ static int launch_filter_bwd(const FilterBwdArgs& a, const FilterBwdOut& o, hipS
     return launch_status();
 }
 
-template <int DX, int DY>
-static int fb_dispatch_h(const FilterBwdArgs& a, const FilterBwdOut& o, int H, hipStream_t s) {
-    switch (H) {
-#if PSVO_L == 1   // (two hidden layers: widths 32 and 64; narrower ones are zero-padded upstream)
-        case 16: return launch_filter_bwd<DX, DY, 16>(a, o, s);
-#endif
-        case 32: return launch_filter_bwd<DX, DY, 32>(a, o, s);
-        case 64: return launch_filter_bwd<DX, DY, 64>(a, o, s);
-        default: return PSVO_ERR_UNSUPPORTED;
-    }
-}
-
-template <int DX>
-static int fb_dispatch_dy(const FilterBwdArgs& a, const FilterBwdOut& o, int Dy, int H, hipStream_t s) {
-    switch (Dy) {
-        case 1: return fb_dispatch_h<DX, 1>(a, o, H, s);
-        case 2: return fb_dispatch_h<DX, 2>(a, o, H, s);
-        default: return PSVO_ERR_UNSUPPORTED;
-    }
-}
-
 }  // inline namespace PSVO_LNS
 }  // namespace psvo
 
@@ -1337,9 +1330,7 @@ static int fb_dispatch_dy(const FilterBwdArgs& a, const FilterBwdOut& o, int Dy,
 extern "C" int psvo_filter_acc_size(int Dx, int Dy) { return 10 * Dx + Dy; }
 
 extern "C" long long psvo_filter_ws_floats(int B, int T, int N, int Dx, int Dy) {
-    // per-sequence sums | d mu2 rows | affine-scan records (T,B,N,REC) | per-step partial sums (T,B,NACC)
-    const long long rec = (Dx * Dx + 2 * Dx + 1 + 3) / 4 * 4;      // ScanRec<Dx>::REC
-    return (long long)B * (10 * Dx + Dy) + (long long)T * B * Dx * N + 4 + (long long)T * B * rec * N + (long long)T * B * (10 * Dx + Dy);
+    return psvo::filter_ws_layout(B, T, N, Dx, Dy).total;
 }
 #endif
 
@@ -1383,19 +1374,12 @@ PSVO_ENTRY(psvo_filter_backward)(
     a.X = X; a.Fm = Fm; a.P1 = P1; a.logW = logW; a.lse = lse; a.idx = idx;
     a.dlse = dlse; a.nparts = nparts; a.dFm_ext = dFm_ext; a.dlogW_ext = dlogW_ext;
     a.dP = dP; a.dF = dF; a.dG = dG; a.dmu2 = dmu2; a.dm0 = dm0; a.dfm0 = dfm0; a.sacc = sacc;
-    a.dm2_rows = sacc + (size_t)desc->B * psvo_filter_acc_size(desc->Dx, desc->Dy);
-    {   // the records are read with 16-byte accesses: their offset inside the (16-byte aligned) workspace is rounded up
-        const size_t off = (size_t)desc->B * psvo_filter_acc_size(desc->Dx, desc->Dy) + (size_t)desc->T * desc->B * desc->Dx * desc->N;
-        a.scanAB = sacc + ((off + 3) & ~(size_t)3);
-    }
-    if (reinterpret_cast<uintptr_t>(a.scanAB) & 15) a.scanAB = nullptr;      // (a misaligned workspace: the persistent kernel)
-    a.scanPart = !a.scanAB ? nullptr : a.scanAB + (size_t)desc->T * desc->B * ((desc->Dx * desc->Dx + 2 * desc->Dx + 1 + 3) / 4 * 4) * desc->N;
+    const FilterWsLayout l = filter_ws_layout(desc->B, desc->T, desc->N, desc->Dx, desc->Dy);
+    const bool scan = (reinterpret_cast<uintptr_t>(sacc + l.rec) & 15) == 0;      // (a misaligned workspace: the persistent kernel)
+    a.dm2_rows = sacc + l.dm2;
+    a.scanAB = scan ? sacc + l.rec : nullptr; a.scanPart = scan ? sacc + l.part : nullptr;
     FilterBwdOut o{dsig_q1, dsig_q2, dsig_f, dsig_g, dsig0, dfsig0};
     hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (desc->Dx) {
-        case 2: return fb_dispatch_dy<2>(a, o, desc->Dy, desc->H, s);
-        case 3: return fb_dispatch_dy<3>(a, o, desc->Dy, desc->H, s);
-        case 4: return fb_dispatch_dy<4>(a, o, desc->Dy, desc->H, s);
-        default: return PSVO_ERR_UNSUPPORTED;
-    }
+    return dispatch_shape(desc->Dx, desc->Dy, desc->H, [&](auto dx, auto dy, auto h) {
+        return launch_filter_bwd<dx(), dy(), h()>(a, o, s); });
 }

@@ -1130,32 +1130,6 @@ static int launch_bwd(const BwdArgs& a, const BwdOut& o, hipStream_t stream) {
     return launch_status();
 }
 
-#define PSVO_COV_DISPATCH(LAUNCH, ...)                                                         \
-    do {                                                                                       \
-        const int key = desc->Dx * 1000 + desc->Dy * 100 + desc->H;                            \
-        switch (key) {                                                                         \
-            case 2116: return LAUNCH<2, 1, 16>(__VA_ARGS__);                                   \
-            case 2132: return LAUNCH<2, 1, 32>(__VA_ARGS__);                                   \
-            case 2164: return LAUNCH<2, 1, 64>(__VA_ARGS__);                                   \
-            case 2216: return LAUNCH<2, 2, 16>(__VA_ARGS__);                                   \
-            case 2232: return LAUNCH<2, 2, 32>(__VA_ARGS__);                                   \
-            case 2264: return LAUNCH<2, 2, 64>(__VA_ARGS__);                                   \
-            case 3116: return LAUNCH<3, 1, 16>(__VA_ARGS__);                                   \
-            case 3132: return LAUNCH<3, 1, 32>(__VA_ARGS__);                                   \
-            case 3164: return LAUNCH<3, 1, 64>(__VA_ARGS__);                                   \
-            case 3216: return LAUNCH<3, 2, 16>(__VA_ARGS__);                                   \
-            case 3232: return LAUNCH<3, 2, 32>(__VA_ARGS__);                                   \
-            case 3264: return LAUNCH<3, 2, 64>(__VA_ARGS__);                                   \
-            case 4116: return LAUNCH<4, 1, 16>(__VA_ARGS__);                                   \
-            case 4132: return LAUNCH<4, 1, 32>(__VA_ARGS__);                                   \
-            case 4164: return LAUNCH<4, 1, 64>(__VA_ARGS__);                                   \
-            case 4216: return LAUNCH<4, 2, 16>(__VA_ARGS__);                                   \
-            case 4232: return LAUNCH<4, 2, 32>(__VA_ARGS__);                                   \
-            case 4264: return LAUNCH<4, 2, 64>(__VA_ARGS__);                                   \
-            default: return PSVO_ERR_UNSUPPORTED;                                              \
-        }                                                                                      \
-    } while (0)
-
 static bool desc_ok(const psvo_desc* d) {
     return d && d->B > 0 && d->T > 0 && d->N > 0;
 }
@@ -1166,7 +1140,8 @@ struct WsLayout {
     long long dm2, ds2, rec, part, total;
 };
 static WsLayout ws_layout(int B, int T, int N, int Dx, int Dy) {
-    const long long R = Dx == 2 ? CovRec<2>::REC : Dx == 3 ? CovRec<3>::REC : Dx == 4 ? CovRec<4>::REC : 0;     // (else: no scan)
+    long long R = 0;      // (a Dx outside the envelope: no scan)
+    pick_dx(Dx, [&](auto dx) { return (int)(R = CovRec<dx()>::REC); });
     const long long sums = (long long)B * (2 * Dx + Dy), rows = (long long)T * B * Dx * N, recs = (long long)T * B * R * N;
     const long long end = sums + 2 * rows, rec = (end + 3) & ~3LL;
     return {sums, sums + rows, rec, rec + recs, end + 4 + recs + (long long)T * B * (2 * Dx + Dy)};
@@ -1204,7 +1179,9 @@ extern "C" int psvo_filter_forward_cov(const psvo_desc* desc, const psvo_mlp* q1
     a.mu2 = mu2; a.sig2 = sig2; a.m0 = m0; a.sig0 = sig0; a.fm0 = fm0; a.fsig0 = fsig0;
     a.obs = obs; a.eps = eps; a.u = u; a.idx_in = idx_in;
     a.X = X; a.Xanc = Xanc; a.Fm = Fm; a.Fs = Fs; a.P1 = P1; a.P1s = P1s; a.logW = logW; a.idx_out = idx_out; a.lse = lse;
-    PSVO_COV_DISPATCH(launch_fwd, a, static_cast<hipStream_t>(stream));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return dispatch_shape(desc->Dx, desc->Dy, desc->H, [&](auto dx, auto dy, auto h) {
+        return launch_fwd<dx(), dy(), h()>(a, s); });
 }
 
 extern "C" int psvo_filter_backward_cov(
@@ -1242,5 +1219,7 @@ extern "C" int psvo_filter_backward_cov(
     a.sacc = ws; a.dm2_rows = ws + l.dm2; a.ds2_rows = ws + l.ds2;
     a.scanRec = scan ? ws + l.rec : nullptr; a.scanPart = scan ? ws + l.part : nullptr;
     BwdOut o{dmu2, dsig2, dsigc_q1, dsigc_f, dsigc_g};
-    PSVO_COV_DISPATCH(launch_bwd, a, o, static_cast<hipStream_t>(stream));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return dispatch_shape(desc->Dx, desc->Dy, desc->H, [&](auto dx, auto dy, auto h) {
+        return launch_bwd<dx(), dy(), h()>(a, o, s); });
 }

@@ -590,27 +590,6 @@ static int launch_filter(const FilterArgs& a, hipStream_t stream) {
     return launch_status();
 }
 
-template <int DX, int DY>
-static int dispatch_h(const FilterArgs& a, int H, hipStream_t s) {
-    switch (H) {
-#if PSVO_L == 1   // (two hidden layers: widths 32 and 64; narrower ones are zero-padded upstream)
-        case 16: return launch_filter<DX, DY, 16>(a, s);
-#endif
-        case 32: return launch_filter<DX, DY, 32>(a, s);
-        case 64: return launch_filter<DX, DY, 64>(a, s);
-        default: return PSVO_ERR_UNSUPPORTED;
-    }
-}
-
-template <int DX>
-static int dispatch_dy(const FilterArgs& a, int Dy, int H, hipStream_t s) {
-    switch (Dy) {
-        case 1: return dispatch_h<DX, 1>(a, H, s);
-        case 2: return dispatch_h<DX, 2>(a, H, s);
-        default: return PSVO_ERR_UNSUPPORTED;
-    }
-}
-
 }  // inline namespace PSVO_LNS
 }  // namespace psvo
 
@@ -647,10 +626,6 @@ PSVO_ENTRY(psvo_filter_forward)(const psvo_desc* desc, const psvo_mlp* q1, const
     a.obs = obs; a.eps = eps; a.u = u; a.idx_in = idx_in;
     a.X = X; a.Xanc = Xanc; a.Fm = Fm; a.P1 = P1; a.logW = logW; a.idx_out = idx_out; a.lse = lse;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (desc->Dx) {
-        case 2: return dispatch_dy<2>(a, desc->Dy, desc->H, s);
-        case 3: return dispatch_dy<3>(a, desc->Dy, desc->H, s);
-        case 4: return dispatch_dy<4>(a, desc->Dy, desc->H, s);
-        default: return PSVO_ERR_UNSUPPORTED;
-    }
+    return dispatch_shape(desc->Dx, desc->Dy, desc->H, [&](auto dx, auto dy, auto h) {
+        return launch_filter<dx(), dy(), h()>(a, s); });
 }

@@ -731,38 +731,6 @@ static int launch_wr_bwd(const WrBwdArgs& a, const WrBwdOut& o, hipStream_t stre
     return launch_status();
 }
 
-template <int DX, int DY, int H>
-static int wb_dispatch_m(const WrBwdArgs& a, const WrBwdOut& o, int M, hipStream_t s) {
-    switch (M) {
-        case 4: return launch_wr_bwd<DX, DY, H, 4>(a, o, s);
-        case 8: return launch_wr_bwd<DX, DY, H, 8>(a, o, s);
-        case 16: return launch_wr_bwd<DX, DY, H, 16>(a, o, s);
-        case 32: return launch_wr_bwd<DX, DY, H, 32>(a, o, s);
-        default: return PSVO_ERR_UNSUPPORTED;
-    }
-}
-
-template <int DX, int DY>
-static int wb_dispatch_h(const WrBwdArgs& a, const WrBwdOut& o, int H, int M, hipStream_t s) {
-    switch (H) {
-#if PSVO_L == 1   // (two hidden layers: widths 32 and 64; narrower ones are zero-padded upstream)
-        case 16: return wb_dispatch_m<DX, DY, 16>(a, o, M, s);
-#endif
-        case 32: return wb_dispatch_m<DX, DY, 32>(a, o, M, s);
-        case 64: return wb_dispatch_m<DX, DY, 64>(a, o, M, s);
-        default: return PSVO_ERR_UNSUPPORTED;
-    }
-}
-
-template <int DX>
-static int wb_dispatch_dy(const WrBwdArgs& a, const WrBwdOut& o, int Dy, int H, int M, hipStream_t s) {
-    switch (Dy) {
-        case 1: return wb_dispatch_h<DX, 1>(a, o, H, M, s);
-        case 2: return wb_dispatch_h<DX, 2>(a, o, H, M, s);
-        default: return PSVO_ERR_UNSUPPORTED;
-    }
-}
-
 }  // inline namespace PSVO_LNS
 }  // namespace psvo
 
@@ -818,10 +786,6 @@ PSVO_ENTRY(psvo_bsimwr_backward)(
     a.err = reinterpret_cast<unsigned*>(ws + wb_ws_floats(desc->B, desc->T, desc->N) - 1);
     WrBwdOut o{dsig_f, dsig_g, dsig_q1inv, dsig_bq2, dsig_init, disig};
     hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (desc->Dx) {
-        case 2: return wb_dispatch_dy<2>(a, o, desc->Dy, desc->H, desc->M, s);
-        case 3: return wb_dispatch_dy<3>(a, o, desc->Dy, desc->H, desc->M, s);
-        case 4: return wb_dispatch_dy<4>(a, o, desc->Dy, desc->H, desc->M, s);
-        default: return PSVO_ERR_UNSUPPORTED;
-    }
+    return dispatch_shape_m(desc->Dx, desc->Dy, desc->H, desc->M, [&](auto dx, auto dy, auto h, auto m) {
+        return launch_wr_bwd<dx(), dy(), h(), m()>(a, o, s); });
 }

@@ -231,36 +231,72 @@ def filter_forward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, 
     return out
 
 
+# The plain backward simulations (PSVO: bsim_*, PSVOwR: bsimwr_*) take the same inputs ahead of their own and their reverse
+# launches write the same rows: what the four wrappers share is below; the argument lists mirror include/psvo_hip.h in each.
+def _bsim_structs(d, f, g, q1_inv):
+    return _mlp_struct(f, d.Dx, d.H, d.Dx, "f"), _mlp_struct(g, d.Dx, d.H, d.Dy, "g"), _mlp_struct(q1_inv, d.Dx, d.H, d.Dx, "q1_inv")
+
+
+def _bsim_chk(desc, filt, sig_f, sig_g, sig_q1inv, sig_bq2, bmu2, minit, sig_init, imean, isig, obs, eps_b, u_b, sel_in):
+    B, T, N, M, Dx, Dy = desc.B, desc.T, desc.N, desc.M, desc.Dx, desc.Dy
+    _chk(filt["Fm"], (T, B, Dx, N), "Fm"); _chk(filt["logW"], (T, B, N), "logW"); _chk(filt["lse"], (T, B), "lse")
+    _chk(sig_f, (Dx,), "sig_f"); _chk(sig_g, (Dy,), "sig_g"); _chk(sig_q1inv, (Dx,), "sig_q1inv"); _chk(sig_bq2, (Dx,), "sig_bq2")
+    _chk(bmu2, (T, B, Dx), "bmu2"); _chk(minit, (B, Dx), "minit"); _chk(sig_init, (Dx,), "sig_init")
+    _chk(imean, (B, Dx), "imean"); _chk(isig, (Dx,), "isig"); _chk(obs, (T, B, Dy), "obs"); _chk(eps_b, (T, B, Dx, N, M), "eps_b")
+    _chk(u_b, (T, B, N), "u_b"); _chk(sel_in, (T, B, N), "sel_in", torch.int32)
+
+
+def _bsim_saves(desc, dev, save):
+    """what the reverse launch reads back (allocated when a reverse pass will follow); row T-1 of mu1 is written as zeros: no predecessor"""
+    B, T, N, M, Dx = desc.B, desc.T, desc.N, desc.M, desc.Dx
+    z = lambda *s: _empty(*s, device=dev) if save else None
+    return {"lam2": z(T, B, N, M), "om": z(T, B, N, M), "mu1": z(T, B, Dx, N)}
+
+
+def _bsim_chk_saves(desc, bs, fn, own):
+    """`bs` has what `fn`_forward(save=True) returns: the saves, and the caller's `own` ((key, shape), ...)"""
+    B, T, N, M, Dx = desc.B, desc.T, desc.N, desc.M, desc.Dx
+    for k, shp in (("lam2", (T, B, N, M)), ("om", (T, B, N, M)), ("mu1", (T, B, Dx, N))) + own:
+        if bs.get(k) is None:
+            raise ValueError("%s_backward needs %s_forward(save=True) outputs (missing %s)" % (fn, fn, k))
+        _chk(bs[k], shp, k)
+
+
+def _bsim_grads(desc, dev, nparts, own):
+    """the outputs of both reverse launches, in allocation order: the rows for psvo_mlp_wgrad, the per-workgroup partials (nparts
+    per sequence), the caller's `own` ((key, shape), ...), the scale gradients"""
+    B, T, N, M, Dx, Dy = desc.B, desc.T, desc.N, desc.M, desc.Dx, desc.Dy
+    z = lambda *s: _empty(*s, device=dev)
+    out = {"xt": z(T, B, Dx, N, M), "dFt": z(T, B, Dx, N, M), "dGt": z(T, B, Dy, N, M), "dmu1": z(T, B, Dx, N),
+           "dFm_part": z(T, B, nparts, Dx, N), "dlogW_part": z(T, B, nparts, N)}
+    out.update((k, z(*shp)) for k, shp in own)
+    out.update({"dsig_f": z(Dx), "dsig_g": z(Dy), "dsig_q1inv": z(Dx), "dsig_bq2": z(Dx), "dsig_init": z(Dx), "disig": z(Dx)})
+    return out
+
+
+def _bsim_wgrad(out, desc, f, g, q1_inv, x_next, gb):
+    """MLP_f / MLP_g on the sub-particles, MLP_q1inv on x_next[t+1]; gb: the slices of the flat gradient buffer to add to, or Nones"""
+    T, Dx, Dy, H = desc.T, desc.Dx, desc.Dy, desc.H
+    out["gf"] = mlp_wgrad(out["xt"][:T - 1], out["dFt"][:T - 1], f, Dx, H, Dx, grad=gb[0])
+    out["gg"] = mlp_wgrad(out["xt"], out["dGt"], g, Dx, H, Dy, grad=gb[1])
+    out["gq1inv"] = mlp_wgrad(x_next[1:], out["dmu1"][:T - 1], q1_inv, Dx, H, Dx, grad=gb[2])
+
+
 def bsim_forward(desc, filt, f, g, q1_inv, sig_f, sig_g, sig_q1inv, sig_bq2, bmu2, minit, sig_init,
                  imean, isig, obs, eps_b, u_b=None, sel_in=None, save=False):
     """psvo_bsim_forward.  `filt` is the dict returned by filter_forward.
     Returns dict(bwX, flp, glp, Omega, sel, score)."""
     lib = _lib.load()
-    B, T, N, M, Dx, Dy, H = desc.B, desc.T, desc.N, desc.M, desc.Dx, desc.Dy, desc.H
+    B, T, N, Dx = desc.B, desc.T, desc.N, desc.Dx
     dev = eps_b.device
-    fs = _mlp_struct(f, Dx, H, Dx, "f")
-    gs = _mlp_struct(g, Dx, H, Dy, "g")
-    qs = _mlp_struct(q1_inv, Dx, H, Dx, "q1_inv")
-    for k in ("X", "Fm"):
-        _chk(filt[k], (T, B, Dx, N), k)
-    _chk(filt["logW"], (T, B, N), "logW"); _chk(filt["lse"], (T, B), "lse")
-    _chk(sig_f, (Dx,), "sig_f"); _chk(sig_g, (Dy,), "sig_g")
-    _chk(sig_q1inv, (Dx,), "sig_q1inv"); _chk(sig_bq2, (Dx,), "sig_bq2")
-    _chk(bmu2, (T, B, Dx), "bmu2"); _chk(minit, (B, Dx), "minit"); _chk(sig_init, (Dx,), "sig_init")
-    _chk(imean, (B, Dx), "imean"); _chk(isig, (Dx,), "isig")
-    _chk(obs, (T, B, Dy), "obs"); _chk(eps_b, (T, B, Dx, N, M), "eps_b")
-    _chk(u_b, (T, B, N), "u_b"); _chk(sel_in, (T, B, N), "sel_in", torch.int32)
+    fs, gs, qs = _bsim_structs(desc, f, g, q1_inv)
+    _chk(filt["X"], (T, B, Dx, N), "X")
+    _bsim_chk(desc, filt, sig_f, sig_g, sig_q1inv, sig_bq2, bmu2, minit, sig_init, imean, isig, obs, eps_b, u_b, sel_in)
     if u_b is None and sel_in is None:
         raise ValueError("backward simulation needs uniforms `u_b` or teacher-forced `sel_in`")
-    out = {
-        "bwX": _empty(T, B, Dx, N, device=dev), "flp": _empty(T, B, N, device=dev),
-        "glp": _empty(T, B, N, device=dev), "Omega": _empty(T, B, N, device=dev),
-        "sel": _empty(T, B, N, device=dev, dtype=torch.int32), "score": _empty(B, N, device=dev),
-        "lam2": _empty(T, B, N, M, device=dev) if save else None,
-        "om": _empty(T, B, N, M, device=dev) if save else None,
-        # (row t = T-1 of mu1 is written as zeros by the kernel: there is no predecessor step)
-        "mu1": _empty(T, B, Dx, N, device=dev) if save else None,
-    }
+    z = lambda *s: _empty(*s, device=dev)
+    out = {"bwX": z(T, B, Dx, N), "flp": z(T, B, N), "glp": z(T, B, N), "Omega": z(T, B, N),
+           "sel": _empty(T, B, N, device=dev, dtype=torch.int32), "score": z(B, N), **_bsim_saves(desc, dev, save)}
     _mark("psvo_bsim_forward", 0)
     st = lib.psvo_bsim_forward(
         ctypes.byref(desc), _ptr(filt["X"]), _ptr(filt["Fm"]), _ptr(filt["logW"]), _ptr(filt["lse"]),
@@ -798,21 +834,14 @@ def bsim_backward(desc, filt, f, g, q1_inv, sig_f, sig_g, sig_q1inv, sig_bq2, bm
                   obs, eps_b, bs, dscore, gbufs=None, after_kernel=None, wgrad_stream=None, defer_wgrad=False):
     """psvo_bsim_backward + psvo_mlp_wgrad.  `bs` = bsim_forward(..., save=True) outputs."""
     lib = _lib.load()
-    B, T, N, M, Dx, Dy, H = desc.B, desc.T, desc.N, desc.M, desc.Dx, desc.Dy, desc.H
+    B, T, N, Dx, Dy = desc.B, desc.T, desc.N, desc.Dx, desc.Dy
     dev = eps_b.device
-    fs = _mlp_struct(f, Dx, H, Dx, "f")
-    gs = _mlp_struct(g, Dx, H, Dy, "g")
-    qs = _mlp_struct(q1_inv, Dx, H, Dx, "q1_inv")
+    fs, gs, qs = _bsim_structs(desc, f, g, q1_inv)
     _chk(dscore, (B, N), "dscore")
-    for k, shp in (("lam2", (T, B, N, M)), ("om", (T, B, N, M)), ("mu1", (T, B, Dx, N)), ("bwX", (T, B, Dx, N))):
-        if bs.get(k) is None:
-            raise ValueError("bsim_backward needs bsim_forward(save=True) outputs (missing %s)" % k)
-        _chk(bs[k], shp, k)
+    _bsim_chk_saves(desc, bs, "bsim", (("bwX", (T, B, Dx, N)),))
     nblk = lib.psvo_bsim_blocks(ctypes.byref(desc))
     z = lambda *s: _empty(*s, device=dev)
-    out = {"xt": z(T, B, Dx, N, M), "dFt": z(T, B, Dx, N, M), "dGt": z(T, B, Dy, N, M), "dmu1": z(T, B, Dx, N),
-           "dFm_part": z(T, B, nblk, Dx, N), "dlogW_part": z(T, B, nblk, N), "dFm": z(T, B, Dx, N), "dlogW": z(T, B, N),
-           "dlse": z(T, B), "dsig_f": z(Dx), "dsig_g": z(Dy), "dsig_q1inv": z(Dx), "dsig_bq2": z(Dx), "dsig_init": z(Dx), "disig": z(Dx)}
+    out = _bsim_grads(desc, dev, nblk, (("dFm", (T, B, Dx, N)), ("dlogW", (T, B, N)), ("dlse", (T, B))))
     _chain_rows(out, z, T, B, Dx, N)
     sacc = z(B, nblk, lib.psvo_bsim_acc_size(Dx, Dy))
     _mark("psvo_bsim_backward", 0)
@@ -838,16 +867,9 @@ def bsim_backward(desc, filt, f, g, q1_inv, sig_f, sig_g, sig_q1inv, sig_bq2, bm
     _lib.check(st, "psvo_bsim_backward_fold")
     if after_kernel is not None:
         after_kernel(out)
-    # weight gradients from rows: MLP_f / MLP_g on the sub-particles, MLP_q1inv on bwX[t+1];
-    # gbufs = (f, g, q1_inv) slices of the flat gradient buffer to accumulate into directly, or None
-    # wgrad_stream (only with gbufs: nothing is returned that the caller would read): issue the weight gradients on
-    # that stream, ordered after the kernel above, so that the caller's stream is free for what comes next
-    gb = gbufs or (None, None, None)
-
-    def wgrad():
-        out["gf"] = mlp_wgrad(out["xt"][:T - 1], out["dFt"][:T - 1], f, Dx, H, Dx, grad=gb[0])
-        out["gg"] = mlp_wgrad(out["xt"], out["dGt"], g, Dx, H, Dy, grad=gb[1])
-        out["gq1inv"] = mlp_wgrad(bs["bwX"][1:], out["dmu1"][:T - 1], q1_inv, Dx, H, Dx, grad=gb[2])
+    # weight gradients from rows; gbufs = (f, g, q1_inv) slices of the flat gradient buffer to accumulate into, or None.  wgrad_stream
+    # (only with gbufs: nothing is returned that the caller would read): issue them there, ordered after the kernel above
+    wgrad = lambda: _bsim_wgrad(out, desc, f, g, q1_inv, bs["bwX"], gbufs or (None, None, None))
     if defer_wgrad:      # the caller issues them (out["_wgrad"]() under launch_on(stream), ordered after this kernel)
         out["_wgrad"] = wgrad
         return out
@@ -860,30 +882,18 @@ def bsimwr_forward(desc, filt, f, g, q1_inv, sig_f, sig_g, sig_q1inv, sig_bq2, b
                    imean, isig, obs, eps_b, u_b=None, u_r=None, sel_in=None, anc_in=None, save=False):
     """psvo_bsimwr_forward (PSVOwR).  Returns dict(bwX, bwXanc, bwW, lseW, sel, anc[, lam2, om, mu1])."""
     lib = _lib.load()
-    B, T, N, M, Dx, Dy, H = desc.B, desc.T, desc.N, desc.M, desc.Dx, desc.Dy, desc.H
+    B, T, N, Dx = desc.B, desc.T, desc.N, desc.Dx
     dev = eps_b.device
-    fs = _mlp_struct(f, Dx, H, Dx, "f")
-    gs = _mlp_struct(g, Dx, H, Dy, "g")
-    qs = _mlp_struct(q1_inv, Dx, H, Dx, "q1_inv")
-    _chk(filt["Fm"], (T, B, Dx, N), "Fm")
-    _chk(filt["logW"], (T, B, N), "logW"); _chk(filt["lse"], (T, B), "lse")
-    _chk(sig_f, (Dx,), "sig_f"); _chk(sig_g, (Dy,), "sig_g")
-    _chk(sig_q1inv, (Dx,), "sig_q1inv"); _chk(sig_bq2, (Dx,), "sig_bq2")
-    _chk(bmu2, (T, B, Dx), "bmu2"); _chk(minit, (B, Dx), "minit"); _chk(sig_init, (Dx,), "sig_init")
-    _chk(imean, (B, Dx), "imean"); _chk(isig, (Dx,), "isig")
-    _chk(obs, (T, B, Dy), "obs"); _chk(eps_b, (T, B, Dx, N, M), "eps_b")
-    _chk(u_b, (T, B, N), "u_b"); _chk(sel_in, (T, B, N), "sel_in", torch.int32)
+    fs, gs, qs = _bsim_structs(desc, f, g, q1_inv)
+    _bsim_chk(desc, filt, sig_f, sig_g, sig_q1inv, sig_bq2, bmu2, minit, sig_init, imean, isig, obs, eps_b, u_b, sel_in)
     _chk(u_r, (T, B, N), "u_r"); _chk(anc_in, (T, B, N), "anc_in", torch.int32)
     if (u_b is None and sel_in is None) or (u_r is None and anc_in is None):
         raise ValueError("PSVOwR needs uniforms (`u_b`, `u_r`) or teacher-forced indices (`sel_in`, `anc_in`)")
     z = lambda *s: _empty(*s, device=dev)
     zi = lambda *s: _empty(*s, device=dev, dtype=torch.int32)
     out = {"bwX": z(T, B, Dx, N), "bwXanc": z(T, B, Dx, N), "bwW": z(T, B, N), "lseW": z(T, B),
-           "sel": zi(T, B, N), "anc": zi(T, B, N),
-           "lam2": z(T, B, N, M) if save else None, "om": z(T, B, N, M) if save else None,
-           "mu1": z(T, B, Dx, N) if save else None,
-           # workspace; its last word (viewed as int32) is nonzero iff a cluster barrier timed out
-           "ws": z(lib.psvo_bsimwr_ws_floats(B, T, N))}
+           "sel": zi(T, B, N), "anc": zi(T, B, N), **_bsim_saves(desc, dev, save),
+           "ws": z(lib.psvo_bsimwr_ws_floats(B, T, N))}   # (its last word, as int32, is nonzero iff a cluster barrier timed out)
     _mark("psvo_bsimwr_forward", 0)
     st = lib.psvo_bsimwr_forward(
         ctypes.byref(desc), _ptr(filt["Fm"]), _ptr(filt["logW"]), _ptr(filt["lse"]),
@@ -901,23 +911,15 @@ def bsimwr_backward(desc, filt, f, g, q1_inv, sig_f, sig_g, sig_q1inv, sig_bq2, 
                     obs, eps_b, bs, dlseW, gbufs=None, after_kernel=None, wgrad_stream=None):
     """psvo_bsimwr_backward + psvo_mlp_wgrad.  `bs` = bsimwr_forward(..., save=True) outputs."""
     lib = _lib.load()
-    B, T, N, M, Dx, Dy, H = desc.B, desc.T, desc.N, desc.M, desc.Dx, desc.Dy, desc.H
+    B, T, N, Dx, Dy = desc.B, desc.T, desc.N, desc.Dx, desc.Dy
     dev = eps_b.device
-    fs = _mlp_struct(f, Dx, H, Dx, "f")
-    gs = _mlp_struct(g, Dx, H, Dy, "g")
-    qs = _mlp_struct(q1_inv, Dx, H, Dx, "q1_inv")
+    fs, gs, qs = _bsim_structs(desc, f, g, q1_inv)
     _chk(dlseW, (T, B), "dlseW")
-    for k, shp in (("lam2", (T, B, N, M)), ("om", (T, B, N, M)), ("mu1", (T, B, Dx, N)), ("bwXanc", (T, B, Dx, N)),
-                   ("bwW", (T, B, N)), ("lseW", (T, B))):
-        if bs.get(k) is None:
-            raise ValueError("bsimwr_backward needs bsimwr_forward(save=True) outputs (missing %s)" % k)
-        _chk(bs[k], shp, k)
+    _bsim_chk_saves(desc, bs, "bsimwr", (("bwXanc", (T, B, Dx, N)), ("bwW", (T, B, N)), ("lseW", (T, B))))
     z = lambda *s: _empty(*s, device=dev)
-    K = lib.psvo_bsimwr_blocks(B, N, M)
-    out = {"xt": z(T, B, Dx, N, M), "dFt": z(T, B, Dx, N, M), "dGt": z(T, B, Dy, N, M), "dmu1": z(T, B, Dx, N),
-           "dFm_part": z(T, B, K, Dx, N), "dlogW_part": z(T, B, K, N), "dlse_part": z(T, B, K),
-           "dsig_f": z(Dx), "dsig_g": z(Dy), "dsig_q1inv": z(Dx), "dsig_bq2": z(Dx), "dsig_init": z(Dx), "disig": z(Dx),
-           "ws": z(lib.psvo_bsimwr_bwd_ws_floats(B, T, N, Dx))}
+    K = lib.psvo_bsimwr_blocks(B, N, desc.M)
+    out = _bsim_grads(desc, dev, K, (("dlse_part", (T, B, K)),))
+    out["ws"] = z(lib.psvo_bsimwr_bwd_ws_floats(B, T, N, Dx))
     _chain_rows(out, z, T, B, Dx, N)
     sacc = z(B, K, lib.psvo_bsim_acc_size(Dx, Dy))
     _mark("psvo_bsimwr_backward", 0)
@@ -940,11 +942,8 @@ def bsimwr_backward(desc, filt, f, g, q1_inv, sig_f, sig_g, sig_q1inv, sig_bq2, 
     out["dlse"] = out["dlse_part"].sum(2)
     if after_kernel is not None:
         after_kernel(out)
-    gb = gbufs or (None, None, None)
     with _wgrad_on(wgrad_stream if gbufs is not None else None):
-        out["gf"] = mlp_wgrad(out["xt"][:T - 1], out["dFt"][:T - 1], f, Dx, H, Dx, grad=gb[0])
-        out["gg"] = mlp_wgrad(out["xt"], out["dGt"], g, Dx, H, Dy, grad=gb[1])
-        out["gq1inv"] = mlp_wgrad(bs["bwXanc"][1:], out["dmu1"][:T - 1], q1_inv, Dx, H, Dx, grad=gb[2])
+        _bsim_wgrad(out, desc, f, g, q1_inv, bs["bwXanc"], gbufs or (None, None, None))
     return out
 
 

@@ -124,6 +124,69 @@ def test_invalid_arguments_are_rejected_without_a_device(built_lib):
         _lib.check(_lib.PSVO_ERR_HIP, "x")
 
 
+def test_shapes_outside_the_envelope_are_unsupported(built_lib):
+    """Every entry point that reaches a shape dispatch (psvo_amd/csrc/common.h: pick_dx / pick_dy / pick_h / pick_m), called with
+    every pointer set and a descriptor that is valid except for its shape, returns PSVO_ERR_UNSUPPORTED from the dispatcher's
+    default arm: nothing ahead of the dispatch touches a device.  A shape INSIDE the lists would launch with host pointers, so
+    each shape is asserted to be outside before the call, and the test does not run where a device is present."""
+    import itertools
+    import torch
+    from psvo_amd import _lib
+    if torch.cuda.is_available():
+        pytest.skip("host-code test: never hands a host pointer to a library that can reach a device")
+    lib = _lib.load()
+    buf = (ctypes.c_float * 64)()
+    addr = (ctypes.addressof(buf) + 15) & ~15        # one small 16-byte-aligned host buffer behind every pointer
+    assert addr + 64 <= ctypes.addressof(buf) + ctypes.sizeof(buf)
+    DX, DY, HH, MM = (2, 3, 4), (1, 2), (16, 32, 64), (4, 8, 16, 32)
+    plain = ["psvo_filter_forward", "psvo_filter_backward", "psvo_bsim_forward", "psvo_bsim_backward", "psvo_bsimwr_forward",
+             "psvo_bsimwr_backward"]
+    cov = ["psvo_filter_forward_cov", "psvo_filter_backward_cov", "psvo_bsim_forward_cov", "psvo_bsim_backward_cov",
+           "psvo_bsim_backward_cov_ws", "psvo_bsimwr_forward_cov", "psvo_bsimwr_backward_cov", "psvo_bsimwr_backward_cov_ws"]
+    fold = ["psvo_bsim_backward_fold"]       # (dispatches on Dx and Dy only)
+
+    def call(name, d):
+        types = _lib.SIGNATURES[name][1]
+        keep, args = [], [ctypes.byref(d)]
+        for i, ty in enumerate(types[1:], 1):
+            if ty is ctypes.POINTER(_lib.psvo_mlp):
+                m = _lib.psvo_mlp()
+                for f, _ in m._fields_:
+                    setattr(m, f, addr)
+                keep.append(m)
+                args.append(ctypes.byref(m))
+            elif i == len(types) - 1:
+                args.append(None)      # stream
+            elif ty is ctypes.c_void_p:
+                args.append(ctypes.c_void_p(addr))
+            else:
+                args.append(1)         # nparts
+        return getattr(lib, name)(*args)
+
+    vals = dict(Dx=(1, 5), Dy=(0, 3), H=(8, 48, 128), M=(2, 12, 64))
+    calls = 0
+    for name in plain + cov + fold:
+        has_m, has_h = "filter" not in name and name not in fold, name not in fold
+        keys = [k for k in vals if (k != "M" or has_m) and (k != "H" or has_h)]
+        for layers in ((1,) if name in cov else (1, 2)):       # (cov: layers = 2 is refused earlier, with the same status)
+            cases = [{k: v} for k in keys for v in vals[k]]
+            cases += [{k1: vals[k1][0], k2: vals[k2][-1]} for k1, k2 in itertools.combinations(keys, 2)]
+            if layers == 2 and has_h:
+                cases.append({"H": 16})
+            for c in cases:
+                d = _lib.psvo_desc()
+                d.B, d.T, d.N, d.M, d.Dx, d.Dy, d.H = 2, 4, 8, 4, 2, 1, 32
+                d.resample, d.two_q, d.bootstrap, d.emission, d.layers = 1, 1, 0, 0, layers
+                for k, v in c.items():
+                    setattr(d, k, v)
+                inside = (d.Dx in DX and d.Dy in DY and (not has_h or (d.H in HH and not (layers == 2 and d.H == 16)))
+                          and (not has_m or d.M in MM))
+                assert not inside, (name, layers, c)
+                assert call(name, d) == _lib.PSVO_ERR_UNSUPPORTED, (name, layers, c)
+                calls += 1
+    assert calls == 300
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     from psvo_amd import _lib
     monkeypatch.setattr(_lib, "_lib", None)
