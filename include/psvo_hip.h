@@ -604,6 +604,35 @@ int psvo_bilstm_wgrad_fold(int B, int Din, int Dh, const float* dW_part, const f
 int psvo_adam_step(float* params, const float* grads, float* m, float* v, long long n, float lr,
                    float beta1, float beta2, float eps, long long step, float grad_scale, void* stream);
 
+/* Guarded Adam step: clip the gradient by its global L2 norm and / or leave the step out when that norm is not finite, decided
+ * on the device (two launches, no atomics, no allocation, no host read; every sum in a fixed order, so bit-reproducible).
+ *
+ * psvo_grad_norm_blocks(n) = G, the number of partial sums: min(256, ceil(n / 4096)), at least 1; a function of n alone.
+ * psvo_grad_sumsq: workgroup k < G writes partial[k] = sum of grads[i]^2 over its slice i in [k S, min(n, (k + 1) S)),
+ *   S = ceil(n / G) rounded up to a multiple of 4.  Accumulated in double (the product of two floats is exact there and
+ *   the sum cannot overflow); a NaN or an infinity among the entries propagates into its slice's sum.
+ * psvo_adam_step_guarded: every workgroup folds partial[0 .. G) in one fixed order and forms
+ *       norm = |grad_scale| * sqrt(sum)        -- the L2 norm of the gradient Adam sees (after the 1/world_size), then
+ *     norm not finite and skip_nonfinite != 0:  params, m and v are not written; state[2] and state[3] count the step;
+ *     else clip_norm > 0 and norm > clip_norm:  g_i = (grads_i * grad_scale) * (float)(clip_norm / norm); state[1] counts it;
+ *     else:                                     exactly psvo_adam_step, bit for bit (a factor of 1 is never multiplied in).
+ *   (An infinite norm with skip_nonfinite == 0 and clip_norm > 0 takes the second row: the factor is 0.)
+ *   lr_t is computed on the host from `step` exactly as in psvo_adam_step, and the caller advances `step` on EVERY call, a
+ *   skipped one included: the unguarded case stays bit-identical to psvo_adam_step and host and device can never disagree
+ *   about a count.  The price: after a skip the bias correction is marginally too small (lr_t as if one more step had been
+ *   averaged in), which matters only during the first few thousand steps.
+ *   state[8] (doubles: exact for counts up to 2^53) belongs to the caller, who zeroes it once; lane 0 of workgroup 0 updates it
+ *   with ordinary stores:  [0] steps applied (clipped ones included), [1] steps clipped, [2] steps skipped, [3] steps
+ *   skipped in a row up to now (0 after an applied step), [4] norm of the last call, [5] largest finite norm so far,
+ *   [6], [7] reserved.  [0] + [2] = number of calls.
+ *   `partial` must be the G sums psvo_grad_sumsq wrote for the same grads and n on the same stream.
+ * PSVO_ERR_INVALID before any launch: a null pointer (stream excepted), n <= 0, step <= 0, clip_norm < 0 or not finite. */
+int psvo_grad_norm_blocks(long long n);
+int psvo_grad_sumsq(const float* grads, long long n, double* partial, void* stream);
+int psvo_adam_step_guarded(float* params, const float* grads, float* m, float* v, long long n, float lr,
+                           float beta1, float beta2, float eps, long long step, float grad_scale, float clip_norm,
+                           int skip_nonfinite, const double* partial, double* state, void* stream);
+
 /* out[p] (+)= sum_{r < nrows} part[r * stride + p], p < n: folds per-sequence / per-workgroup partial
  * gradients straight into the flat gradient buffer (deterministic, no atomics). */
 int psvo_reduce_rows(const float* part, int nrows, long long stride, int n, float* out, int accumulate,

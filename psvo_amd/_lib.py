@@ -89,6 +89,11 @@ SIGNATURES = {
     "psvo_bilstm_wgrad_fold": (ctypes.c_int, [ctypes.c_int] * 3 + [_P] * 4 + [ctypes.c_int, _P]),
     "psvo_adam_step": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_longlong, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                       ctypes.c_float, ctypes.c_longlong, ctypes.c_float, _P]),
+    "psvo_grad_norm_blocks": (ctypes.c_int, [ctypes.c_longlong]),
+    "psvo_grad_sumsq": (ctypes.c_int, [_P, ctypes.c_longlong, _P, _P]),
+    "psvo_adam_step_guarded": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_longlong, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                              ctypes.c_float, ctypes.c_longlong, ctypes.c_float, ctypes.c_float, ctypes.c_int,
+                                              _P, _P, _P]),
     "psvo_reduce_rows": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, _P, ctypes.c_int, _P]),
     "psvo_sigma_forward": (ctypes.c_int, [_P, _P, _P, ctypes.c_int, _P]),
     "psvo_sigma_backward": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int, ctypes.c_int, _P]),

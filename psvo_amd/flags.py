@@ -67,6 +67,9 @@ DEFINITIONS = [
     ("lr_reduce_patience", int, 30, "reduce learning rate when testing loss doesn't improve"),
     ("lr_reduce_factor", float, 1 / math.sqrt(2), "new_lr = old_lr * lr_reduce_factor"),
     ("min_lr", float, 3e-3 / 10, "minimum learning rate"),
+    # gradient guard (not in the reference's registry; its sweep script passes clip_norm = 10.0, auto_sh.py:109): both off by default
+    ("clip_norm", float, 0.0, "clip the gradient to this global L2 norm before Adam (0 = off)"),
+    ("skip_nonfinite_steps", bool, False, "leave out a training step whose gradient norm is inf or NaN"),
     # printing and data saving (runner_flag.py:131-153)
     ("print_freq", int, 1, "frequency to evaluate testing loss & other metrics and save results"),
     ("save_trajectory", bool, True, "whether to save hidden trajectories during training"),

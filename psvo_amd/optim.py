@@ -6,6 +6,7 @@ all-reduce and a single fused Adam launch (psvo_adam_step) whatever the number o
 (~22.5 k floats for PSVO with H = 32, Dh = 32).
 """
 import ctypes
+import math
 
 import torch
 
@@ -107,21 +108,52 @@ class FlatParams(object):
 class TFAdam(object):
     """tf.train.AdamOptimizer(lr) (beta1=0.9, beta2=0.999, epsilon=1e-8) on a FlatParams buffer;
     maximises the objective whose gradient sits in flat.grad (the reference minimises -log_ZSMC,
-    src/trainer.py:118)."""
+    src/trainer.py:118).
 
-    def __init__(self, flat, beta1=0.9, beta2=0.999, epsilon=1e-8):
+    The guard (off by default; contract in include/psvo_hip.h): `clip_norm` > 0 rescales a gradient whose global L2 norm --
+    after the 1/world_size -- exceeds it, `skip_nonfinite` leaves a step out whose norm is inf or NaN.  Both are decided on the
+    device (psvo_grad_sumsq + psvo_adam_step_guarded, no host synchronisation); guard_stats() reads the counts back."""
+
+    STATE_KEYS = ("applied", "clipped", "skipped", "consecutive_skipped", "last_norm", "max_norm")
+
+    def __init__(self, flat, beta1=0.9, beta2=0.999, epsilon=1e-8, clip_norm=0.0, skip_nonfinite=False):
+        self.clip_norm, self.skip_nonfinite = float(clip_norm), bool(skip_nonfinite)
+        if not (math.isfinite(self.clip_norm) and self.clip_norm >= 0.0):
+            raise ValueError("clip_norm must be finite and >= 0 (0 = off), got %r" % (clip_norm,))
         self.flat = flat
         self.beta1, self.beta2, self.epsilon = beta1, beta2, epsilon
         self.m = torch.zeros_like(flat.flat)
         self.v = torch.zeros_like(flat.flat)
         self.t = 0
+        self.guarded = self.clip_norm > 0.0 or self.skip_nonfinite
+        if self.guarded:
+            G = _lib.load().psvo_grad_norm_blocks(flat.numel)
+            self.partial = torch.zeros(G, device=flat.flat.device, dtype=torch.float64)
+            self.state = torch.zeros(8, device=flat.flat.device, dtype=torch.float64)
 
     def step(self, lr, world_size=1):
         """theta <- theta + Adam(d log_ZSMC); flat.grad holds the SUM over ranks of d log_ZSMC."""
         self.t += 1
         lib = _lib.load()
         p = lambda t: ctypes.c_void_p(t.data_ptr())
+        if self.guarded:
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            _lib.check(lib.psvo_grad_sumsq(p(self.flat.grad), self.flat.numel, p(self.partial), stream), "psvo_grad_sumsq")
+            st = lib.psvo_adam_step_guarded(p(self.flat.flat), p(self.flat.grad), p(self.m), p(self.v), self.flat.numel,
+                                            float(lr), self.beta1, self.beta2, self.epsilon, self.t, -1.0 / world_size,
+                                            self.clip_norm, int(self.skip_nonfinite), p(self.partial), p(self.state), stream)
+            _lib.check(st, "psvo_adam_step_guarded")
+            return
         st = lib.psvo_adam_step(p(self.flat.flat), p(self.flat.grad), p(self.m), p(self.v), self.flat.numel,
                                 float(lr), self.beta1, self.beta2, self.epsilon, self.t, -1.0 / world_size,
                                 ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
         _lib.check(st, "psvo_adam_step")
+
+    def guard_stats(self):
+        """{applied, clipped, skipped, consecutive_skipped (counts since construction; applied includes clipped, applied +
+        skipped = steps), last_norm, max_norm (largest finite norm so far)}: ONE device read.  None with the guard off."""
+        if not self.guarded:
+            return None
+        vals = self.state.cpu().tolist()
+        out = {k: (x if k.endswith("norm") else int(x)) for k, x in zip(self.STATE_KEYS, vals)}
+        return out

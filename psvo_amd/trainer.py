@@ -10,6 +10,11 @@ Data parallelism (new relative to the reference): with W r
 FLAGS.batch_size sequences is sharded FLAGS.batch_size / W per rank; one flat all-reduce of the gradient per step,
 identical Adam update on every rank (checked bit for bit every print_freq epochs); evaluation batches are dealt
 round-robin over the ranks and gathered.
+
+Gradient guard (new relative to the reference's trainer; FLAGS.clip_norm, FLAGS.skip_nonfinite_steps, both off by default): the
+optimizer clips by the global norm and leaves non-finite steps out on the device (psvo_amd.optim.TFAdam).  The norm is taken
+after the all-reduce, so every rank decides alike.  At every evaluation the counts since the previous one are printed, go into
+metric_<iter>.p under the guard_* keys, and an interval in which every step was skipped stops the training.
 """
 import math
 import os
@@ -159,7 +164,10 @@ class trainer:
         assert self.batch_size % dp.world_size() == 0, "batch_size must split evenly over the ranks"
         self.flat = FlatParams(self.model)
         dp.broadcast_(self.flat.flat)
-        self.optimizer = TFAdam(self.flat)                       # tf.train.AdamOptimizer(lr), trainer.py:117
+        self.optimizer = TFAdam(self.flat, clip_norm=getattr(self.FLAGS, "clip_norm", 0.0),     # tf.train.AdamOptimizer(lr), trainer.py:117
+                                skip_nonfinite=getattr(self.FLAGS, "skip_nonfinite_steps", False))
+        self._guard_seen = {"applied": 0, "clipped": 0, "skipped": 0}
+        self.guard_intervals = []                                # one dict of guard_* numbers per evaluation (guard on)
         log = {"Xs": "Xs", "y_hat": "y_hat"}
         verbose = dp.rank() == 0
         check_exchange = getattr(self.SMC, "check_exchange", None)   # (PSVOwR: sticky flag of the kernels' bounded polls)
@@ -260,14 +268,39 @@ class trainer:
             print("Nan in log_ZSMC, stop training")
             raise StopTraining()
 
+        guard = self._guard_interval()
         if self.save_res:
             for key, val in m.items():
                 getattr(self, key + "s").append(val)
             if dp.rank() == 0:
                 os.makedirs(self.epoch_data_DIR, exist_ok=True)
                 with open(self.epoch_data_DIR + "metric_{}.p".format(iter_num + 1), "wb") as f:
-                    pickle.dump(dict(m), f)
+                    pickle.dump(dict(m, **guard), f)
+        if guard and guard["guard_skipped"] > 0 and guard["guard_applied"] == 0:
+            msg = ("every one of the {} training steps since the last evaluation had a non-finite gradient norm and was "
+                   "skipped: the model can no longer produce a finite gradient, stop training".format(guard["guard_skipped"]))
+            if dp.rank() == 0:
+                print(msg)
+            raise StopTraining(msg)
         return m["log_ZSMC_train"], m["log_ZSMC_test"], m["R_square_train"], m["R_square_test"]
+
+    def _guard_interval(self):
+        """{} with the guard off; else the optimizer's counts since the previous evaluation and its last / largest finite
+        gradient norm, as the guard_* keys of metric_<iter>.p (one device read; printed by rank 0; every rank holds the same
+        numbers because every rank steps on the same all-reduced gradient)"""
+        stats = self.optimizer.guard_stats() if self.optimizer is not None else None
+        if stats is None:
+            return {}
+        out = {"guard_last_norm": stats["last_norm"], "guard_max_norm": stats["max_norm"]}
+        for key in ("applied", "clipped", "skipped"):
+            out["guard_" + key] = stats[key] - self._guard_seen[key]
+            self._guard_seen[key] = stats[key]
+        self.guard_intervals.append(out)
+        if dp.rank() == 0:
+            print("gradient guard: last norm {:.4g}, largest norm {:.4g}; since the last evaluation {} steps applied "
+                  "({} of them clipped), {} skipped".format(out["guard_last_norm"], out["guard_max_norm"], out["guard_applied"],
+                                                            out["guard_clipped"], out["guard_skipped"]))
+        return out
 
     def adjust_lr(self, iter_num, print_freq):
         """Plateau schedule on the held-out ELBO history (trainer.py:244-270): whenever the best evaluation moves, both
