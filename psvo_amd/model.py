@@ -17,7 +17,9 @@ class LSTMBlockCellLayer(nn.Module):
 
     Parameters keep the TF layout: kernel (in + h, 4h) with gate order (i, j, f, o), bias (4h),
     forget_bias = 1 added to f.  The sequence loop itself is upstream of the particle path
-    (SURVEY section 8f-1); it runs through torch's fused LSTM (MIOpen) after a layout permute.
+    (SURVEY section 8f-1).  For tensors in HBM it is the persistent kernels psvo_bilstm_forward /
+    psvo_bilstm_backward on these parameters as they stand (StackBiRNN.forward).  Only CPU tensors go
+    through torch's LSTM after a layout permute (torch_weights): the host-side mirror of the CPU tests.
     """
 
     def __init__(self, Din, Dh, name="lstm"):

@@ -150,3 +150,48 @@ def kernel_names(fn):
         out = fn()
         torch.cuda.synchronize()
     return out, {e.name for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA}
+
+
+# ---- the encoder wirings at the widest instantiations (tests/test_gpu_lstm.py on the GPU, tests/test_host.py for the reference)
+# (mode, Dhs, width of the observations)
+ENCODER_WIRINGS = [("stack", [64, 64], 2), ("multi", [32, 64], 2), ("uni", [64, 32], 2), ("uni", [32], 100)]
+
+
+def encoder_layers(enc, dtype):
+    """StackBiRNN's cells in the oracle's layout, as fresh leaves"""
+    leaf = lambda p: p.detach().cpu().to(dtype).clone().requires_grad_(True)
+    layers = []
+    for i, fw in enumerate(enc.fw):
+        L = {"fw": (leaf(fw.kernel), leaf(fw.bias))}
+        if len(enc.bw):
+            L["bw"] = (leaf(enc.bw[i].kernel), leaf(enc.bw[i].bias))
+        layers.append(L)
+    return layers
+
+
+def oracle_encoder(mode, layers, x, dout):
+    """output and gradients ({parameter name: grad}, plus "x") of the wiring `mode` in the dtype of `x`"""
+    x = x.clone().requires_grad_(True)
+    if mode == "stack":
+        out = O.stack_bidirectional_rnn(x, layers)
+    elif mode == "multi":
+        out = torch.cat(O.bidirectional_rnn(x, layers), dim=-1)
+    else:
+        out = O.static_rnn(x, layers)
+    names, leaves = ["x"], [x]
+    for i, L in enumerate(layers):
+        for d in sorted(L):
+            names += ["%s.%d.kernel" % (d, i), "%s.%d.bias" % (d, i)]
+            leaves += list(L[d])
+    grads = torch.autograd.grad((out * dout.to(x.dtype)).sum(), leaves)
+    return out.detach().double(), {n: g.double() for n, g in zip(names, grads)}
+
+
+def make_encoder(mode, Dhs, Din, seed=3):
+    from psvo_amd.model import StackBiRNN
+    torch.manual_seed(seed)
+    enc = perturb_(StackBiRNN(Din, Dhs, "y_smoother", mode))
+    g = torch.Generator().manual_seed(50 + seed)
+    x = torch.randn(2, 7, Din, generator=g) * 1.5
+    dout = torch.randn(2, 7, enc.Dout, generator=g)
+    return enc, x, dout

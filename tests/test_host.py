@@ -375,3 +375,24 @@ def test_covariance_head_mirror_matches_oracle_on_cpu():
     with pytest.raises(NotImplementedError):
         MLP_transformation([8], 2, 2, output_cov=True, diag_cov=False)
     assert MLP_transformation([8], 2, 2, output_cov=False, diag_cov=True).transform(x)[1] is None    # MLP.py:40: no head
+
+
+@pytest.mark.parametrize("mode,Dhs,Din", Hh.ENCODER_WIRINGS, ids=["%s-Din%d" % (m, n) for m, _, n in Hh.ENCODER_WIRINGS])
+def test_oracle_encoder_gradients_match_torch_lstm_in_fp64(mode, Dhs, Din):
+    """The yardstick of tests/test_gpu_lstm.py checked independently: fp64 output and gradients of the oracle's three encoder
+    wirings (a Python loop over lstm_block_cell, torch autograd) against StackBiRNN's CPU path (torch's own LSTM on the
+    re-ordered weights) at the widest cells.  Both are fp64 evaluations of the same function: 1e-12 of each tensor's largest
+    entry leaves four digits over the ~1e-16 rounding of either."""
+    enc, x, dout = Hh.make_encoder(mode, Dhs, Din)
+    enc = enc.double()
+    o_ref, g_ref = Hh.oracle_encoder(mode, Hh.encoder_layers(enc, torch.float64), x.double(), dout)
+    xd = x.double().requires_grad_(True)
+    out = enc(xd)
+    (out * dout.double()).sum().backward()
+    got = {"x": xd.grad}
+    got.update({n: p.grad for n, p in enc.named_parameters()})
+    assert set(got) == set(g_ref) and len(got) == 1 + 2 * len(Dhs) * (1 if mode == "uni" else 2)
+    assert float((out.detach() - o_ref).abs().max()) <= 1e-12 * float(o_ref.abs().max())
+    for n, r in g_ref.items():
+        assert float(r.abs().max()) > 0, n
+        assert float((got[n] - r).abs().max()) <= 1e-12 * float(r.abs().max()), n
