@@ -219,6 +219,43 @@ int psvo_filter_backward_cov(const psvo_desc* desc,
                              float* ws, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Marginal particle smoother: forward filtering, backward smoothing (FFBS) on the particle system a forward filter left in
+ * HBM.  Restates FFBS_reweight_log_Ws of the reference's unused sweep code (not_used/SMC_supreme/SMC.py:451-482, with
+ * smoothing_perc = 1 and normalised inputs) and its resampling of X_prevs by the reweighted weights (:87-94); the flags FFBS /
+ * FFBS_to_learn are carried by auto_sh.py:94-97.  Added within ABI 6: purely additive, no existing struct or signature changed.
+ *
+ * Per sequence b, with a_t[k] = logW[t,b,k] - logsumexp_k logW[t,b,:] and the transition density
+ *     l_t[j,k] = log N(X[t+1,b,:,j]; Fm[t,b,:,k], s_t[:,k]),   diagonal, on SCALES, the -sum_d log s_t[d,k] term included,
+ *     s_t[:,k] = sig_f[:] (constant) or Fs[t,b,:,k] (per particle):
+ *     S[T-1][k] = a_{T-1}[k]
+ *     for t = T-2 .. 0:   den[j]  = logsumexp_k (a_t[k] + l_t[j,k])
+ *                         S[t][k] = a_t[k] + logsumexp_j (S[t+1][j] - den[j] + l_t[j,k])
+ * X[t+1] and Fm[t] are both pre-resampling histories, the pair the backward simulation's N x N term uses (PSVO.py:128-133).
+ * S[t] is renormalised at every step (an identity in exact arithmetic), so sum_k exp logWs[t,b,k] = 1 to fp32 rounding.
+ *
+ * One persistent workgroup per sequence walks t downwards; the N x N tile is recomputed in both pair phases and never
+ * written to HBM; no MLP is evaluated.  No atomics and every sum in a fixed order: two calls on the same inputs give
+ * bit-identical outputs, with or without PSVO_TUNE_DETERMINISTIC.  No gradient: the outputs are evaluation quantities.
+ *
+ *  desc            B, T, N, Dx are read; nothing else is looked at.  Dx in {2,3,4}, N <= 512 (else PSVO_ERR_UNSUPPORTED);
+ *                  T = 1 is valid (the output is then the normalised filter weights)
+ *  X, Fm (T,B,Dx,N) outputs of psvo_filter_forward / psvo_filter_forward_cov
+ *  Fs  (T,B,Dx,N)  per-particle transition scales (psvo_filter_forward_cov), or NULL
+ *  sig_f (Dx)      constant transition scale, or NULL; exactly one of Fs / sig_f (else PSVO_ERR_INVALID)
+ *  logW (T,B,N)    the filter's log-weights (entries of -inf are particles of weight zero)
+ *  u (T,B,N)       uniforms in [0,1) for N multinomial draws per step from exp logWs[t,b,:], or idx_in (T,B,N) teacher-forced
+ *                  draws (values clamped to [0, N)); both NULL = no draw.  The draw is the filter's: cdf[idx-1] <= u total < cdf[idx]
+ *                  on the inclusive prefix sums of the weights, last index clamped
+ *  outputs: logWs (T,B,N) normalised smoothed log-weights (required);
+ *           Xmean (T,B,Dx) = sum_k exp(logWs[t,b,k]) X[t,b,:,k] and ess (T,B) = 1 / sum_k exp(2 logWs[t,b,k]), each may be NULL;
+ *           Xs (T,B,Dx,N) = X[t,b,:,idx] and idx_out (T,B,N), each may be NULL; non-NULL needs u or idx_in (else PSVO_ERR_INVALID).
+ * ------------------------------------------------------------------------------------------- */
+int psvo_ffbs_smooth(const psvo_desc* desc,
+                     const float* X, const float* Fm, const float* Fs, const float* sig_f, const float* logW,
+                     const float* u, const int32_t* idx_in,
+                     float* logWs, float* Xmean, float* ess, float* Xs, int32_t* idx_out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Backward simulation with proposal, STATE-DEPENDENT diagonal scales (FLAGS.output_cov and FLAGS.diag_cov; see
  * psvo_filter_forward_cov).  Same loop and outputs as psvo_bsim_forward (PSVO.backward_simulation_w_proposal, reference
  * src/SMC/PSVO.py:69-203); differences:

@@ -32,6 +32,8 @@ class SVO:
 
         self.smooth_obs = True
         self.resample_particles = True
+        # marginal particle smoother behind the filter at evaluation time (FLAGS.FFBS; psvo_ffbs_smooth)
+        self.FFBS = bool(getattr(FLAGS, "FFBS", False))
 
         self.name = name
         self.generator = None        # torch.Generator on the compute device; None = global RNG
@@ -41,7 +43,14 @@ class SVO:
         """obs (batch, time, Dy), hidden (batch, time, Dx) -> (log_ZSMC scalar, {"Xs": (B,T,N,Dx)}).
 
         `noise` optionally injects the random draws in the HBM layout of include/psvo_hip.h:
-        eps_f (T,B,Dx,N), u_f (T,B,N) or idx_f (T,B,N) int32.
+        eps_f (T,B,Dx,N), u_f (T,B,N) or idx_f (T,B,N) int32; with FLAGS.FFBS also u_s (T,B,N) or idx_s (T,B,N) int32, the
+        draws of the smoothed particles.
+
+        With FLAGS.FFBS and autograd not recording (evaluation, trajectory saving, prediction) the marginal smoother runs
+        behind the filter: log["Xs"] then holds particles resampled by the SMOOTHED weights (the filtered ones move to
+        log["Xs_filter"]), and log["X_smooth_mean"] (B,T,Dx), log["ess_smooth"] (B,T), log["logW_smooth"] (T,B,N) and
+        log["smoother"] (the kernel's output dict in its own layout, with the drawn indices) are added.
+        Under autograd nothing changes: the smoother has no gradient and is not launched.
         """
         batch_size, time, _ = obs.shape
         self.Dx, self.batch_size, self.time = self.model.Dx, batch_size, time
@@ -54,8 +63,28 @@ class SVO:
         # (T, B, Dx, N) -> (batch_size, time, n_particles, Dx)
         log["Xs"] = filt["Xanc"].permute(1, 0, 3, 2)
         log["filter"] = filt
+        if self.FFBS and not torch.is_grad_enabled():
+            self._smooth(filt, log, noise or {})
         self._release()
         return log_ZSMC, log
+
+    def _smooth(self, filt, log, noise):
+        """forward filtering, backward smoothing on the particle system `filt` (psvo_ffbs_smooth): the transition scale is the
+        one the filter weighted with -- per particle under output_cov, else sigma_q1 when f shares q1's network, else sigma_f"""
+        T, B, N = self.time, self.batch_size, self.n_particles
+        sig_f = None
+        if filt.get("Fs") is None:
+            sig_f = _c(self._sigma(self.q1 if self.model.use_bootstrap else self.f))
+        u, idx_in = noise.get("u_s"), noise.get("idx_s")
+        if u is None and idx_in is None:
+            u = self._rand(T, B, N, device=filt["X"].device)
+        sm = ops.ffbs_smooth(self._desc(), filt, sig_f=sig_f, u=u, idx_in=idx_in)
+        log["Xs_filter"] = log["Xs"]
+        log["Xs"] = sm["Xs"].permute(1, 0, 3, 2)                       # (T, B, Dx, N) -> (batch_size, time, n_particles, Dx)
+        log["X_smooth_mean"] = sm["Xmean"].transpose(0, 1)
+        log["ess_smooth"] = sm["ess"].transpose(0, 1)
+        log["logW_smooth"] = sm["logWs"]
+        log["smoother"] = sm
 
     def _release(self):
         """drop what one evaluation cached on the object (scale vectors, hoisted means, features, stream context).

@@ -70,6 +70,9 @@ DEFINITIONS = [
     # gradient guard (not in the reference's registry; its sweep script passes clip_norm = 10.0, auto_sh.py:109): both off by default
     ("clip_norm", float, 0.0, "clip the gradient to this global L2 norm before Adam (0 = off)"),
     ("skip_nonfinite_steps", bool, False, "leave out a training step whose gradient norm is inf or NaN"),
+    # marginal particle smoother for the filter objectives (not in the reference's registry; its sweep script carries FFBS and
+    # FFBS_to_learn, auto_sh.py:94-97, for not_used/SMC_supreme/SMC.py:451-482): off by default, evaluation only
+    ("FFBS", bool, False, "SVO / AESMC / IWAE: evaluate with forward-filtering backward-smoothing weights and particles"),
     # printing and data saving (runner_flag.py:131-153)
     ("print_freq", int, 1, "frequency to evaluate testing loss & other metrics and save results"),
     ("save_trajectory", bool, True, "whether to save hidden trajectories during training"),

@@ -597,6 +597,39 @@ def filter_forward_cov(desc, q1, f, g, sigc_q1, sigc_f, sigc_g, mu2, sig2, m0, s
     return out
 
 
+def ffbs_smooth(desc, filt, sig_f=None, u=None, idx_in=None, want_draws=True):
+    """psvo_ffbs_smooth: the marginal particle smoother on a forward filter's outputs.  `filt` is the dict filter_forward /
+    filter_forward_cov returned (X, Fm, logW, and Fs for state-dependent scales); `sig_f` (Dx) is the constant transition
+    scale -- exactly one of filt["Fs"] / sig_f.  `u` (T,B,N) uniforms or `idx_in` (T,B,N) int32 teacher-forced draws are needed
+    when want_draws.  Returns dict(logWs (T,B,N), Xmean (T,B,Dx), ess (T,B), Xs (T,B,Dx,N), idx (T,B,N)); Xs / idx are None
+    without draws.  Asynchronous on the launch stream."""
+    lib = _lib.load()
+    B, T, N, Dx = desc.B, desc.T, desc.N, desc.Dx
+    X, Fm, Fs, logW = filt["X"], filt["Fm"], filt.get("Fs"), filt["logW"]
+    if X is None or Fm is None or logW is None:
+        raise ValueError("ffbs_smooth needs the filter's X, Fm and logW")
+    _chk(X, (T, B, Dx, N), "X"); _chk(Fm, (T, B, Dx, N), "Fm"); _chk(Fs, (T, B, Dx, N), "Fs"); _chk(logW, (T, B, N), "logW")
+    _chk(sig_f, (Dx,), "sig_f")
+    if (Fs is None) == (sig_f is None):
+        raise ValueError("ffbs_smooth takes exactly one transition scale: the filter's per-particle `Fs` or a constant `sig_f`")
+    _chk(u, (T, B, N), "u"); _chk(idx_in, (T, B, N), "idx_in", torch.int32)
+    if want_draws and u is None and idx_in is None:
+        raise ValueError("smoothed draws need uniforms `u` or teacher-forced `idx_in`")
+    dev = X.device
+    out = {"logWs": _empty(T, B, N, device=dev), "Xmean": _empty(T, B, Dx, device=dev), "ess": _empty(T, B, device=dev),
+           "Xs": _empty(T, B, Dx, N, device=dev) if want_draws else None,
+           "idx": _empty(T, B, N, device=dev, dtype=torch.int32) if want_draws else None}
+    if not want_draws:
+        u = idx_in = None
+    _mark("psvo_ffbs_smooth", 0)
+    st = lib.psvo_ffbs_smooth(ctypes.byref(desc), _ptr(X), _ptr(Fm), _ptr(Fs), _ptr(sig_f), _ptr(logW), _ptr(u), _ptr(idx_in),
+                              _ptr(out["logWs"]), _ptr(out["Xmean"]), _ptr(out["ess"]), _ptr(out["Xs"]), _ptr(out["idx"]),
+                              _stream())
+    _mark("psvo_ffbs_smooth", 1)
+    _lib.check(st, "psvo_ffbs_smooth")
+    return out
+
+
 def filter_backward_cov(desc, q1, f, g, sigc_q1, sigc_f, sigc_g, mu2, sig2, m0, sig0, fm0, fsig0, obs, eps, filt,
                         dlse=None, dFm=None, dFs=None, dlogW=None):
     """psvo_filter_backward_cov + two psvo_mlp_wgrad launches per MLP (one per head; both contribute to dW1 / db1).

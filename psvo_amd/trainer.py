@@ -15,6 +15,11 @@ Gradient guard (new relative to the reference's trainer; FLAGS.clip_norm, FLAGS.
 optimizer clips by the global norm and leaves non-finite steps out on the device (psvo_amd.optim.TFAdam).  The norm is taken
 after the all-reduce, so every rank decides alike.  At every evaluation the counts since the previous one are printed, go into
 metric_<iter>.p under the guard_* keys, and an interval in which every step was skipped stops the training.
+
+Marginal smoother (FLAGS.FFBS, off by default; SVO / AESMC / IWAE): every evaluation then runs psvo_ffbs_smooth behind the filter
+(psvo_amd.SMC.SVO), so "Xs", the k-step predictions and the saved trajectories come from the smoothed particles; the mean and the
+minimum of the smoothed weights' effective sample size over each split are printed and go into metric_<iter>.p as
+ffbs_ess_mean_<split> / ffbs_ess_min_<split>.  Training steps are untouched.
 """
 import math
 import os
@@ -251,10 +256,13 @@ class trainer:
     def evaluate_and_save_metrics(self, iter_num, y_hat_N_BxTxDy=None, y_N_BxTxDy=None):
         """ELBO and k-step R-square on the training and held-out sets; appended to the histories and pickled as
         metric_<iter>.p with the reference's keys (trainer.py:201-241).  A non-finite training ELBO stops training."""
-        fetches = ["log_ZSMC", "y_hat", "y"]
-        m = {}
+        ffbs = bool(getattr(self.SMC, "FFBS", False))
+        fetches = ["log_ZSMC", "y_hat", "y"] + (["ess_smooth"] if ffbs else [])
+        m, ess = {}, {}
         for split, obs, hid in (("train", self.obs_train, self.hidden_train), ("test", self.obs_test, self.hidden_test)):
-            elbos, y_hat, y = self.evaluate(fetches, {self.obs: obs, self.hidden: hid})
+            elbos, y_hat, y, *rest = self.evaluate(fetches, {self.obs: obs, self.hidden: hid})
+            if ffbs:
+                ess["ffbs_ess_mean_" + split], ess["ffbs_ess_min_" + split] = float(np.mean(rest[0])), float(np.min(rest[0]))
             m["log_ZSMC_" + split] = np.mean(elbos)
             m["R_square_" + split] = self.evaluate_R_square(y_hat, y)
 
@@ -263,6 +271,10 @@ class trainer:
             print("iter", iter_num + 1)
             print("Train log_ZSMC: {:>7.3f}, valid log_ZSMC: {:>7.3f}".format(m["log_ZSMC_train"], m["log_ZSMC_test"]))
             print("Train, Valid k-step Rsq:\n", m["R_square_train"], "\n", m["R_square_test"])
+            if ffbs:
+                print("FFBS effective sample size (of {} particles), mean / min: train {:.2f} / {:.2f}, valid {:.2f} / {:.2f}"
+                      .format(self.n_particles, ess["ffbs_ess_mean_train"], ess["ffbs_ess_min_train"],
+                              ess["ffbs_ess_mean_test"], ess["ffbs_ess_min_test"]))
 
         if not math.isfinite(m["log_ZSMC_train"]):
             print("Nan in log_ZSMC, stop training")
@@ -275,7 +287,7 @@ class trainer:
             if dp.rank() == 0:
                 os.makedirs(self.epoch_data_DIR, exist_ok=True)
                 with open(self.epoch_data_DIR + "metric_{}.p".format(iter_num + 1), "wb") as f:
-                    pickle.dump(dict(m, **guard), f)
+                    pickle.dump(dict(m, **guard, **ess), f)
         if guard and guard["guard_skipped"] > 0 and guard["guard_applied"] == 0:
             msg = ("every one of the {} training steps since the last evaluation had a non-finite gradient norm and was "
                    "skipped: the model can no longer produce a finite gradient, stop training".format(guard["guard_skipped"]))
@@ -346,6 +358,8 @@ class trainer:
                     y_hat, y = self.SMC.n_step_prediction(self.MSE_steps, Xs, obs_d)
                     out["y_hat"] = [v.cpu().numpy() for v in y_hat]
                     out["y"] = [v.cpu().numpy() for v in y]
+            if "ess_smooth" in names:
+                out["ess_smooth"] = log["ess_smooth"].contiguous().cpu().numpy()      # (B, T); FLAGS.FFBS only
         return [out[n] for n in names]
 
     def evaluate(self, fetches, feed_dict_w_batches={}, average=False, keepdims=False):
