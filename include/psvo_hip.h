@@ -24,7 +24,8 @@
  *   - per-particle MLPs have ONE hidden layer of width H (reference default `*_layers=[32]`,
  *     src/runner_flag.py:53-57) or TWO of the same width (`*_layers=[64, 64]`, the example the reference's flag
  *     file gives, src/runner_flag.py:50-52; psvo_desc.layers = 2); kernels are instantiated for Dx in {2,3,4},
- *     Dy in {1,2}, H in {16,32,64} (two layers: {32,64}), M in {4,8,16,32}; N <= 512 (filter, PSVOwR reverse
+ *     Dy in {1,2} (3 .. 32 for the filter alone: the *_wobs entry points), H in {16,32,64} (two layers: {32,64}),
+ *     M in {4,8,16,32}; N <= 512 (filter, PSVOwR reverse
  *     pass), N <= 1024 (backward simulation); any T, B <= 65535.  Anything else returns PSVO_ERR_UNSUPPORTED
  *     (never a silent fallback).
  */
@@ -566,6 +567,56 @@ int psvo_filter_backward(const psvo_desc* desc,
                          float* dP, float* dF, float* dG, float* dmu2, float* dm0, float* dfm0,
                          float* dsig_q1, float* dsig_q2, float* dsig_f, float* dsig_g, float* dsig0, float* dfsig0,
                          float* sacc, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Wide observations ("wobs"): the forward filter, its reverse pass and MLP_g's weight gradient for 3 <= Dy <= 32
+ * (psvo_amd/csrc/filter_wobs.hip; added within ABI 6 -- the entry points above keep Dy in {1, 2}).  For the filter objectives
+ * (SVO, AESMC, IWAE); the backward simulations evaluate MLP_g too and stay at Dy <= 2.
+ * Envelope of the two filter entry points: 3 <= Dy <= 32 (a run-time bound, nothing is instantiated per width), Dx in {2,3,4},
+ * H in {16,32,64} (narrower: zero-padded by the caller as above), N <= 512, one hidden layer (desc->layers <= 1), Gaussian and
+ * Poisson emission, every bootstrap / two_q wiring, resampling on or off.  Anything else -- Dy <= 2 and Dy > 32 included --
+ * returns PSVO_ERR_UNSUPPORTED before a device is touched.
+ *
+ * psvo_filter_forward_wobs: arguments, outputs, layouts and the draw rule of psvo_filter_forward (idx = the number of CDF
+ *   entries <= u * total, clamped to N - 1; or teacher-forced idx_in), so that psvo_elbo_filter, psvo_ffbs_smooth and the host
+ *   code consume the result unchanged.  One persistent workgroup per sequence, lane = particle.  MLP_g's output layer and the
+ *   step's observation row are read from LDS at wave-uniform addresses (the row of step t+1 is in flight while step t
+ *   computes); the emission log-density adds its Dy terms in the order e = 0 .. Dy-1.
+ * psvo_filter_backward_wobs: reverse mode of it with the outputs of psvo_filter_backward (dP, dF, dG (T,B,Dy,N); dmu2, dm0,
+ *   dfm0; dsig_q1, dsig_q2, dsig_f, dsig_g (Dy), dsig0, dfsig0) and its m0 / fm0 (sig0 / fsig0) aliasing rule.  Upstream
+ *   gradient: dlse (T,B) only (NULL = 0).  ws: psvo_filter_wobs_ws_floats(B, T, N, Dx, Dy) floats (per-sequence sums, then the
+ *   (T,B,Dx,N) rows of d mu2).  Every sum has one fixed order and there are no float atomics: a parent particle adds the
+ *   gradients of its children in child order, sums over particles are per-lane columns folded in lane / wave order, sums over
+ *   sequences in sequence order.  Two runs of the same inputs are bit-identical whatever PSVO_TUNE_DETERMINISTIC is.
+ * psvo_mlp_wgrad_wobs: the contract of psvo_mlp_wgrad (grad = [dW1 | db1 | dW2 | db2], keras layout; X [S][Din][L],
+ *   dOut [S][Dout][L]; accumulate != 0 adds into grad) for Din <= 4, H in {16,32,64}, 3 <= Dout <= 32.  dW2 = h^T dOut and
+ *   dh = dOut W2^T run on v_mfma_f32_16x16x4_f32 over LDS tiles of 64 rows, dW1 / db1 / db2 and the relu mask on the vector
+ *   ALU; rows past the end contribute nothing.  partial: psvo_mlp_wgrad_wobs_blocks(S*L) * len(grad) floats, one slice per
+ *   workgroup, folded in workgroup order.
+ * ------------------------------------------------------------------------------------------- */
+int psvo_filter_forward_wobs(const psvo_desc* desc,
+                             const psvo_mlp* q1, const psvo_mlp* f, const psvo_mlp* g,
+                             const float* sig_q1, const float* sig_q2, const float* sig_f, const float* sig_g,
+                             const float* mu2,
+                             const float* m0, const float* sig0, const float* fm0, const float* fsig0,
+                             const float* obs, const float* eps, const float* u, const int32_t* idx_in,
+                             float* X, float* Xanc, float* Fm, float* P1, float* logW, int32_t* idx_out,
+                             float* lse, void* stream);
+long long psvo_filter_wobs_ws_floats(int B, int T, int N, int Dx, int Dy);
+int psvo_filter_backward_wobs(const psvo_desc* desc,
+                              const psvo_mlp* q1, const psvo_mlp* f, const psvo_mlp* g,
+                              const float* sig_q1, const float* sig_q2, const float* sig_f, const float* sig_g,
+                              const float* mu2,
+                              const float* m0, const float* sig0, const float* fm0, const float* fsig0,
+                              const float* obs, const float* eps,
+                              const float* X, const float* Fm, const float* P1, const float* logW, const float* lse,
+                              const int32_t* idx, const float* dlse,
+                              float* dP, float* dF, float* dG, float* dmu2, float* dm0, float* dfm0,
+                              float* dsig_q1, float* dsig_q2, float* dsig_f, float* dsig_g, float* dsig0, float* dfsig0,
+                              float* ws, void* stream);
+int psvo_mlp_wgrad_wobs_blocks(long long rows);
+int psvo_mlp_wgrad_wobs(long long S, int L, int Din, int H, int Dout, const float* X, const float* dOut,
+                        const psvo_mlp* w, float* partial, float* grad, int accumulate, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * One-hidden-layer MLP over plain rows (the hoisted per-(sequence, step) networks q0, q2, BSim_q2,

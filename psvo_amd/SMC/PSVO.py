@@ -12,6 +12,8 @@ from .SVO import SVO
 
 
 class PSVO(SVO):
+    uses_backward_simulation = True
+
     def __init__(self, model, FLAGS, name="log_ZSMC"):
         SVO.__init__(self, model, FLAGS, name="log_ZSMC")
 

@@ -9,12 +9,18 @@ permutes the result to the reference's (batch, time, particles, Dx).
 import torch
 
 from .. import ops
-from ..autograd import FilterCovFunction, FilterFunction
+from ..autograd import FilterCovFunction, FilterFunction, FilterWobsFunction
 
 
 class SVO:
+    # the objective runs a backward simulation behind the filter (PSVO, PSVOwR): those kernels evaluate MLP_g for Dy <= 2 only
+    uses_backward_simulation = False
+    # observation widths of the plain filter kernels / of the wide-observation ("wobs") kernels (csrc/filter_wobs.hip)
+    _PLAIN_DY, _WOBS_MAX_DY = 2, 32
+
     def __init__(self, model, FLAGS, name="log_ZSMC"):
         self.model = model
+        self.wide_obs = self._route_wide_obs(model)
 
         # SSM distributions
         self.q0 = model.q0_dist
@@ -37,6 +43,29 @@ class SVO:
 
         self.name = name
         self.generator = None        # torch.Generator on the compute device; None = global RNG
+
+    @classmethod
+    def _route_wide_obs(cls, model):
+        """True when the filter of this objective runs on the wide-observation kernels (model.Dy > 2: psvo_filter_forward_wobs /
+        psvo_filter_backward_wobs / psvo_mlp_wgrad_wobs).  What those kernels do not cover is refused here, up front."""
+        Dy = getattr(model, "Dy", cls._PLAIN_DY)          # (a bare model object without widths has nothing to route)
+        if Dy <= cls._PLAIN_DY:
+            return False
+        limit = "observations wider than Dy = %d run on the wide-observation filter kernels" % cls._PLAIN_DY
+        if Dy > cls._WOBS_MAX_DY:
+            raise ValueError("Dy = %d: %s, which take 3 <= Dy <= %d; no fallback path exists" % (Dy, limit, cls._WOBS_MAX_DY))
+        if cls.uses_backward_simulation:
+            raise ValueError("Dy = %d with PSVO / PSVOwR: %s of the filter objectives (SVO, AESMC, IWAE); the backward-simulation "
+                             "kernels evaluate the emission network for Dy <= %d only" % (Dy, limit, cls._PLAIN_DY))
+        if model.output_cov:
+            raise ValueError("Dy = %d with output_cov: %s, which take state-independent scales; the state-dependent-scale "
+                             "kernels take Dy <= %d" % (Dy, limit, cls._PLAIN_DY))
+        trans = [model.q1_tran, model.g_tran] + ([] if model.use_bootstrap else [model.f_tran])
+        deep = [t.Dhs for t in trans if len(t.Dhs) != 1]
+        if deep:
+            raise ValueError("Dy = %d with per-particle MLP layers %s: %s, which take one hidden layer per MLP; two hidden "
+                             "layers run for Dy <= %d only" % (Dy, deep, limit, cls._PLAIN_DY))
+        return True
 
     # ------------------------------------------------------------------------------------------
     def get_log_ZSMC(self, obs, hidden, noise=None):
@@ -255,8 +284,11 @@ class SVO:
         desc = self._desc()
         gb = (self._gbuf(model.q1_tran), None if model.use_bootstrap else self._gbuf(model.f_tran), self._gbuf(model.g_tran))
         desc._gbufs = gb if (gb[0] is not None and gb[2] is not None and (model.use_bootstrap or gb[1] is not None)) else None
-        # one opaque autograd node: psvo_filter_forward / psvo_filter_backward
-        lse, Fm, logW, X, Xanc, idx = FilterFunction.apply(
+        # one opaque autograd node: psvo_filter_forward / psvo_filter_backward, or their wide-observation forms (Dy > 2)
+        node = FilterFunction
+        if self.wide_obs:
+            node, desc._gbufs = FilterWobsFunction, None
+        lse, Fm, logW, X, Xanc, idx = node.apply(
             desc, obs_TB, eps, u, idx_in,
             *first, self._sigma(self.q1), sig_q2, sig_f, self._sigma(self.g), mu2, m0, sig0, fm0, fsig0, *extra)
         return {"lse": lse, "Fm": Fm, "logW": logW, "X": X, "Xanc": Xanc, "idx": idx, "eps": eps, "u": u}

@@ -320,6 +320,47 @@ class FilterCovFunction(torch.autograd.Function):
             r["dm0"], r["dsig0"], r["dfm0"], r["dfsig0"])
 
 
+class FilterWobsFunction(torch.autograd.Function):
+    """psvo_filter_forward_wobs / psvo_filter_backward_wobs: the forward filter for wide observations (3 <= Dy <= 32, one hidden
+    layer per particle MLP) of the filter objectives SVO / AESMC / IWAE.
+
+    apply(...) takes FilterFunction's arguments and returns its outputs; lse is the differentiable one (the reverse kernel takes
+    no upstream gradient of Fm / logW: no backward simulation runs behind a wide filter).
+    One stream, gradients returned as tensors (no in-place accumulation into the flat buffer)."""
+
+    @staticmethod
+    def forward(ctx, desc, obs_TB, eps, u, idx_in, *t):
+        ctx.set_materialize_grads(False)
+        t = [_cf(v) for v in t]
+        q1, f, g = _mlps(t)
+        rest = t[12:21]                 # sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, fm0, fsig0
+        if desc.bootstrap:
+            f = None
+        filt = ops.filter_forward_wobs(desc, q1, f, g, *rest, obs_TB, eps, u, idx_in)
+        ctx.desc, ctx.filt = desc, _aliases(filt)
+        ctx.saved = (q1, f, g, rest, obs_TB, eps)
+        ctx.mark_non_differentiable(filt["X"], filt["Xanc"], filt["idx"])
+        return filt["lse"], filt["Fm"], filt["logW"], filt["X"], filt["Xanc"], filt["idx"]
+
+    @staticmethod
+    def backward(ctx, dlse, dFm, dlogW, *_):
+        desc = ctx.desc
+        q1, f, g, rest, obs_TB, eps = ctx.saved
+        r = ops.filter_backward_wobs(desc, q1, f, g, *rest, obs_TB, eps, ctx.filt, dlse=_cg(dlse), dFm=_cg(dFm),
+                                     dlogW=_cg(dlogW))
+        Dx, Dy, H = desc.Dx, desc.Dy, desc.H
+        two_q, boot = bool(desc.two_q), bool(desc.bootstrap)
+        gfirst, _ = _mlp_grads(r, ("gq1", None if boot else "gf", "gg"), ((Dx, Dx), (Dx, Dx), (Dx, Dy)), H, 1,
+                               (None, None, None))
+        m0, sig0, fm0, fsig0 = rest[5:9]
+        same_m = m0.data_ptr() == fm0.data_ptr()       # (one tensor as both: the kernel put the sum into d m0)
+        same_s = sig0.data_ptr() == fsig0.data_ptr()
+        return (None, None, None, None, None) + gfirst + (
+            r["dsig_q1"], r["dsig_q2"] if two_q else None, None if boot else r["dsig_f"], r["dsig_g"],
+            r["dmu2"] if two_q else None, r["dm0"], r["dsig0"], None if same_m else r["dfm0"],
+            None if same_s else r["dfsig0"])
+
+
 def _filter_node_of(Fm, ov):
     """the FilterFunction node that produced `Fm` in this evaluation (its ctx), if the overlap wiring is on: the
     backward-simulation node may launch that node's reverse kernel early.  (A downstream reference only: this node

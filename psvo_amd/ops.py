@@ -194,8 +194,8 @@ def _mark(name, phase):
 
 
 def filter_forward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, fm0, fsig0,
-                   obs, eps, u=None, idx_in=None):
-    """psvo_filter_forward.  Returns dict(X, Xanc, Fm, logW, idx, lse)."""
+                   obs, eps, u=None, idx_in=None, entry="psvo_filter_forward"):
+    """psvo_filter_forward (`entry`: an entry point with the same contract).  Returns dict(X, Xanc, Fm, logW, idx, lse)."""
     lib = _lib.load()
     B, T, N, Dx, Dy, H = desc.B, desc.T, desc.N, desc.Dx, desc.Dy, desc.H
     dev = eps.device
@@ -219,16 +219,22 @@ def filter_forward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, 
         "idx": _empty(T, B, N, device=dev, dtype=torch.int32), "lse": _empty(T, B, device=dev),
         "P1": None if desc.bootstrap else _empty(T, B, Dx, N, device=dev),
     }
-    _mark("psvo_filter_forward", 0)
-    st = lib.psvo_filter_forward(
+    _mark(entry, 0)
+    st = getattr(lib, entry)(
         ctypes.byref(desc), ctypes.byref(q1s), ctypes.byref(fs) if fs is not None else None, ctypes.byref(gs),
         _ptr(sig_q1), _ptr(sig_q2), _ptr(sig_f), _ptr(sig_g), _ptr(mu2), _ptr(m0), _ptr(sig0), _ptr(fm0),
         _ptr(fsig0), _ptr(obs), _ptr(eps), _ptr(u), _ptr(idx_in),
         _ptr(out["X"]), _ptr(out["Xanc"]), _ptr(out["Fm"]), _ptr(out["P1"]), _ptr(out["logW"]), _ptr(out["idx"]),
         _ptr(out["lse"]), _stream())
-    _mark("psvo_filter_forward", 1)
-    _lib.check(st, "psvo_filter_forward")
+    _mark(entry, 1)
+    _lib.check(st, entry)
     return out
+
+
+def filter_forward_wobs(*args, **kw):
+    """psvo_filter_forward_wobs: the forward filter for wide observations (3 <= Dy <= 32, one hidden layer); arguments,
+    outputs and layouts of filter_forward."""
+    return filter_forward(*args, entry="psvo_filter_forward_wobs", **kw)
 
 
 # The plain backward simulations (PSVO: bsim_*, PSVOwR: bsimwr_*) take the same inputs ahead of their own and their reverse
@@ -365,9 +371,10 @@ def bilstm_forward(x, W_fw, b_fw, W_bw, b_bw, save=False):
     return (out, cs, gates) if save else out
 
 
-def mlp_wgrad(X, dOut, w, Din, H, Dout, grad=None, axis=2):
+def mlp_wgrad(X, dOut, w, Din, H, Dout, grad=None, axis=2, wobs=False):
     """psvo_mlp_wgrad / psvo_mlp2_wgrad: rows X [S][Din][L], dOut [S][Dout][L] -> flat grad [dW1|db1|dW2|db2]
     (two hidden layers, len(w) == 6: [dW1|db1|dWh|dbh|dW2|db2], the H x H products on the f32 matrix instruction).
+    wobs: psvo_mlp_wgrad_wobs, one hidden layer with 3 <= Dout <= 32 (the H x Dout products on the matrix instruction).
     X / dOut are contiguous tensors whose feature axis is `axis` (dims before it flatten to the
     segments S, dims after it to the rows L of a segment), e.g. (T,B,Din,N) or (T,B,Din,N,M)."""
     lib = _lib.load()
@@ -385,9 +392,11 @@ def mlp_wgrad(X, dOut, w, Din, H, Dout, grad=None, axis=2):
         L *= v
     ws = _mlp_struct(w, Din, H, Dout, "w")
     two = len(w) == 6
-    name = "psvo_mlp2_wgrad" if two else "psvo_mlp_wgrad"
+    if two and wobs:
+        raise ValueError("mlp_wgrad: the wide-output weight gradient takes one hidden layer")
+    name = "psvo_mlp2_wgrad" if two else "psvo_mlp_wgrad_wobs" if wobs else "psvo_mlp_wgrad"
     NP = mlp_grad_size(Din, H, Dout, 2 if two else 1)
-    nblk = (lib.psvo_mlp2_wgrad_blocks if two else lib.psvo_mlp_wgrad_blocks)(S * L)
+    nblk = getattr(lib, name + "_blocks")(S * L)
     partial = _empty(nblk, NP, device=dev)
     acc = grad is not None
     if grad is None:
@@ -400,6 +409,11 @@ def mlp_wgrad(X, dOut, w, Din, H, Dout, grad=None, axis=2):
     _mark(name, 1)
     _lib.check(st, name)
     return grad
+
+
+def mlp_wgrad_wobs(X, dOut, w, Din, H, Dout, grad=None, axis=2):
+    """psvo_mlp_wgrad_wobs: mlp_wgrad for an MLP with 3 <= Dout <= 32 outputs"""
+    return mlp_wgrad(X, dOut, w, Din, H, Dout, grad=grad, axis=axis, wobs=True)
 
 
 def rows_mlp_forward(X, w):
@@ -483,9 +497,10 @@ def split_mlp_grad(g, Din, H, Dout, layers=1):
 
 
 def filter_backward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, fm0, fsig0, obs, eps, filt,
-                    dlse=None, dFm=None, dlogW=None, gbufs=None, before_wgrad=None, defer_wgrad=False):
+                    dlse=None, dFm=None, dlogW=None, gbufs=None, before_wgrad=None, defer_wgrad=False, wobs=False):
     """psvo_filter_backward + psvo_mlp_wgrad.  `filt` = forward outputs.  dFm (T,B,Dx,N) / dlogW (T,B,N)
-    are upstream gradients (or None).  Returns a dict of gradients."""
+    are upstream gradients (or None).  Returns a dict of gradients.
+    wobs: psvo_filter_backward_wobs + psvo_mlp_wgrad_wobs for MLP_g (wide observations; upstream gradient dlse only)."""
     lib = _lib.load()
     B, T, N, Dx, Dy, H = desc.B, desc.T, desc.N, desc.Dx, desc.Dy, desc.H
     dev = eps.device
@@ -497,20 +512,24 @@ def filter_backward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0,
     out = {"dP": z(T, B, Dx, N), "dF": None if desc.bootstrap else z(T, B, Dx, N), "dG": z(T, B, Dy, N),
            "dmu2": z(T, B, Dx) if desc.two_q else None, "dm0": z(B, Dx), "dfm0": z(B, Dx),
            "dsig_q1": z(Dx), "dsig_q2": z(Dx), "dsig_f": z(Dx), "dsig_g": z(Dy), "dsig0": z(Dx), "dfsig0": z(Dx)}
-    sacc = z(lib.psvo_filter_ws_floats(B, T, N, Dx, Dy))
+    name = "psvo_filter_backward_wobs" if wobs else "psvo_filter_backward"
+    if wobs and (dFm is not None or dlogW is not None):
+        raise ValueError("%s takes the upstream gradient of lse only (no backward simulation behind a wide filter)" % name)
+    sacc = z((lib.psvo_filter_wobs_ws_floats if wobs else lib.psvo_filter_ws_floats)(B, T, N, Dx, Dy))
     nparts = 1 if (dFm is not None or dlogW is not None) else 0
-    _mark("psvo_filter_backward", 0)
+    upstream = (_ptr(dlse),) if wobs else (_ptr(dlse), nparts, _ptr(dFm), _ptr(dlogW))
+    _mark(name, 0)
     with _fixed_order():
-        st = lib.psvo_filter_backward(
+        st = getattr(lib, name)(
             ctypes.byref(desc), ctypes.byref(q1s), ctypes.byref(fs) if fs is not None else None, ctypes.byref(gs),
             _ptr(sig_q1), _ptr(sig_q2), _ptr(sig_f), _ptr(sig_g), _ptr(mu2), _ptr(m0), _ptr(sig0), _ptr(fm0), _ptr(fsig0),
             _ptr(obs), _ptr(eps), _ptr(filt["X"]), _ptr(filt["Fm"]), _ptr(filt["P1"]), _ptr(filt["logW"]),
-            _ptr(filt["lse"]), _ptr(filt["idx"]), _ptr(dlse), nparts, _ptr(dFm), _ptr(dlogW),
+            _ptr(filt["lse"]), _ptr(filt["idx"]), *upstream,
             _ptr(out["dP"]), _ptr(out["dF"]), _ptr(out["dG"]), _ptr(out["dmu2"]), _ptr(out["dm0"]), _ptr(out["dfm0"]),
             _ptr(out["dsig_q1"]), _ptr(out["dsig_q2"]), _ptr(out["dsig_f"]), _ptr(out["dsig_g"]), _ptr(out["dsig0"]),
             _ptr(out["dfsig0"]), _ptr(sacc), _stream())
-    _mark("psvo_filter_backward", 1)
-    _lib.check(st, "psvo_filter_backward")
+    _mark(name, 1)
+    _lib.check(st, name)
     # weight gradients from rows; gbufs = (q1, f, g) slices of the flat gradient buffer to accumulate into
     # directly (then no gradient tensor is returned for that MLP), or None
     gb = gbufs or (None, None, None)
@@ -525,9 +544,9 @@ def filter_backward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0,
             for t in (filt["X"], out["dG"]):
                 t.record_stream(g_stream)
             with launch_on(g_stream):
-                out["gg"] = mlp_wgrad(filt["X"], out["dG"], g, Dx, H, Dy, grad=gb[2])
+                out["gg"] = mlp_wgrad(filt["X"], out["dG"], g, Dx, H, Dy, grad=gb[2], wobs=wobs)
         else:
-            out["gg"] = mlp_wgrad(filt["X"], out["dG"], g, Dx, H, Dy, grad=gb[2])
+            out["gg"] = mlp_wgrad(filt["X"], out["dG"], g, Dx, H, Dy, grad=gb[2], wobs=wobs)
     if defer_wgrad:          # the caller issues them later (out["_wgrad"]()), e.g. after other writers of the same slices
         out["_wgrad"] = wgrad
         return out
@@ -535,6 +554,12 @@ def filter_backward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0,
         before_wgrad()
     wgrad()
     return out
+
+
+def filter_backward_wobs(*args, **kw):
+    """psvo_filter_backward_wobs + psvo_mlp_wgrad (q1, f) + psvo_mlp_wgrad_wobs (g): the reverse of filter_forward_wobs;
+    arguments and result of filter_backward without dFm / dlogW."""
+    return filter_backward(*args, wobs=True, **kw)
 
 
 # ---------------------------------------------------------------------------------------------
