@@ -734,6 +734,24 @@ __device__ __forceinline__ void quad_bcast4(float v, float (&out)[4]) {
     out[3] = dpp_mov<0xFF>(v, v);
 }
 
+// one 32-bit word of a per-step input array whatever its element type (float values and int32 indices travel through the same
+// slots and are bit-cast back by the consumer): may_alias keeps type-based alias analysis from ordering these reads against
+// accesses of the other type
+typedef float __attribute__((__may_alias__)) in_word_t;
+
+// field f of a list that a quad holds spread over its lanes (lane p has fields p, p + 4, .. in slots 0, 1, ..), in all four
+// lanes: one v_mov_dpp (f is a constant after unrolling), to be called under uniform control flow
+template <int NS>
+__device__ __forceinline__ float quad_field(const float (&slot)[NS], int f) {
+    const float v = slot[f >> 2];
+    switch (f & 3) {
+        case 0: return dpp_mov<0x00>(v, v);
+        case 1: return dpp_mov<0x55>(v, v);
+        case 2: return dpp_mov<0xAA>(v, v);
+        default: return dpp_mov<0xFF>(v, v);
+    }
+}
+
 // all-reduce over aligned groups of G lanes (G a power of two <= 64)
 template <int G>
 __device__ __forceinline__ float group_sum(float v) {

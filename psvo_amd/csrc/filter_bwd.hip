@@ -543,51 +543,130 @@ __global__ void __launch_bounds__(512) filter_bwd_lpp_kernel(const FilterBwdArgs
         return (t >= 1 && a.resample) ? a.idx[((size_t)(t - 1) * B + b) * N + n] : n;
     };
     const bool one_part = (a.nparts == 1);
-    // issue-only prefetch (see filter_bwd_kernel)
-    auto load_step = [&](int t, int anc, float (&sx)[DX], float (&se)[DX], float (&sm2)[DX], float (&sy)[DY],
-                         float (&smean1)[DX], float (&sfmean)[DX], float (&sdfm)[DX], float (&ssc)[4]) {
-        const size_t tb = (size_t)t * B + b;
-        const size_t tp = (t == 0) ? tb : tb - B;
+    const bool ext_fm = a.dFm_ext && one_part, ext_lw = a.dlogW_ext && one_part;
+    // Per-step inputs: the quad fetches each of them ONCE (see filter_fwd_lpp_kernel).  The field list is
+    //   X[DX] | eps[DX] | Fm[anc][DX] | dFm_ext[DX] | logW | dlogW_ext | next ancestor | mu2[DX] | obs[DY] | lse | dlse | P1[anc][DX]
+    // and lane p of the quad loads fields p, p + 4, ..: kSlots loads per lane and step (one fewer when bootstrap leaves the
+    // last slot empty) instead of one per field.  A field of step t reads row max(t - lag, 0) of its (T, B, ., N) array: lag
+    // 1 for the parent's Fm / P1 (row t - 1, indexed by the ancestor), lag 2 for the ancestor index that step t - 1 will
+    // gather with (idx row t - 2).  Pointer, stride and lag of the lane's slots are set up here, once; the upstream
+    // gradients in several parts (nparts > 1) keep their own loads below.
+    constexpr int kFX = 0, kFE = DX, kFFm = 2 * DX, kFDf = 3 * DX, kFLw = 4 * DX, kFDlw = 4 * DX + 1, kFAnc = 4 * DX + 2,
+                  kFM2 = 4 * DX + 3, kFY = 5 * DX + 3, kFLse = 5 * DX + 3 + DY, kFDlse = kFLse + 1, kFP1 = kFLse + 2,
+                  kFields = kFP1 + DX, kSlots = (kFields + 3) / 4;
+    // (one invariant ties the three places that know about lags together: field_ptr gives lag 1 to exactly the fields of
+    //  [kFFm, kFFm + DX) and [kFP1, kFP1 + DX) and lag 2 to kFAnc alone; slot_gathers / slot_lags below are the per-slot
+    //  shadows of those ranges, and issue_step adds the ancestor to a lane's address iff its lag is 1)
+    static_assert(kFAnc >= kFFm + DX && kFAnc < kFP1, "the ancestor field (lag 2) lies outside the gathered (lag 1) ranges");
+    const int nslots = a.bootstrap ? (kFP1 + 3) / 4 : kSlots;
+    auto slot_gathers = [](int s) { return (4 * s < kFFm + DX && 4 * s + 3 >= kFFm) || (4 * s < kFP1 + DX && 4 * s + 3 >= kFP1); };
+    auto slot_lags = [&](int s) { return slot_gathers(s) || (4 * s <= kFAnc && 4 * s + 3 >= kFAnc); };
+    const in_word_t* in_ptr[kSlots];
+    int in_str[kSlots], in_lag[kSlots];           // floats per time step; rows behind t
+    // (the field of a lane is picked by selects over the slot's four candidates, each a compile-time field: an if / else chain
+    //  on the lane's own field number would be a divergent branch per field)
+    auto field_ptr = [&](int f, const in_word_t*& ptr, int& str, int& lg) {
+        const in_word_t* q = nullptr;                 // base of the field's array at (row 0, b); null: absent
+        int w = 0, lag = 0;                       // floats of a (t, b) row of that array
+        if (f < kFE) { q = a.X + (size_t)(b * DX + f - kFX) * N + n; w = DX * N; }
+        else if (f < kFFm) { q = a.eps + (size_t)(b * DX + f - kFE) * N + n; w = DX * N; }
+        else if (f < kFDf) { q = a.Fm + (size_t)(b * DX + f - kFFm) * N; w = DX * N; lag = 1; }
+        else if (f < kFLw) { if (ext_fm) { q = a.dFm_ext + (size_t)(b * DX + f - kFDf) * N + n; w = DX * N; } }
+        else if (f == kFLw) { q = a.logW + (size_t)b * N + n; w = N; }
+        else if (f == kFDlw) { if (ext_lw) { q = a.dlogW_ext + (size_t)b * N + n; w = N; } }
+        else if (f == kFAnc) { if (a.resample) { q = reinterpret_cast<const in_word_t*>(a.idx) + (size_t)b * N + n; w = N; lag = 2; } }
+        else if (f < kFY) { if (a.two_q) { q = a.mu2 + b * DX + f - kFM2; w = DX; } }
+        else if (f < kFLse) { q = a.obs + b * DY + f - kFY; w = DY; }
+        else if (f == kFLse) { q = a.lse + b; w = 1; }
+        else if (f == kFDlse) { if (a.dlse) { q = a.dlse + b; w = 1; } }
+        else if (f < kFields) { if (!a.bootstrap) { q = a.P1 + (size_t)(b * DX + f - kFP1) * N; w = DX * N; lag = 1; } }
+        if (q) {
+            ptr = q + (size_t)max(T - 1 - lag, 0) * B * w;
+            str = B * w;
+            lg = lag;
+        } else {                                  // re-reads one word that is always there (never used)
+            ptr = a.eps + (size_t)b * DX * N + n;
+            str = 0;
+            lg = 0;
+        }
+    };
 #pragma unroll
-        for (int d = 0; d < DX; ++d) {
-            sx[d] = a.X[(tb * DX + d) * N + n];
-            se[d] = a.eps[(tb * DX + d) * N + n];
-            sm2[d] = a.two_q ? a.mu2[tb * DX + d] : 0.f;
-            sfmean[d] = a.Fm[(tp * DX + d) * N + anc];
-            smean1[d] = a.bootstrap ? 0.f : a.P1[(tp * DX + d) * N + anc];
-            if (a.dFm_ext) {
-                if (one_part) {
-                    sdfm[d] = a.dFm_ext[(tb * DX + d) * N + n];
-                } else {
-                    float ext = 0.f;
-                    for (int q = 0; q < a.nparts; ++q) ext += a.dFm_ext[((tb * a.nparts + q) * DX + d) * N + n];
-                    sdfm[d] = ext;
-                }
-            } else {
-                sdfm[d] = 0.f;
+    for (int s = 0; s < kSlots; ++s) {
+        field_ptr(4 * s, in_ptr[s], in_str[s], in_lag[s]);
+#pragma unroll
+        for (int j = 1; j < 4; ++j) {
+            const in_word_t* q;
+            int st, lg;
+            field_ptr(4 * s + j, q, st, lg);
+            in_ptr[s] = (p == j) ? q : in_ptr[s];
+            in_str[s] = (p == j) ? st : in_str[s];
+            in_lag[s] = (p == j) ? lg : in_lag[s];
+        }
+    }
+    float raw_n[kSlots];
+#pragma unroll
+    for (int s = 0; s < kSlots; ++s) raw_n[s] = 0.f;
+    // issue-only prefetch (see filter_bwd_kernel): the loads of step t, whose particles have the ancestor `anc`
+    auto issue_step = [&](int t, int anc) {
+#pragma unroll
+        for (int s = 0; s < kSlots; ++s) {
+            if (s < nslots) {
+                if (slot_gathers(s)) raw_n[s] = in_ptr[s][in_lag[s] == 1 ? anc : 0];
+                else raw_n[s] = *in_ptr[s];
+                if (slot_lags(s)) in_ptr[s] -= (t > in_lag[s]) ? in_str[s] : 0;
+                else in_ptr[s] -= in_str[s];
             }
         }
+    };
+    // upstream gradients in several parts: every lane sums its particle's parts (issued with the prefetch, as before)
+    auto issue_parts = [&](int t, float (&sdfm)[DX], float& sdlw) {
+        const size_t tb = (size_t)t * B + b;
+        if (a.dFm_ext && !one_part) {
 #pragma unroll
-        for (int k = 0; k < DY; ++k) sy[k] = a.obs[tb * DY + k];
-        ssc[0] = a.logW[tb * N + n];
-        ssc[1] = a.lse[tb];
-        ssc[2] = a.dlse ? a.dlse[tb] : 0.f;
-        if (a.dlogW_ext) {
-            if (one_part) {
-                ssc[3] = a.dlogW_ext[tb * N + n];
-            } else {
+            for (int d = 0; d < DX; ++d) {
                 float ext = 0.f;
-                for (int q = 0; q < a.nparts; ++q) ext += a.dlogW_ext[(tb * a.nparts + q) * N + n];
-                ssc[3] = ext;
+                for (int q = 0; q < a.nparts; ++q) ext += a.dFm_ext[((tb * a.nparts + q) * DX + d) * N + n];
+                sdfm[d] = ext;
             }
-        } else {
-            ssc[3] = 0.f;
+        }
+        if (a.dlogW_ext && !one_part) {
+            float ext = 0.f;
+            for (int q = 0; q < a.nparts; ++q) ext += a.dlogW_ext[(tb * a.nparts + q) * N + n];
+            sdlw = ext;
         }
     };
     float c_x[DX], c_e[DX], c_m2[DX], c_y[DY], c_mean1[DX], c_fmean[DX], c_dfm[DX], c_sc[4];
-    int c_anc = load_anc(T - 1);
-    int anc_next = load_anc(T - 2);
-    load_step(T - 1, c_anc, c_x, c_e, c_m2, c_y, c_mean1, c_fmean, c_dfm, c_sc);
+    int c_anc = load_anc(T - 1), anc_next = n;
+    // quad broadcast of the fields loaded for step t (all 64 lanes active); `pdfm` / `pdlw`: the sums of issue_parts
+    auto take_step = [&](int t, const float (&pdfm)[DX], float pdlw) {
+#pragma unroll
+        for (int d = 0; d < DX; ++d) {
+            c_x[d] = quad_field(raw_n, kFX + d);
+            c_e[d] = quad_field(raw_n, kFE + d);
+            const float m2 = quad_field(raw_n, kFM2 + d), p1 = quad_field(raw_n, kFP1 + d), df = quad_field(raw_n, kFDf + d);
+            c_m2[d] = a.two_q ? m2 : 0.f;
+            c_fmean[d] = quad_field(raw_n, kFFm + d);
+            c_mean1[d] = a.bootstrap ? 0.f : p1;
+            c_dfm[d] = a.dFm_ext ? (one_part ? df : pdfm[d]) : 0.f;
+        }
+#pragma unroll
+        for (int k = 0; k < DY; ++k) c_y[k] = quad_field(raw_n, kFY + k);
+        const float dlse = quad_field(raw_n, kFDlse), dlw = quad_field(raw_n, kFDlw);
+        const int an = __builtin_bit_cast(int, quad_field(raw_n, kFAnc));
+        c_sc[0] = quad_field(raw_n, kFLw);
+        c_sc[1] = quad_field(raw_n, kFLse);
+        c_sc[2] = a.dlse ? dlse : 0.f;
+        c_sc[3] = a.dlogW_ext ? (one_part ? dlw : pdlw) : 0.f;
+        anc_next = (a.resample && t >= 2) ? an : n;     // ancestor of step t - 1
+    };
+    {
+        float pdfm[DX], pdlw = 0.f;
+#pragma unroll
+        for (int d = 0; d < DX; ++d) pdfm[d] = 0.f;
+        issue_step(T - 1, c_anc);
+        issue_parts(T - 1, pdfm, pdlw);
+        take_step(T - 1, pdfm, pdlw);
+    }
     __syncthreads();
 
     SEC_INIT(filter_bwd)
@@ -605,12 +684,13 @@ __global__ void __launch_bounds__(512) filter_bwd_lpp_kernel(const FilterBwdArgs
         float* curF = accF + (t & 1) * nw * CP;
         float* nxtF = accF + ((t + 1) & 1) * nw * CP + wave * CP;
 
-        float n_x[DX], n_e[DX], n_m2[DX], n_y[DY], n_mean1[DX], n_fmean[DX], n_dfm[DX], n_sc[4];
-        int n_anc = n;
+        float n_dfm[DX], n_dlw = 0.f;
+#pragma unroll
+        for (int d = 0; d < DX; ++d) n_dfm[d] = 0.f;
+        const int n_anc = anc_next;
         if (t >= 1) {
-            n_anc = anc_next;
-            load_step(t - 1, n_anc, n_x, n_e, n_m2, n_y, n_mean1, n_fmean, n_dfm, n_sc);
-            anc_next = load_anc(t - 2);
+            issue_step(t - 1, n_anc);
+            issue_parts(t - 1, n_dfm, n_dlw);
         }
         SEC(1);   // (lpp) issue of the prefetch loads
         // the scatter targets of this step (complete since the barrier that ended step t + 1) are requested HERE, a whole
@@ -794,15 +874,7 @@ __global__ void __launch_bounds__(512) filter_bwd_lpp_kernel(const FilterBwdArgs
         SEC(7);   // (lpp) LDS scatter-add into the parents
         if (t >= 1) {
             c_anc = n_anc;
-#pragma unroll
-            for (int d = 0; d < DX; ++d) {
-                c_x[d] = n_x[d]; c_e[d] = n_e[d]; c_m2[d] = n_m2[d];
-                c_mean1[d] = n_mean1[d]; c_fmean[d] = n_fmean[d]; c_dfm[d] = n_dfm[d];
-            }
-#pragma unroll
-            for (int k = 0; k < DY; ++k) c_y[k] = n_y[k];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) c_sc[k] = n_sc[k];
+            take_step(t - 1, n_dfm, n_dlw);
         }
 #pragma unroll
         for (int i = 0; i < AC::kSet; ++i) {

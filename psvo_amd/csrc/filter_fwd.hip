@@ -365,23 +365,73 @@ __global__ void __launch_bounds__(MAXT) filter_fwd_lpp_kernel(const FilterArgs a
     }
     float lnw = neg_logN;
 
-    float eps_c[DX], mu2_c[DX], obs_c[DY], u_c = 0.f;
-    int idx_c = 0;
-    auto load_inputs = [&](int t, float (&e)[DX], float (&m)[DX], float (&o)[DY], float& uu, int& ii) {
-        const size_t tb = (size_t)t * B + b;
-#pragma unroll
-        for (int d = 0; d < DX; ++d) {
-            e[d] = a.eps[(tb * DX + d) * N + n];
-            m[d] = a.two_q ? a.mu2[tb * DX + d] : 0.f;
-        }
-#pragma unroll
-        for (int k = 0; k < DY; ++k) o[k] = a.obs[tb * DY + k];
-        if (a.resample) {
-            if (a.idx_in) ii = a.idx_in[tb * N + n];
-            else uu = a.u[tb * N + n];
+    // Per-step inputs: the quad fetches each of them ONCE.  The scalar inputs of a particle and of its sequence form one
+    // field list -- eps[DX] | u (or the teacher-forced index) | mu2[DX] | obs[DY] -- and lane p of the quad loads fields
+    // p, p + 4, ..: kSlots loads per lane and step instead of one per field.  Every array is (T, B, ., N)-major, so a
+    // slot's pointer advances by a constant per step; pointer and stride are set up here, once.  The loaded words stay
+    // raw until the register rotation that ends the step, which hands them to the quad (quad_field: one v_mov_dpp each).
+    constexpr int kFU = DX, kFM2 = DX + 1, kFY = 2 * DX + 1, kFields = 2 * DX + 1 + DY, kSlots = (kFields + 3) / 4;
+    const in_word_t* in_ptr[kSlots];
+    int in_str[kSlots];                           // floats per time step
+    // (the field of a lane is picked by selects over the slot's four candidates, each a compile-time field: an if / else chain
+    //  on the lane's own field number would be a divergent branch per field)
+    auto field_ptr = [&](int f, const in_word_t*& q, int& st) {
+        q = a.eps + (size_t)b * DX * N + n;       // a field that is absent re-reads this word (never used)
+        st = 0;
+        if (f < kFU) {
+            q = a.eps + ((size_t)b * DX + f) * N + n;
+            st = B * DX * N;
+        } else if (f == kFU) {
+            if (a.resample) {
+                q = (a.idx_in ? reinterpret_cast<const in_word_t*>(a.idx_in) : static_cast<const in_word_t*>(a.u)) + (size_t)b * N + n;
+                st = B * N;
+            }
+        } else if (f < kFY) {
+            if (a.two_q) {
+                q = a.mu2 + (size_t)b * DX + (f - kFM2);
+                st = B * DX;
+            }
+        } else if (f < kFields) {
+            q = a.obs + (size_t)b * DY + (f - kFY);
+            st = B * DY;
         }
     };
-    load_inputs(0, eps_c, mu2_c, obs_c, u_c, idx_c);
+#pragma unroll
+    for (int s = 0; s < kSlots; ++s) {
+        field_ptr(4 * s, in_ptr[s], in_str[s]);
+#pragma unroll
+        for (int j = 1; j < 4; ++j) {
+            const in_word_t* q;
+            int st;
+            field_ptr(4 * s + j, q, st);
+            in_ptr[s] = (p == j) ? q : in_ptr[s];
+            in_str[s] = (p == j) ? st : in_str[s];
+        }
+    }
+    float eps_c[DX], mu2_c[DX], obs_c[DY], u_c = 0.f;
+    int idx_c = 0;
+    float raw_n[kSlots];
+    auto issue_inputs = [&]() {    // issues the loads of the slots' next time step, nothing else
+#pragma unroll
+        for (int s = 0; s < kSlots; ++s) {
+            raw_n[s] = *in_ptr[s];
+            in_ptr[s] += in_str[s];
+        }
+    };
+    auto take_inputs = [&]() {     // quad broadcast of the loaded fields (all 64 lanes active)
+#pragma unroll
+        for (int d = 0; d < DX; ++d) {
+            eps_c[d] = quad_field(raw_n, d);
+            const float m = quad_field(raw_n, kFM2 + d);
+            mu2_c[d] = a.two_q ? m : 0.f;
+        }
+#pragma unroll
+        for (int k = 0; k < DY; ++k) obs_c[k] = quad_field(raw_n, kFY + k);
+        u_c = quad_field(raw_n, kFU);
+        idx_c = __builtin_bit_cast(int, u_c);
+    };
+    issue_inputs();
+    take_inputs();
     __syncthreads();  // weights visible
 
     SEC_INIT(filter_fwd)
@@ -391,9 +441,7 @@ __global__ void __launch_bounds__(MAXT) filter_fwd_lpp_kernel(const FilterArgs a
         SEC(0);   // (lpp) loop overhead
         const size_t tb = (size_t)t * B + b;
         const StepK<DX> K = decltype(first_tag)::value ? K0 : K1;
-        float eps_n[DX], mu2_n[DX], obs_n[DY], u_n = 0.f;
-        int idx_n = 0;
-        if (t + 1 < T) load_inputs(t + 1, eps_n, mu2_n, obs_n, u_n, idx_n);
+        if (t + 1 < T) issue_inputs();
 
         SEC(1);   // (lpp) issue of the prefetch loads
         // ---- proposal (SVO.py:186-197), densities: the same in the four lanes of the particle --------
@@ -543,15 +591,7 @@ __global__ void __launch_bounds__(MAXT) filter_fwd_lpp_kernel(const FilterArgs a
             __syncthreads();  // red[] reuse
         }
 
-#pragma unroll
-        for (int d = 0; d < DX; ++d) {
-            eps_c[d] = eps_n[d];
-            mu2_c[d] = mu2_n[d];
-        }
-#pragma unroll
-        for (int k = 0; k < DY; ++k) obs_c[k] = obs_n[k];
-        u_c = u_n;
-        idx_c = idx_n;
+        take_inputs();   // (waits for the prefetch)
     };
     step(std::true_type{}, 0);
     for (int t = 1; t < T; ++t) step(std::false_type{}, t);
