@@ -257,6 +257,39 @@ int psvo_ffbs_smooth(const psvo_desc* desc,
                      float* logWs, float* Xmean, float* ess, float* Xs, int32_t* idx_out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Backward-sampled trajectories (forward filtering, backward simulation: FFBSi) on the particle system a forward filter left
+ * in HBM: N whole paths per sequence, where psvo_ffbs_smooth draws every step on its own from the smoothed marginals.  Added
+ * within ABI 6: purely additive.  Notation of psvo_ffbs_smooth (a_t, l_t, s_t); per sequence b and trajectory n = 0..N-1:
+ *     t = T-1 :  v[n,k] = a_{T-1}[k]
+ *     t < T-1 :  v[n,k] = a_t[k] + l_t(X[t+1,b,:,j_{t+1}(n)]; k)
+ *     j_t(n)      = #{k : cdf_n[k] <= u[t,b,n] total_n}, clamped to N-1    (the filter's draw; cdf_n = inclusive prefix sums in
+ *                   k order of exp(v[n,k] - shift_n), total_n their sum)
+ *     logq[t,b,n] = v[n,j_t(n)] - logsumexp_k v[n,:]
+ *     Xs[t,b,:,n] = X[t,b,:,j_t(n)]
+ *     distinct[t,b] = number of different values among j_t(0..N-1)
+ * sum_t logq[t,b,n] is the log-probability of path n under the sampler; distinct is the path-degeneracy diagnostic (the
+ * counterpart of the smoother's ess).  The kernel shifts by the log-sum-exp itself, so its weights are normalised and
+ * total_n = 1 to the rounding of one fp32 number; where cdf_n ends below u the draw is clamped to the LAST PARTICLE WITH
+ * logW > -inf.  A particle of weight zero (logW = -inf) is never drawn.
+ *
+ * One persistent workgroup per sequence walks t downwards, a lane per trajectory; the N x N tile is recomputed in both pair
+ * phases of a step and never stored; no MLP is evaluated.  No atomics and every sum in a fixed order: two calls on the same
+ * inputs give bit-identical outputs, with or without PSVO_TUNE_DETERMINISTIC.  No gradient.
+ *
+ *  desc            B, T, N, Dx are read; nothing else is looked at.  Dx in {2,3,4}, N <= 512 (else PSVO_ERR_UNSUPPORTED);
+ *                  T = 1 is valid (N draws from the normalised filter weights)
+ *  X, Fm, Fs, sig_f, logW   as for psvo_ffbs_smooth; exactly one of Fs / sig_f (else PSVO_ERR_INVALID)
+ *  u (T,B,N)       uniforms in [0,1), one per trajectory and step, or NULL
+ *  idx_in (T,B,N)  teacher-forced indices (values clamped to [0, N)), or NULL; at least one of u / idx_in (else
+ *                  PSVO_ERR_INVALID), idx_in wins.  logq, Xs and distinct are produced for the forced indices
+ *  outputs: Xs (T,B,Dx,N), idx_out (T,B,N), logq (T,B,N), distinct (T,B); each may be NULL, not all (else PSVO_ERR_INVALID).
+ * ------------------------------------------------------------------------------------------- */
+int psvo_ffbs_sample(const psvo_desc* desc,
+                     const float* X, const float* Fm, const float* Fs, const float* sig_f, const float* logW,
+                     const float* u, const int32_t* idx_in,
+                     float* Xs, int32_t* idx_out, float* logq, int32_t* distinct, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Backward simulation with proposal, STATE-DEPENDENT diagonal scales (FLAGS.output_cov and FLAGS.diag_cov; see
  * psvo_filter_forward_cov).  Same loop and outputs as psvo_bsim_forward (PSVO.backward_simulation_w_proposal, reference
  * src/SMC/PSVO.py:69-203); differences:

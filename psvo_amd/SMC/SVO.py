@@ -40,6 +40,8 @@ class SVO:
         self.resample_particles = True
         # marginal particle smoother behind the filter at evaluation time (FLAGS.FFBS; psvo_ffbs_smooth)
         self.FFBS = bool(getattr(FLAGS, "FFBS", False))
+        # backward-sampled trajectories behind the filter at evaluation time (FLAGS.FFBSi; psvo_ffbs_sample)
+        self.FFBSi = bool(getattr(FLAGS, "FFBSi", False))
 
         self.name = name
         self.generator = None        # torch.Generator on the compute device; None = global RNG
@@ -80,6 +82,13 @@ class SVO:
         log["Xs_filter"]), and log["X_smooth_mean"] (B,T,Dx), log["ess_smooth"] (B,T), log["logW_smooth"] (T,B,N) and
         log["smoother"] (the kernel's output dict in its own layout, with the drawn indices) are added.
         Under autograd nothing changes: the smoother has no gradient and is not launched.
+
+        With FLAGS.FFBSi, under the same condition, N trajectories are backward-sampled from the filter's particle system
+        (noise: u_p (T,B,N) or idx_p (T,B,N) int32): log["Xs"] then holds whole paths, log["Xs"][b, :, n, :] one draw from the
+        joint smoothing distribution, as PSVO returns them; log["Xs_filter"] keeps the filtered cloud, log["path_logq"] (T,B,N)
+        is the log-probability of every pick given the path's successor, log["path_distinct"] (B,T) the number of different
+        particles the N paths pass through, log["paths"] the kernel's output dict.  With FLAGS.FFBS as well both kernels run
+        and the smoother's per-step draws move to log["Xs_marginal"].
         """
         batch_size, time, _ = obs.shape
         self.Dx, self.batch_size, self.time = self.model.Dx, batch_size, time
@@ -94,16 +103,23 @@ class SVO:
         log["filter"] = filt
         if self.FFBS and not torch.is_grad_enabled():
             self._smooth(filt, log, noise or {})
+        if self.FFBSi and not torch.is_grad_enabled():
+            self._sample_paths(filt, log, noise or {})
         self._release()
         return log_ZSMC, log
+
+    def _transition_scale(self, filt):
+        """the constant scale the filter weighted the transition with (sigma_q1 when f shares q1's network, else sigma_f), or
+        None under output_cov, where the filter left a scale per particle in filt["Fs"]"""
+        if filt.get("Fs") is not None:
+            return None
+        return _c(self._sigma(self.q1 if self.model.use_bootstrap else self.f))
 
     def _smooth(self, filt, log, noise):
         """forward filtering, backward smoothing on the particle system `filt` (psvo_ffbs_smooth): the transition scale is the
         one the filter weighted with -- per particle under output_cov, else sigma_q1 when f shares q1's network, else sigma_f"""
         T, B, N = self.time, self.batch_size, self.n_particles
-        sig_f = None
-        if filt.get("Fs") is None:
-            sig_f = _c(self._sigma(self.q1 if self.model.use_bootstrap else self.f))
+        sig_f = self._transition_scale(filt)
         u, idx_in = noise.get("u_s"), noise.get("idx_s")
         if u is None and idx_in is None:
             u = self._rand(T, B, N, device=filt["X"].device)
@@ -114,6 +130,22 @@ class SVO:
         log["ess_smooth"] = sm["ess"].transpose(0, 1)
         log["logW_smooth"] = sm["logWs"]
         log["smoother"] = sm
+
+    def _sample_paths(self, filt, log, noise):
+        """forward filtering, backward simulation on the particle system `filt` (psvo_ffbs_sample), with the scale of _smooth"""
+        T, B, N = self.time, self.batch_size, self.n_particles
+        u, idx_in = noise.get("u_p"), noise.get("idx_p")
+        if u is None and idx_in is None:
+            u = self._rand(T, B, N, device=filt["X"].device)
+        paths = ops.ffbs_sample(self._desc(), filt, sig_f=self._transition_scale(filt), u=u, idx_in=idx_in)
+        if "Xs_filter" in log:                                          # (FLAGS.FFBS too: log["Xs"] holds the smoother's draws)
+            log["Xs_marginal"] = log["Xs"]
+        else:
+            log["Xs_filter"] = log["Xs"]
+        log["Xs"] = paths["Xs"].permute(1, 0, 3, 2)                     # (T, B, Dx, N) -> (batch_size, time, n_particles, Dx)
+        log["path_logq"] = paths["logq"]
+        log["path_distinct"] = paths["distinct"].transpose(0, 1)
+        log["paths"] = paths
 
     def _release(self):
         """drop what one evaluation cached on the object (scale vectors, hoisted means, features, stream context).

@@ -14,6 +14,7 @@
 // however sharp the transitions are.  No atomics; every sum is a per-lane loop, a wave scan or a fold over the <= 8 waves in
 // wave order: the output is the same bit for bit on every run.
 #include "common.h"
+#include "ffbs_pair.h"
 
 namespace psvo {
 
@@ -24,96 +25,6 @@ struct FfbsArgs {
     float *logWs, *Xmean, *ess, *Xs;
     int32_t* idx_out;
 };
-
-// floats per staged row: float4 reads for Dx = 3 as for Dx = 4
-constexpr int ffbs_dxp(int DX) { return DX == 3 ? 4 : DX; }
-
-template <int DX>
-__device__ __forceinline__ void lds_row_store(float* __restrict__ p, const float (&v)[DX]) {
-    if constexpr (DX == 2) *reinterpret_cast<float2*>(p) = float2{v[0], v[1]};
-    else *reinterpret_cast<float4*>(p) = float4{v[0], v[1], v[2], DX == 4 ? v[DX - 1] : 0.f};
-}
-
-// a staged row as packed pairs: (d0, d1) [, (d2, d3)]; Dx = 3 carries a zero in the last slot (own and scale zero there too)
-template <int DX>
-__device__ __forceinline__ void lds_row_load2(const float* __restrict__ p, f2 (&v)[(DX + 1) / 2]) {
-    if constexpr (DX == 2) {
-        const float2 q = *reinterpret_cast<const float2*>(p);
-        v[0] = f2{q.x, q.y};
-    } else {
-        const float4 q = *reinterpret_cast<const float4*>(p);
-        v[0] = f2{q.x, q.y};
-        v[1] = f2{q.z, q.w};
-    }
-}
-template <int DX>
-__device__ __forceinline__ void pack_row(const float (&x)[DX], f2 (&v)[(DX + 1) / 2]) {
-    v[0] = f2{x[0], x[1]};
-    if constexpr (DX == 3) v[1] = f2{x[2], 0.f};
-    if constexpr (DX == 4) v[1] = f2{x[2], x[3]};
-}
-
-// four staged rows of a pair phase in registers
-template <int DX, bool ROWSCALE>
-struct Rows4 {
-    static constexpr int NP = (DX + 1) / 2;
-    float v[4];
-    f2 p[4][NP], rr[4][NP];
-    __device__ __forceinline__ void load(const float* __restrict__ sv, const float* __restrict__ sp,
-                                         const float* __restrict__ sr, int i0) {
-        const float4 a4 = *reinterpret_cast<const float4*>(sv + i0);
-        v[0] = a4.x; v[1] = a4.y; v[2] = a4.z; v[3] = a4.w;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            lds_row_load2<DX>(sp + (i0 + i) * ffbs_dxp(DX), p[i]);
-            if constexpr (ROWSCALE) lds_row_load2<DX>(sr + (i0 + i) * ffbs_dxp(DX), rr[i]);
-        }
-    }
-};
-
-// log2 sum_i exp2(sv[i] - sum_d ((sp[i][d] - own[d]) rr[d])^2) over the n8 staged rows (n8 a multiple of 8; padding rows carry
-// sv = -inf), rr = the row's own scale factors sr[i][.] (ROWSCALE) or the lane's r[.].  Rows are read at wave-uniform addresses
-// (LDS broadcasts), four at a time and one group AHEAD of the arithmetic: with one or two waves per SIMD nothing else hides
-// the LDS latency (measured: without the read-ahead the loop ran at the sum of latency and arithmetic per group).  The squares
-// run on packed f32 pairs (two dimensions per instruction); the max-shifted sum is kept online, rescaled once per four rows,
-// in TWO accumulators (even and odd groups of four) that are merged at the end -- a fixed order.  -inf when every term is.
-template <int DX, bool ROWSCALE>
-__device__ __forceinline__ float pair_lse(const float* __restrict__ sv, const float* __restrict__ sp,
-                                          const float* __restrict__ sr, const f2 (&own)[(DX + 1) / 2],
-                                          const f2 (&r)[(DX + 1) / 2], int n8) {
-    constexpr int NP = (DX + 1) / 2;
-    const float ninf = -__builtin_huge_valf();
-    float m[2] = {ninf, ninf}, s[2] = {0.f, 0.f};
-    auto fold = [&](const Rows4<DX, ROWSCALE>& R, int h) {
-        float v[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            f2 acc = f2{0.f, 0.f};
-#pragma unroll
-            for (int q = 0; q < NP; ++q) {
-                const f2 z = (R.p[i][q] - own[q]) * (ROWSCALE ? R.rr[i][q] : r[q]);
-                acc = pk_fma(z, z, acc);
-            }
-            v[i] = R.v[i] - (acc.x + acc.y);
-        }
-        const float mn = fmaxf(fmaxf(m[h], fmaxf(v[0], v[1])), fmaxf(v[2], v[3]));
-        const float mb = (mn == ninf) ? 0.f : mn;
-        s[h] = fmaf(s[h], exp2_fast(m[h] - mb),
-                    (exp2_fast(v[0] - mb) + exp2_fast(v[1] - mb)) + (exp2_fast(v[2] - mb) + exp2_fast(v[3] - mb)));
-        m[h] = mn;
-    };
-    Rows4<DX, ROWSCALE> even, odd;
-    even.load(sv, sp, sr, 0);
-    for (int i0 = 0; i0 < n8; i0 += 8) {
-        odd.load(sv, sp, sr, i0 + 4);
-        fold(even, 0);
-        even.load(sv, sp, sr, i0 + 8 < n8 ? i0 + 8 : 0);      // (the last read-ahead wraps to group 0 and is not used)
-        fold(odd, 1);
-    }
-    const float mn = fmaxf(m[0], m[1]);
-    const float mb = (mn == ninf) ? 0.f : mn;
-    return mn + log2_fast(fmaf(s[0], exp2_fast(m[0] - mb), s[1] * exp2_fast(m[1] - mb)));
-}
 
 template <int DX, int COV, int MAXT>
 __global__ void __launch_bounds__(MAXT) ffbs_kernel(const FfbsArgs a) {

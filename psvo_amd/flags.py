@@ -73,6 +73,9 @@ DEFINITIONS = [
     # marginal particle smoother for the filter objectives (not in the reference's registry; its sweep script carries FFBS and
     # FFBS_to_learn, auto_sh.py:94-97, for not_used/SMC_supreme/SMC.py:451-482): off by default, evaluation only
     ("FFBS", bool, False, "SVO / AESMC / IWAE: evaluate with forward-filtering backward-smoothing weights and particles"),
+    # backward-sampled trajectories for the filter objectives (not in the reference's registry: its PSVO samples paths, its
+    # filters do not): off by default, evaluation only
+    ("FFBSi", bool, False, "SVO / AESMC / IWAE: return N backward-sampled trajectories per sequence (backward simulation)"),
     # printing and data saving (runner_flag.py:131-153)
     ("print_freq", int, 1, "frequency to evaluate testing loss & other metrics and save results"),
     ("save_trajectory", bool, True, "whether to save hidden trajectories during training"),

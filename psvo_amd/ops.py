@@ -655,6 +655,35 @@ def ffbs_smooth(desc, filt, sig_f=None, u=None, idx_in=None, want_draws=True):
     return out
 
 
+def ffbs_sample(desc, filt, sig_f=None, u=None, idx_in=None):
+    """psvo_ffbs_sample: N backward-sampled trajectories per sequence (FFBSi) on a forward filter's outputs.  `filt` and `sig_f`
+    as for ffbs_smooth -- exactly one of filt["Fs"] / sig_f.  `u` (T,B,N) uniforms, one per trajectory and step, or `idx_in`
+    (T,B,N) int32 teacher-forced indices; at least one, idx_in wins.  Returns dict(Xs (T,B,Dx,N) the paths, idx (T,B,N) int32
+    their particle indices, logq (T,B,N) the log-probability of each pick given the path's successor, distinct (T,B) int32 the
+    number of different particles the N paths pass through).  Asynchronous on the launch stream."""
+    lib = _lib.load()
+    B, T, N, Dx = desc.B, desc.T, desc.N, desc.Dx
+    X, Fm, Fs, logW = filt["X"], filt["Fm"], filt.get("Fs"), filt["logW"]
+    if X is None or Fm is None or logW is None:
+        raise ValueError("ffbs_sample needs the filter's X, Fm and logW")
+    _chk(X, (T, B, Dx, N), "X"); _chk(Fm, (T, B, Dx, N), "Fm"); _chk(Fs, (T, B, Dx, N), "Fs"); _chk(logW, (T, B, N), "logW")
+    _chk(sig_f, (Dx,), "sig_f")
+    if (Fs is None) == (sig_f is None):
+        raise ValueError("ffbs_sample takes exactly one transition scale: the filter's per-particle `Fs` or a constant `sig_f`")
+    _chk(u, (T, B, N), "u"); _chk(idx_in, (T, B, N), "idx_in", torch.int32)
+    if u is None and idx_in is None:
+        raise ValueError("backward sampling needs uniforms `u` or teacher-forced `idx_in`")
+    dev = X.device
+    out = {"Xs": _empty(T, B, Dx, N, device=dev), "idx": _empty(T, B, N, device=dev, dtype=torch.int32),
+           "logq": _empty(T, B, N, device=dev), "distinct": _empty(T, B, device=dev, dtype=torch.int32)}
+    _mark("psvo_ffbs_sample", 0)
+    st = lib.psvo_ffbs_sample(ctypes.byref(desc), _ptr(X), _ptr(Fm), _ptr(Fs), _ptr(sig_f), _ptr(logW), _ptr(u), _ptr(idx_in),
+                              _ptr(out["Xs"]), _ptr(out["idx"]), _ptr(out["logq"]), _ptr(out["distinct"]), _stream())
+    _mark("psvo_ffbs_sample", 1)
+    _lib.check(st, "psvo_ffbs_sample")
+    return out
+
+
 def filter_backward_cov(desc, q1, f, g, sigc_q1, sigc_f, sigc_g, mu2, sig2, m0, sig0, fm0, fsig0, obs, eps, filt,
                         dlse=None, dFm=None, dFs=None, dlogW=None):
     """psvo_filter_backward_cov + two psvo_mlp_wgrad launches per MLP (one per head; both contribute to dW1 / db1).

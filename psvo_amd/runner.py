@@ -70,6 +70,9 @@ def main(FLAGS):
     if getattr(FLAGS, "FFBS", False) and (FLAGS.PSVO or FLAGS.PSVOwR):
         raise ValueError("--FFBS smooths the particle system of a filter objective (SVO, AESMC, IWAE); PSVO and PSVOwR "
                          "already return backward-simulation trajectories")
+    if getattr(FLAGS, "FFBSi", False) and (FLAGS.PSVO or FLAGS.PSVOwR):
+        raise ValueError("--FFBSi samples trajectories from the particle system of a filter objective (SVO, AESMC, IWAE); PSVO "
+                         "and PSVOwR already return backward-simulation trajectories")
     if FLAGS.use_2_q:
         FLAGS.q_uses_true_X = False
     device = _device()

@@ -20,6 +20,11 @@ Marginal smoother (FLAGS.FFBS, off by default; SVO / AESMC / IWAE): every evalua
 (psvo_amd.SMC.SVO), so "Xs", the k-step predictions and the saved trajectories come from the smoothed particles; the mean and the
 minimum of the smoothed weights' effective sample size over each split are printed and go into metric_<iter>.p as
 ffbs_ess_mean_<split> / ffbs_ess_min_<split>.  Training steps are untouched.
+
+Backward-sampled trajectories (FLAGS.FFBSi, off by default; SVO / AESMC / IWAE): every evaluation then runs psvo_ffbs_sample
+behind the filter, so "Xs", the k-step predictions and the saved trajectories are whole paths, as under PSVO; the mean and the
+minimum over each split of the number of distinct particles the N paths pass through are printed and go into metric_<iter>.p
+as ffbsi_distinct_mean_<split> / ffbsi_distinct_min_<split>.  Training steps are untouched.
 """
 import math
 import os
@@ -257,12 +262,15 @@ class trainer:
         """ELBO and k-step R-square on the training and held-out sets; appended to the histories and pickled as
         metric_<iter>.p with the reference's keys (trainer.py:201-241).  A non-finite training ELBO stops training."""
         ffbs = bool(getattr(self.SMC, "FFBS", False))
-        fetches = ["log_ZSMC", "y_hat", "y"] + (["ess_smooth"] if ffbs else [])
+        ffbsi = bool(getattr(self.SMC, "FFBSi", False))
+        fetches = ["log_ZSMC", "y_hat", "y"] + (["ess_smooth"] if ffbs else []) + (["path_distinct"] if ffbsi else [])
         m, ess = {}, {}
         for split, obs, hid in (("train", self.obs_train, self.hidden_train), ("test", self.obs_test, self.hidden_test)):
             elbos, y_hat, y, *rest = self.evaluate(fetches, {self.obs: obs, self.hidden: hid})
             if ffbs:
                 ess["ffbs_ess_mean_" + split], ess["ffbs_ess_min_" + split] = float(np.mean(rest[0])), float(np.min(rest[0]))
+            if ffbsi:
+                ess["ffbsi_distinct_mean_" + split], ess["ffbsi_distinct_min_" + split] = float(np.mean(rest[-1])), float(np.min(rest[-1]))
             m["log_ZSMC_" + split] = np.mean(elbos)
             m["R_square_" + split] = self.evaluate_R_square(y_hat, y)
 
@@ -275,6 +283,10 @@ class trainer:
                 print("FFBS effective sample size (of {} particles), mean / min: train {:.2f} / {:.2f}, valid {:.2f} / {:.2f}"
                       .format(self.n_particles, ess["ffbs_ess_mean_train"], ess["ffbs_ess_min_train"],
                               ess["ffbs_ess_mean_test"], ess["ffbs_ess_min_test"]))
+            if ffbsi:
+                print("FFBSi distinct particles per step (of {}), mean / min: train {:.2f} / {:.0f}, valid {:.2f} / {:.0f}"
+                      .format(self.n_particles, ess["ffbsi_distinct_mean_train"], ess["ffbsi_distinct_min_train"],
+                              ess["ffbsi_distinct_mean_test"], ess["ffbsi_distinct_min_test"]))
 
         if not math.isfinite(m["log_ZSMC_train"]):
             print("Nan in log_ZSMC, stop training")
@@ -360,6 +372,8 @@ class trainer:
                     out["y"] = [v.cpu().numpy() for v in y]
             if "ess_smooth" in names:
                 out["ess_smooth"] = log["ess_smooth"].contiguous().cpu().numpy()      # (B, T); FLAGS.FFBS only
+            if "path_distinct" in names:
+                out["path_distinct"] = log["path_distinct"].contiguous().cpu().numpy()      # (B, T) int32; FLAGS.FFBSi only
         return [out[n] for n in names]
 
     def evaluate(self, fetches, feed_dict_w_batches={}, average=False, keepdims=False):
