@@ -16,9 +16,10 @@
 //     are reduced over the four lane groups once per step by two swap-add stages (v_permlane32_swap / v_permlane16_swap:
 //     one swap + one add per pair of values, no selects); per-(chain, m) sums  U = sum_j p u,  V = sum_j p u^2  are
 //     all-reduced over the 16 lanes of the row with four DPP row rotations.
-// Addressing: every array is read / written as base (SGPR pair) + one 32-bit byte offset per array SHAPE kept in a VGPR and
-// advanced by a constant per step, and the float loop constants live in VGPRs (common.h keep_in_vgpr): no index arithmetic
-// in the loop, no scalar-register spills.  Arrays are therefore limited to 4 GiB each (the dispatcher falls back to v1).
+// Addressing: every array is read / written (global address space: gptr below) as base (SGPR pair) + one 32-bit byte offset
+// per array SHAPE kept in a VGPR and advanced by a constant per step, and the float loop constants live in VGPRs (common.h
+// keep_in_vgpr): no index arithmetic in the loop, no scalar-register spills.  Arrays are therefore limited to 4 GiB each (the
+// dispatcher falls back to v1).
 //
 // MFMA variant of the per-j sums (template flag JM, measured beside the VALU form):
 //   d[F'|W^]_j = sum_k c_kj [x'_k | 1]  is  C^T [X' | 1]  with k = (item, m) -- v_mfma_f32_16x16x4_f32 takes the lane's
@@ -32,16 +33,28 @@
 namespace psvo {
 PSVO_TIMERS_DEFINE(bsim_bwd2)
 
-// base + 32-bit byte offset: hipcc selects the saddr form (global_load_dword v, v_off, s[base:base+1])
-__device__ __forceinline__ float ldf(const float* base, unsigned off) {
-    return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + off);
+// Every array of the kernel is reached through a GLOBAL-address-space pointer (gptr): base (SGPR pair) + 32-bit byte offset
+// then compiles to the saddr form (global_load_dword v, v_off, s[base:base+1]).  A pointer that arg_block (common.h) hands
+// out as an integer is a generic pointer to hipcc, and a dereference of it is a FLAT access: it builds a 64-bit address on
+// the VALU and counts on lgkmcnt as well as vmcnt, so that every LDS wait behind a prefetch (s_waitcnt lgkmcnt(0)) waited
+// for the prefetched words too.  No access of this unit may go through a plain pointer.
+template <class T>
+using gptr = T __attribute__((address_space(1)))*;
+template <class T>
+__device__ __forceinline__ gptr<T> as_global(T* p) { return (gptr<T>)p; }
+template <class T>
+__device__ __forceinline__ gptr<T> as_global(unsigned long long p) { return (gptr<T>)p; }
+__device__ __forceinline__ float ldf(gptr<const float> base, unsigned off) {
+    return *reinterpret_cast<gptr<const float>>(reinterpret_cast<gptr<const char>>(base) + off);
 }
-__device__ __forceinline__ int ldi(const int32_t* base, unsigned off) {
-    return *reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(base) + off);
+__device__ __forceinline__ int ldi(gptr<const int32_t> base, unsigned off) {
+    return *reinterpret_cast<gptr<const int32_t>>(reinterpret_cast<gptr<const char>>(base) + off);
 }
-__device__ __forceinline__ void stf(float* base, unsigned off, float v) {
-    *reinterpret_cast<float*>(reinterpret_cast<char*>(base) + off) = v;
+__device__ __forceinline__ void stf(gptr<float> base, unsigned off, float v) {
+    *reinterpret_cast<gptr<float>>(reinterpret_cast<gptr<char>>(base) + off) = v;
 }
+// pointer argument re-read at its point of use (common.h: PSVO_ARG), as a global pointer
+#define PSVO_GARG(args_type, field) ::psvo::as_global(PSVO_ARG(args_type, field))
 
 // One reduce-scatter stage over lane bit 5 (bit 4): every lane passes in the value it KEEPS a sum of on the low side
 // (`lo`: lanes 0-31 / even rows) and on the high side (`hi`); returned is, on a low-side lane, lo(own) + lo(partner) and
@@ -242,7 +255,7 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
     }
     // (s_init, is_init, i_isig, im, mi are read in the first / last step only: scalar registers)
     const float ninf = -__builtin_huge_valf();
-    const float aw = valid ? a.dscore[(size_t)b * N + n] : 0.f;  // d loss / d score of this chain
+    const float aw = valid ? as_global(a.dscore)[(size_t)b * N + n] : 0.f;  // d loss / d score of this chain
 
     // ---- byte offsets of step 0, one per array shape, and their per-step strides -----------------------------------
     const unsigned NM = (unsigned)N * M;
@@ -306,7 +319,7 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
     static_assert(offsetof(BsimBwdArgs, logW) - offsetof(BsimBwdArgs, Fm) == 8 &&
                   offsetof(BsimBwdArgs, lse) - offsetof(BsimBwdArgs, Fm) == 16 && offsetof(BsimBwdArgs, Fm) % 32 == 0,
                   "BsimBwdArgs: forward-tile pointer block");
-    auto get_slot = [&](int tt, int j, float (&raw)[DX + 1], const float* Fm, const float* logW) {
+    auto get_slot = [&](int tt, int j, float (&raw)[DX + 1], gptr<const float> Fm, gptr<const float> logW) {
         const unsigned tb = (unsigned)tt * B + b;
         const unsigned jc = j < N ? j : N - 1;
 #pragma unroll
@@ -321,17 +334,17 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
         unsigned long long pt[4];
         arg_block<4>((unsigned)offsetof(BsimBwdArgs, Fm), pt);     // Fm, logW, lse (, sig_f)
         st_t = tt;
-        st_l = ldf(reinterpret_cast<const float*>(pt[2]), 4u * ((unsigned)tt * B + b));
-        if (tid < NP) get_slot(tt, tid, st, reinterpret_cast<const float*>(pt[0]), reinterpret_cast<const float*>(pt[1]));
-        if (two_slots && tid + NTB < NP)
-            get_slot(tt, tid + NTB, st2, reinterpret_cast<const float*>(pt[0]), reinterpret_cast<const float*>(pt[1]));
+        const gptr<const float> p_Fm = as_global<const float>(pt[0]), p_logW = as_global<const float>(pt[1]);
+        st_l = ldf(as_global<const float>(pt[2]), 4u * ((unsigned)tt * B + b));
+        if (tid < NP) get_slot(tt, tid, st, p_Fm, p_logW);
+        if (two_slots && tid + NTB < NP) get_slot(tt, tid + NTB, st2, p_Fm, p_logW);
     };
     auto stage_store = [&](float* buf) {
         if (tid < NP) put_slot(buf, tid, st, st_l);
         if (two_slots && tid + NTB < NP) put_slot(buf, tid + NTB, st2, st_l);
         for (int j = tid + (two_slots ? 2 : 1) * NTB; j < NP; j += NTB) {
             float raw[DX + 1];
-            get_slot(st_t, j, raw, PSVO_ARG(BsimBwdArgs, Fm), PSVO_ARG(BsimBwdArgs, logW));
+            get_slot(st_t, j, raw, PSVO_GARG(BsimBwdArgs, Fm), PSVO_GARG(BsimBwdArgs, logW));
             put_slot(buf, j, raw, st_l);
         }
     };
@@ -394,14 +407,14 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
     auto load_step = [&](bool lst, bool fst, StepIn& s) {    // (the offsets already point at the step to load)
         unsigned long long pb[8];
         arg_block<8>((unsigned)offsetof(BsimBwdArgs, obs), pb);
-        const float* const p_obs = reinterpret_cast<const float*>(pb[0]);
-        const float* const p_eps = reinterpret_cast<const float*>(pb[1]);
-        const float* const p_bwX = reinterpret_cast<const float*>(pb[2]);
-        const int32_t* const p_sel = reinterpret_cast<const int32_t*>(pb[3]);
-        const float* const p_lam2 = reinterpret_cast<const float*>(pb[4]);
-        const float* const p_om = reinterpret_cast<const float*>(pb[5]);
-        const float* const p_mu1 = reinterpret_cast<const float*>(pb[6]);
-        const float* const p_bm = PSVO_ARG(BsimBwdArgs, bmu2);
+        const gptr<const float> p_obs = as_global<const float>(pb[0]);
+        const gptr<const float> p_eps = as_global<const float>(pb[1]);
+        const gptr<const float> p_bwX = as_global<const float>(pb[2]);
+        const gptr<const int32_t> p_sel = as_global<const int32_t>(pb[3]);
+        const gptr<const float> p_lam2 = as_global<const float>(pb[4]);
+        const gptr<const float> p_om = as_global<const float>(pb[5]);
+        const gptr<const float> p_mu1 = as_global<const float>(pb[6]);
+        const gptr<const float> p_bm = PSVO_GARG(BsimBwdArgs, bmu2);
         s.sel = ldi(p_sel, o_n);
 #pragma unroll
         for (int d = 0; d < DX; ++d) {
@@ -422,8 +435,22 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
 #pragma unroll
         for (int k = 0; k < DY; ++k) o_knm[k] += s_knm;
     };
-    StepIn cur_in, nxt_in;
+    // The wave waits for a step's inputs in ONE place: `settle`, where the words become this step's (in front of the loop for
+    // step 0, in the rotation that ends step t for step t + 1).  The empty asm reads every word, so the s_waitcnt that
+    // guards them stands there, and redefines it, so nothing later has a load to wait for.  Left to its own counting hipcc
+    // waits at the first use instead, which is BEHIND the next prefetch, and there it has to assume the path of the last step
+    // (no loads issued: `t + 1 < T` is false), on which only vmcnt(0) proves the older load complete: the wave then sat out the
+    // round trip of the loads it had just issued, in every step.  (The last step has nothing to request and rotates zeros, so
+    // that every path of the loop passes through the one settle: a path around it would leave hipcc a load to guard at the
+    // first write of these registers in the next prefetch.)
+    auto settle = [&](StepIn& s) {
+        keep_in_vgpr(s.eps); keep_in_vgpr(s.bm); keep_in_vgpr(s.xp); keep_in_vgpr(s.mu1); keep_in_vgpr(s.y);
+        keep_in_vgpr(s.om); keep_in_vgpr(s.lam2);
+        asm volatile("" : "+v"(s.sel));
+    };
+    StepIn cur_in;
     load_step(T == 1, true, cur_in);
+    settle(cur_in);
 
     phase_skew(a.skew);
     SEC_INIT(bsim_bwd2)
@@ -442,7 +469,12 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
         // 3 Dx + 4 registers they land in would be live across it, and the kernel is at its 256-VGPR budget there); the MLP
         // phase, the chain reductions and the two barriers that follow still cover most of their latency.
         constexpr bool kLatePrefetch = (DX >= 3);
-        if (!kLatePrefetch && t + 1 < T) load_step(t + 2 == T, false, nxt_in);
+        StepIn nxt_in;
+        auto prefetch = [&]() {
+            if (t + 1 < T) load_step(t + 2 == T, false, nxt_in);
+            else nxt_in = StepIn{};
+        };
+        if (!kLatePrefetch) prefetch();
         SEC(1);   // issue of the prefetch loads
 
         // ---- recompute the proposal ---------------------------------------------------------------------
@@ -830,7 +862,7 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
             }
         }
 
-        if (kLatePrefetch && t + 1 < T) load_step(t + 2 == T, false, nxt_in);
+        if (kLatePrefetch) prefetch();
         if (kLateTile && t + 1 < T && t >= 1) stage_load(t);
         SEC(4);   // hand-back
         // ---- f(x_{t+1} | x~), g(y_t | x~) ------------------------------------------------------------------------
@@ -866,8 +898,8 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
             if (srow) {
 #pragma unroll
                 for (int d = 0; d < DX; ++d) {
-                    stf(reinterpret_cast<float*>(pr[1]), o_dnm[d] - s_dnm, dFo[d]);
-                    stf(reinterpret_cast<float*>(pr[0]), o_dnm[d] - s_dnm, x[d]);
+                    stf(as_global<float>(pr[1]), o_dnm[d] - s_dnm, dFo[d]);
+                    stf(as_global<float>(pr[0]), o_dnm[d] - s_dnm, x[d]);
                 }
             }
             float gm[DY], dGo[DY];
@@ -881,7 +913,7 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
                 const float z = (y[k] - gm[k]) * isg[k];
                 dGo[k] = dphi * z * isg[k] * dmean;
                 if (h0) acc_add(AC::kSg + k, dphi * (z * z - 1.f) * isg[k]);
-                if (srow) stf(reinterpret_cast<float*>(pr[2]), o_knm[k] - s_knm, dGo[k]);
+                if (srow) stf(as_global<float>(pr[2]), o_knm[k] - s_knm, dGo[k]);
             }
             MG::template bwd_input_part<PART>(wg, part, x, dGo, dxt);
         }
@@ -905,7 +937,7 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
                 dmu1[d] = dmu[d] * pc[d] * pi1[d];
                 outv[d] = dmu[d] * pc[d] * pi2[d];
                 if (lead) {
-                    stf(PSVO_ARG(BsimBwdArgs, dmu1), o_dn[d] - s_dn, dmu1[d]);
+                    stf(PSVO_GARG(BsimBwdArgs, dmu1), o_dn[d] - s_dn, dmu1[d]);
                     acc_add(AC::kSc + d, sce[d] + aw * pic[d]);   // -sum_m dq_m / c = a / c
                     acc_add(AC::kSmm1 + d, dmu[d] * mu1[d]);
                     acc_add(AC::kSmb + d, dmu[d] * bm[d]);
@@ -927,7 +959,7 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
             for (int d = 0; d < DX; ++d) {
                 outv[d] = dmu[d];
                 if (lead) {
-                    stf(PSVO_ARG(BsimBwdArgs, dmu1), o_dn[d] - s_dn, 0.f);
+                    stf(PSVO_GARG(BsimBwdArgs, dmu1), o_dn[d] - s_dn, 0.f);
                     acc_add(AC::kSinit + d, sce[d] + aw * is_init[d]);
                 }
             }
@@ -937,19 +969,23 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
         if (lead) {
 #pragma unroll
             for (int d = 0; d < DX; ++d) {
-                stf(PSVO_ARG(BsimBwdArgs, dbmu2_rows), o_dn[d] - s_dn, last ? 0.f : outv[d]);
-                if (last) PSVO_ARG(BsimBwdArgs, dminit_rows)[((size_t)b * DX + d) * N + n] = outv[d];
-                if (first) PSVO_ARG(BsimBwdArgs, dimean_rows)[((size_t)b * DX + d) * N + n] = dim[d];
+                stf(PSVO_GARG(BsimBwdArgs, dbmu2_rows), o_dn[d] - s_dn, last ? 0.f : outv[d]);
+                if (last) PSVO_GARG(BsimBwdArgs, dminit_rows)[((size_t)b * DX + d) * N + n] = outv[d];
+                if (first) PSVO_GARG(BsimBwdArgs, dimean_rows)[((size_t)b * DX + d) * N + n] = dim[d];
             }
         }
         SEC(6);   // chain reductions, MLP_q1inv input gradient
         __syncthreads();
+        // rotation: the next step's inputs were requested a step (Dx >= 3: an MLP phase and the chain reductions) ago.  The tile entries
+        // (st, st2, st_l) were requested before them and vmcnt counts in order: stage_store below has nothing left to wait for.
+        settle(nxt_in);
+        cur_in = nxt_in;
         // ---- this workgroup's partial of d Fm[t-1] / d logW[t-1]: fold the four waves (fixed order) ------------------------
         const size_t tb = (size_t)t * B + b;
         if (!first) {
             const size_t tbm = tb - B;
-            float* const pF = PSVO_ARG(BsimBwdArgs, dFm_part) + (tbm * nblk + blk) * DX * N;
-            float* const pW = PSVO_ARG(BsimBwdArgs, dlogW_part) + (tbm * nblk + blk) * N;
+            const gptr<float> pF = PSVO_GARG(BsimBwdArgs, dFm_part) + (tbm * nblk + blk) * DX * N;
+            const gptr<float> pW = PSVO_GARG(BsimBwdArgs, dlogW_part) + (tbm * nblk + blk) * N;
             for (int j = tid; j < N; j += NTB) {
 #pragma unroll
                 for (int d = 0; d < NA; ++d) {
@@ -962,8 +998,8 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
             }
         }
         if (last) {
-            float* const pF = PSVO_ARG(BsimBwdArgs, dFm_part) + (tb * nblk + blk) * DX * N;
-            float* const pW = PSVO_ARG(BsimBwdArgs, dlogW_part) + (tb * nblk + blk) * N;
+            const gptr<float> pF = PSVO_GARG(BsimBwdArgs, dFm_part) + (tb * nblk + blk) * DX * N;
+            const gptr<float> pW = PSVO_GARG(BsimBwdArgs, dlogW_part) + (tb * nblk + blk) * N;
             for (int j = tid; j < N; j += NTB) {
 #pragma unroll
                 for (int d = 0; d < DX; ++d) pF[d * N + j] = 0.f;
@@ -972,7 +1008,6 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
         }
         SEC(7);   // barrier, workgroup sums, d Fm / d logW flush
         if (t + 1 < T && t >= 1) stage_store(nxt);
-        cur_in = nxt_in;
         __syncthreads();
         SEC(8);   // tile store + barrier
     }
@@ -993,7 +1028,7 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
         if (tid == 0) {
             float s = 0.f;
             for (int w = 0; w < nwv; ++w) s += red[w];
-            a.sacc_part[((size_t)b * nblk + blk) * AC::kN + i] = s;
+            as_global(a.sacc_part)[((size_t)b * nblk + blk) * AC::kN + i] = s;
         }
         __syncthreads();
     }
