@@ -604,7 +604,7 @@ int psvo_filter_backward(const psvo_desc* desc,
 /* ---------------------------------------------------------------------------------------------
  * Wide observations ("wobs"): the forward filter, its reverse pass and MLP_g's weight gradient for 3 <= Dy <= 32
  * (psvo_amd/csrc/filter_wobs.hip; added within ABI 6 -- the entry points above keep Dy in {1, 2}).  For the filter objectives
- * (SVO, AESMC, IWAE); the backward simulations evaluate MLP_g too and stay at Dy <= 2.
+ * (SVO, AESMC, IWAE); PSVO's backward simulation has its own wide entry points further down, PSVOwR's stays at Dy <= 2.
  * Envelope of the two filter entry points: 3 <= Dy <= 32 (a run-time bound, nothing is instantiated per width), Dx in {2,3,4},
  * H in {16,32,64} (narrower: zero-padded by the caller as above), N <= 512, one hidden layer (desc->layers <= 1), Gaussian and
  * Poisson emission, every bootstrap / two_q wiring, resampling on or off.  Anything else -- Dy <= 2 and Dy > 32 included --
@@ -650,6 +650,78 @@ int psvo_filter_backward_wobs(const psvo_desc* desc,
 int psvo_mlp_wgrad_wobs_blocks(long long rows);
 int psvo_mlp_wgrad_wobs(long long S, int L, int Din, int H, int Dout, const float* X, const float* dOut,
                         const psvo_mlp* w, float* partial, float* grad, int accumulate, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * PSVO on wide observations: the backward simulation with proposal and its reverse pass for 3 <= Dy <= 32
+ * (psvo_amd/csrc/bsim_wobs.hip), and the wide reverse filter with upstream gradients of Fm / logW (added within ABI 6).
+ * The Dy <= 2 entry points are unchanged: psvo_bsim_forward, psvo_bsim_backward and psvo_bsim_backward_fold keep answering
+ * PSVO_ERR_UNSUPPORTED for Dy = 3, and psvo_filter_backward_wobs keeps its signature and its results bit for bit.
+ * Envelope of the two backward-simulation entry points: 3 <= Dy <= 32 (a run-time bound, nothing is instantiated per width),
+ * Dx in {2,3,4}, H in {16,32,64}, M in {4,8,16,32}, N <= 512, one hidden layer (desc->layers in {0, 1}), state-independent
+ * scales, Gaussian and Poisson emission.  A missing required pointer, B <= 0, T < 2 or N <= 0 is PSVO_ERR_INVALID whatever the
+ * shape; anything else outside the envelope is PSVO_ERR_UNSUPPORTED; both come back before a device is touched.
+ *
+ * psvo_bsim_forward_wobs: contract, argument list, outputs and layouts of psvo_bsim_forward (bwX, flp, glp, Omega, sel_out,
+ *   score and the optional saves lam2_all, om_all, mu1_all), same arithmetic and the same draw rule (sel = the number of CDF
+ *   entries <= u * total over the chain's M sub-particles, clamped to M - 1; or teacher-forced sel_in), so that psvo_elbo_bsim
+ *   and the host code consume the result unchanged.  Workgroup = 256 / M chains of one sequence, lane = (chain, sub-particle),
+ *   persistent over t = T-1 .. 0; the filter term is an online log-sum-exp (log2 domain) over the forward particles in blocks
+ *   of 8, j ascending; the emission log-density adds z_e^2 in the order e = 0 .. Dy-1.
+ * psvo_bsim_backward_wobs: reverse mode of it, psvo_bsim_backward and psvo_bsim_backward_fold in one call.  Inputs as there;
+ *   outputs: the rows xt, dFt (T,B,Dx,N,M), dGt (T,B,Dy,N,M), dmu1 (T,B,Dx,N); the per-chain rows dbmu2_rows (T,B,Dx,N),
+ *   dminit_rows, dimean_rows (B,Dx,N); the folded dFm (T,B,Dx,N), dlogW (T,B,N), dlse (T,B) = -sum_n dlogW; the scale
+ *   gradients dsig_f, dsig_q1inv, dsig_bq2, dsig_init, disig (Dx), dsig_g (Dy).
+ *   ws: psvo_bsim_wobs_ws_floats(B, T, N, M, Dx, Dy) = T B nblk (Dx + 1) N + B nblk (7 Dx + Dy) floats with
+ *   nblk = psvo_bsim_wobs_blocks(N, M) = ceil(N / (NT / M)), NT = min(256, 64 ceil(N M / 64)): the per-workgroup partials.
+ *   No float atomics; every sum has one fixed order: a pair sum adds the 16 sub-particles of a lane row in lane order, rows by
+ *   two swap-adds, waves in wave order, workgroups in workgroup order; sums over a chain's sub-particles are butterflies;
+ *   scale sums are per-lane values folded lanes first (DPP scan), then waves, then (sequence, workgroup) rows in order;
+ *   d sig_g[e] is one column per lane folded in lane order.  Two runs of the same inputs are bit-identical whatever
+ *   PSVO_TUNE_DETERMINISTIC is.
+ * psvo_filter_backward_wobs_ext: psvo_filter_backward_wobs with the upstream gradients dFm_ext (T,B,nparts,Dx,N) and
+ *   dlogW_ext (T,B,nparts,N) of psvo_filter_backward (NULL = 0; nparts >= 1 when either is given), added in part order.
+ *   With both NULL its outputs equal psvo_filter_backward_wobs bit for bit (that entry point forwards with 0, NULL, NULL).
+ * ------------------------------------------------------------------------------------------- */
+int psvo_bsim_forward_wobs(const psvo_desc* desc,
+                           const float* X, const float* Fm, const float* logW, const float* lse,
+                           const psvo_mlp* f, const psvo_mlp* g, const psvo_mlp* q1_inv,
+                           const float* sig_f, const float* sig_g, const float* sig_q1inv, const float* sig_bq2,
+                           const float* bmu2, const float* minit, const float* sig_init,
+                           const float* imean, const float* isig,
+                           const float* obs, const float* eps_b, const float* u_b, const int32_t* sel_in,
+                           float* bwX, float* flp, float* glp, float* Omega, int32_t* sel_out,
+                           float* score,
+                           float* lam2_all, float* om_all, float* mu1_all,
+                           void* stream);
+int psvo_bsim_wobs_blocks(int N, int M);
+long long psvo_bsim_wobs_ws_floats(int B, int T, int N, int M, int Dx, int Dy);
+int psvo_bsim_backward_wobs(const psvo_desc* desc,
+                            const float* Fm, const float* logW, const float* lse,
+                            const psvo_mlp* f, const psvo_mlp* g, const psvo_mlp* q1_inv,
+                            const float* sig_f, const float* sig_g, const float* sig_q1inv, const float* sig_bq2,
+                            const float* bmu2, const float* minit, const float* sig_init,
+                            const float* imean, const float* isig,
+                            const float* obs, const float* eps_b,
+                            const float* bwX, const int32_t* sel,
+                            const float* lam2_all, const float* om_all, const float* mu1_all,
+                            const float* dscore,
+                            float* xt, float* dFt, float* dGt, float* dmu1,
+                            float* dbmu2_rows, float* dminit_rows, float* dimean_rows,
+                            float* dFm, float* dlogW, float* dlse,
+                            float* dsig_f, float* dsig_g, float* dsig_q1inv, float* dsig_bq2, float* dsig_init,
+                            float* disig, float* ws, void* stream);
+int psvo_filter_backward_wobs_ext(const psvo_desc* desc,
+                                  const psvo_mlp* q1, const psvo_mlp* f, const psvo_mlp* g,
+                                  const float* sig_q1, const float* sig_q2, const float* sig_f, const float* sig_g,
+                                  const float* mu2,
+                                  const float* m0, const float* sig0, const float* fm0, const float* fsig0,
+                                  const float* obs, const float* eps,
+                                  const float* X, const float* Fm, const float* P1, const float* logW, const float* lse,
+                                  const int32_t* idx,
+                                  const float* dlse, int nparts, const float* dFm_ext, const float* dlogW_ext,
+                                  float* dP, float* dF, float* dG, float* dmu2, float* dm0, float* dfm0,
+                                  float* dsig_q1, float* dsig_q2, float* dsig_f, float* dsig_g, float* dsig0, float* dfsig0,
+                                  float* ws, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * One-hidden-layer MLP over plain rows (the hoisted per-(sequence, step) networks q0, q2, BSim_q2,

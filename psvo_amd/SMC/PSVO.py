@@ -7,12 +7,13 @@ import torch
 
 from .. import ops
 from .. import autograd
-from ..autograd import BsimCovFunction, BsimFunction, ElboBsimFunction, Overlap, side_stream
+from ..autograd import BsimCovFunction, BsimFunction, BsimWobsFunction, ElboBsimFunction, Overlap, side_stream
 from .SVO import SVO
 
 
 class PSVO(SVO):
     uses_backward_simulation = True
+    has_wide_backward_simulation = True
 
     def __init__(self, model, FLAGS, name="log_ZSMC"):
         SVO.__init__(self, model, FLAGS, name="log_ZSMC")
@@ -40,8 +41,9 @@ class PSVO(SVO):
         #  f.mean(mu_0) of the t = 0 term accumulates into the same gradient slice on the main stream)
         both = self.model.use_bootstrap and self.model.use_2_q
         self._release()
+        # (wide observations, FLAGS.BSim_wide_obs: the wide filter and the wide backward simulation on one stream)
         self._ov = (Overlap(side_stream(obs.device), side_stream(obs.device, 1) if both else None)
-                    if (autograd.OVERLAP and obs.is_cuda) else None)
+                    if (autograd.OVERLAP and obs.is_cuda and not self.wide_obs) else None)
         self._sigmas = self.model.sigmas()          # every scale vector of this evaluation, one fused launch
         filt = self.SMC(hidden, obs, noise=noise)                      # pre-resampling X and log_Ws
         bs = self.backward_simulation_w_proposal(filt, obs, noise=noise)
@@ -128,13 +130,16 @@ class PSVO(SVO):
         if obs_TB is None or obs_TB.shape[:2] != (T, B):
             obs_TB = obs.transpose(0, 1).contiguous().float()
 
-        # one opaque autograd node: psvo_bsim_forward / psvo_bsim_backward
+        # one opaque autograd node: psvo_bsim_forward / psvo_bsim_backward, or their wide-observation forms (Dy > 2)
         desc = self._desc(M)
         gb = (self._gbuf(model.f_tran), self._gbuf(model.g_tran), self._gbuf(model.q1_inv_tran))
         desc._gbufs = gb if all(v is not None for v in gb) else None
+        node = BsimFunction
+        if self.wide_obs:
+            node, desc._gbufs = BsimWobsFunction, None
         first, extra = self._mlp_args(self._mlp_params(model.f_tran), self._mlp_params(model.g_tran),
                                       self._mlp_params(model.q1_inv_tran))
-        score, bwX, flp, glp, Omega, sel = BsimFunction.apply(
+        score, bwX, flp, glp, Omega, sel = node.apply(
             desc, obs_TB, eps_b, u_b, sel_in, filt["Fm"], filt["logW"], filt["lse"],
             *first, self._sigma(self.f), self._sigma(self.g), self._sigma(self.q1_inv), self._sigma(self.BSim_q2),
             bmu2, minit, self._sigma(self.BSim_q_init), imean, isig, *extra)

@@ -12,6 +12,8 @@ from .PSVO import PSVO
 
 
 class PSVOwR(PSVO):
+    has_wide_backward_simulation = False
+
     def __init__(self, model, FLAGS, name="log_ZSMC"):
         PSVO.__init__(self, model, FLAGS, name=name)
 

@@ -15,12 +15,14 @@ from ..autograd import FilterCovFunction, FilterFunction, FilterWobsFunction
 class SVO:
     # the objective runs a backward simulation behind the filter (PSVO, PSVOwR): those kernels evaluate MLP_g for Dy <= 2 only
     uses_backward_simulation = False
+    # ... and has a wide-observation form of it (PSVO: csrc/bsim_wobs.hip), taken when FLAGS.BSim_wide_obs asks for it
+    has_wide_backward_simulation = False
     # observation widths of the plain filter kernels / of the wide-observation ("wobs") kernels (csrc/filter_wobs.hip)
     _PLAIN_DY, _WOBS_MAX_DY = 2, 32
 
     def __init__(self, model, FLAGS, name="log_ZSMC"):
         self.model = model
-        self.wide_obs = self._route_wide_obs(model)
+        self.wide_obs = self._route_wide_obs(model, bool(getattr(FLAGS, "BSim_wide_obs", False)))
 
         # SSM distributions
         self.q0 = model.q0_dist
@@ -47,23 +49,31 @@ class SVO:
         self.generator = None        # torch.Generator on the compute device; None = global RNG
 
     @classmethod
-    def _route_wide_obs(cls, model):
+    def _route_wide_obs(cls, model, bsim_wide_obs=False):
         """True when the filter of this objective runs on the wide-observation kernels (model.Dy > 2: psvo_filter_forward_wobs /
-        psvo_filter_backward_wobs / psvo_mlp_wgrad_wobs).  What those kernels do not cover is refused here, up front."""
+        psvo_filter_backward_wobs / psvo_mlp_wgrad_wobs) -- and, for PSVO under FLAGS.BSim_wide_obs (`bsim_wide_obs`), its
+        backward simulation on psvo_bsim_forward_wobs / psvo_bsim_backward_wobs.  What those kernels do not cover is refused
+        here, up front.  Without the flag PSVO stays refused: making it the default is a one-line change here."""
         Dy = getattr(model, "Dy", cls._PLAIN_DY)          # (a bare model object without widths has nothing to route)
         if Dy <= cls._PLAIN_DY:
             return False
         limit = "observations wider than Dy = %d run on the wide-observation filter kernels" % cls._PLAIN_DY
         if Dy > cls._WOBS_MAX_DY:
             raise ValueError("Dy = %d: %s, which take 3 <= Dy <= %d; no fallback path exists" % (Dy, limit, cls._WOBS_MAX_DY))
-        if cls.uses_backward_simulation:
+        if cls.uses_backward_simulation and not bsim_wide_obs:
             raise ValueError("Dy = %d with PSVO / PSVOwR: %s of the filter objectives (SVO, AESMC, IWAE); the backward-simulation "
-                             "kernels evaluate the emission network for Dy <= %d only" % (Dy, limit, cls._PLAIN_DY))
+                             "kernels evaluate the emission network for Dy <= %d only (PSVO: pass --BSim_wide_obs for the "
+                             "wide-observation backward simulation)" % (Dy, limit, cls._PLAIN_DY))
+        if cls.uses_backward_simulation and not cls.has_wide_backward_simulation:
+            raise ValueError("Dy = %d with PSVOwR: --BSim_wide_obs covers PSVO only; the cross-chain resampling kernels of PSVOwR "
+                             "evaluate the emission network for Dy <= %d only" % (Dy, cls._PLAIN_DY))
         if model.output_cov:
             raise ValueError("Dy = %d with output_cov: %s, which take state-independent scales; the state-dependent-scale "
                              "kernels take Dy <= %d" % (Dy, limit, cls._PLAIN_DY))
         trans = [model.q1_tran, model.g_tran] + ([] if model.use_bootstrap else [model.f_tran])
-        deep = [t.Dhs for t in trans if len(t.Dhs) != 1]
+        if cls.uses_backward_simulation:
+            trans += [t for t in (model.f_tran, getattr(model, "q1_inv_tran", None)) if t is not None]
+        deep = [t.Dhs for t in dict.fromkeys(trans) if len(t.Dhs) != 1]
         if deep:
             raise ValueError("Dy = %d with per-particle MLP layers %s: %s, which take one hidden layer per MLP; two hidden "
                              "layers run for Dy <= %d only" % (Dy, deep, limit, cls._PLAIN_DY))

@@ -322,10 +322,10 @@ class FilterCovFunction(torch.autograd.Function):
 
 class FilterWobsFunction(torch.autograd.Function):
     """psvo_filter_forward_wobs / psvo_filter_backward_wobs: the forward filter for wide observations (3 <= Dy <= 32, one hidden
-    layer per particle MLP) of the filter objectives SVO / AESMC / IWAE.
+    layer per particle MLP) of the filter objectives SVO / AESMC / IWAE and, with FLAGS.BSim_wide_obs, of PSVO.
 
-    apply(...) takes FilterFunction's arguments and returns its outputs; lse is the differentiable one (the reverse kernel takes
-    no upstream gradient of Fm / logW: no backward simulation runs behind a wide filter).
+    apply(...) takes FilterFunction's arguments and returns its outputs; lse, Fm and logW are differentiable (gradients on Fm /
+    logW -- a BsimWobsFunction behind the filter -- go through psvo_filter_backward_wobs_ext).
     One stream, gradients returned as tensors (no in-place accumulation into the flat buffer)."""
 
     @staticmethod
@@ -444,6 +444,42 @@ class BsimFunction(torch.autograd.Function):
         return (None, None, None, None, None, dFm, dlogW, r["dlse"] if ctx.needs_input_grad[7] else None) + gfirst + (
             r["dsig_f"], r["dsig_g"], r["dsig_q1inv"], r["dsig_bq2"], r["dbmu2"],
             r["dminit"], r["dsig_init"], r["dimean"], r["disig"]) + gextra
+
+
+class BsimWobsFunction(torch.autograd.Function):
+    """psvo_bsim_forward_wobs / psvo_bsim_backward_wobs: the backward simulation behind a wide filter (3 <= Dy <= 32, one hidden
+    layer per particle MLP).
+
+    apply(...) takes BsimFunction's arguments and returns its outputs.  One stream, gradients returned as tensors (no overlap
+    wiring, no in-place accumulation into the flat buffer)."""
+
+    @staticmethod
+    def forward(ctx, desc, obs_TB, eps_b, u_b, sel_in, Fm, logW, lse, *t):
+        t = [_cf(v) for v in t]
+        f, g, q = _mlps(t)
+        rest = t[12:21]                 # sig_f, sig_g, sig_q1inv, sig_bq2, bmu2, minit, sig_init, imean, isig
+        filt = {"X": None, "Fm": _cf(Fm), "logW": _cf(logW), "lse": _cf(lse)}
+        bs = ops.bsim_forward_wobs(desc, {**filt, "X": filt["Fm"]}, f, g, q, *rest, obs_TB, eps_b, u_b, sel_in,
+                                   save=any(ctx.needs_input_grad))
+        ctx.desc, ctx.filt, ctx.bs = desc, filt, _aliases(bs)
+        ctx.saved = (f, g, q, rest, obs_TB, eps_b)
+        ctx.mark_non_differentiable(bs["bwX"], bs["flp"], bs["glp"], bs["Omega"], bs["sel"])
+        ctx.set_materialize_grads(False)
+        return bs["score"], bs["bwX"], bs["flp"], bs["glp"], bs["Omega"], bs["sel"]
+
+    @staticmethod
+    def backward(ctx, dscore, *_):
+        desc = ctx.desc
+        if dscore is None:                    # (score unused by the loss)
+            dscore = torch.zeros(desc.B, desc.N, device=ctx.filt["Fm"].device)
+        f, g, q, rest, obs_TB, eps_b = ctx.saved
+        r = ops.bsim_backward_wobs(desc, ctx.filt, f, g, q, *rest, obs_TB, eps_b, ctx.bs, _cg(dscore).float())
+        Dx, Dy, H = desc.Dx, desc.Dy, desc.H
+        gfirst, _ = _mlp_grads(r, ("gf", "gg", "gq1inv"), ((Dx, Dx), (Dx, Dy), (Dx, Dx)), H, 1, (None, None, None))
+        ops.sum_chain_rows(r, desc.T, desc.B, Dx)
+        return (None, None, None, None, None, r["dFm"], r["dlogW"], r["dlse"] if ctx.needs_input_grad[7] else None) + gfirst + (
+            r["dsig_f"], r["dsig_g"], r["dsig_q1inv"], r["dsig_bq2"], r["dbmu2"],
+            r["dminit"], r["dsig_init"], r["dimean"], r["disig"])
 
 
 def _bsim_cov_forward(ctx, op, desc, obs_TB, eps_b, Fm, Fs, logW, lse, t, **draws):

@@ -12,7 +12,7 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libpsvo_hip.so")
 # (longest compiles first: with 8 parallel hipcc jobs the build then ends when the work does, not when a late-started
 #  psvowr_bwd unit does; the *_l2 units are the same sources compiled with PSVO_L = 2 -- two hidden layers per particle MLP)
-SOURCES = ["bsim_cov.hip", "psvowr_bwd_l2.hip", "psvowr_bwd.hip", "bsim_bwd_dx4_l2.hip", "bsim_fwd_l2.hip", "bsim_fwd.hip",
+SOURCES = ["bsim_wobs.hip", "bsim_cov.hip", "psvowr_bwd_l2.hip", "psvowr_bwd.hip", "bsim_bwd_dx4_l2.hip", "bsim_fwd_l2.hip", "bsim_fwd.hip",
            "bsim_bwd_dx2_l2.hip", "bsim_bwd_dx3_l2.hip", "psvowr_fwd.hip", "psvowr_fwd_l2.hip", "bsim_bwd_dx4.hip",
            "bsim_bwd_dx2.hip", "bsim_bwd_dx3.hip", "filter_bwd_l2.hip", "bsim_bwd2_dx2.hip", "filter_bwd.hip",
            "filter_fwd_l2.hip", "filter_cov.hip", "filter_wobs.hip", "filter_fwd.hip", "bsim_bwd2_dx4.hip", "bsim_bwd2_dx3.hip", "mlp_grad.hip", "lstm_bwd.hip",
@@ -21,7 +21,8 @@ HEADERS = ["common.h", "mlp2_valu.h", os.path.join("..", "..", "include", "psvo_
 # headers only some units include (a change of bsim_bwd2_impl.h rebuilds 4 units, not 27)
 UNIT_HEADERS = {"bsim_bwd_impl.h": ("bsim_bwd_dx", "bsim_bwd2_dx", "bsim_bwd.hip"),
                 "bsim_bwd2_impl.h": ("bsim_bwd2_dx", "bsim_bwd.hip"),
-                "ffbs_pair.h": ("ffbs.hip", "ffbsi.hip")}
+                "ffbs_pair.h": ("ffbs.hip", "ffbsi.hip"),
+                "wobs_common.h": ("filter_wobs.hip", "bsim_wobs.hip")}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-slp-vectorize"]
 # Round 2 built the two-hidden-layer units with `-mllvm -vgpr-regalloc=basic`: their per-lane H x H layer held 2 H values per
 # lane and under that pressure the default (greedy) allocator split live ranges around divergent regions, with hipcc 7.2 placing

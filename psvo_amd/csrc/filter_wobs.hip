@@ -13,117 +13,12 @@
 //     chunks of 16 or 32 (H + H live values per lane would not fit a 512-lane workgroup); the Dy sums of d sig_g live in LDS, one column per lane (owner lanes), folded in lane order after the time loop;
 //   * the gather of resampled particles back-propagates as a scatter-add into the parents.  Every parent collects its
 //     children itself, in child order, from a staged (ancestor, value) list in LDS: no atomics, one fixed order.
-// Kernels are instantiated for Dx in {2,3,4} x H in {16,32,64} (9 each way), the weight gradient for Din in {1..4} x
+// Kernels are instantiated for Dx in {2,3,4} x H in {16,32,64} (9 forward; 18 reverse: with and without the upstream gradients of Fm / logW, template flag EXT), the weight gradient for Din in {1..4} x
 // H in {16,32,64} x one or two 16-wide output tiles (24).
-#include "common.h"
+#include "wobs_common.h"
 
 namespace psvo {
 namespace wobs {
-
-constexpr int kMaxDy = 32;
-
-// sum of `v` over the workgroup in a fixed order (lanes by the DPP scan, waves in wave order); `red` has 16 floats
-__device__ __forceinline__ float block_sum(float v, float* red, int wave, int lane, int nw) {
-    v = wave_sum(v);
-    if (nw == 1) return v;
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    float s = 0.f;
-    for (int i = 0; i < nw; ++i) s += red[i];
-    __syncthreads();
-    return s;
-}
-
-// LDS image of MLP_g: W1[DX][H] | b1[H] | W2T[Dy][H] | b2[Dy]   (room for Dy = 32)
-template <int DX, int H>
-struct GLds {
-    static constexpr int kW1 = 0;
-    static constexpr int kB1 = DX * H;
-    static constexpr int kW2 = kB1 + H;
-    static constexpr int kB2 = kW2 + kMaxDy * H;
-    static constexpr int kSize = kB2 + kMaxDy;
-
-    __device__ static void load(float* __restrict__ w, const psvo_mlp& p, int Dy, int tid, int nthreads) {
-        for (int i = tid; i < DX * H; i += nthreads) w[kW1 + i] = p.W1[i];
-        for (int i = tid; i < H; i += nthreads) w[kB1 + i] = p.b1[i];
-        for (int i = tid; i < Dy * H; i += nthreads) {
-            const int o = i / H, k = i - o * H;
-            w[kW2 + i] = p.W2[k * Dy + o];
-        }
-        for (int i = tid; i < Dy; i += nthreads) w[kB2 + i] = p.b2[i];
-    }
-
-    // h = relu(x W1 + b1)
-    __device__ __forceinline__ static void hidden(const float* __restrict__ w, const float (&x)[DX], float (&h)[H]) {
-#pragma unroll
-        for (int k = 0; k < H; k += 4) {
-            const float4 b = *reinterpret_cast<const float4*>(w + kB1 + k);
-            float p0 = b.x, p1 = b.y, p2 = b.z, p3 = b.w;
-#pragma unroll
-            for (int d = 0; d < DX; ++d) {
-                const float4 wi = *reinterpret_cast<const float4*>(w + kW1 + d * H + k);
-                p0 = fmaf(x[d], wi.x, p0); p1 = fmaf(x[d], wi.y, p1);
-                p2 = fmaf(x[d], wi.z, p2); p3 = fmaf(x[d], wi.w, p3);
-            }
-            h[k] = fmaxf(p0, 0.f); h[k + 1] = fmaxf(p1, 0.f); h[k + 2] = fmaxf(p2, 0.f); h[k + 3] = fmaxf(p3, 0.f);
-        }
-    }
-
-    // output e: h . W2T[e] + b2[e] (four partial sums, folded pairwise)
-    __device__ __forceinline__ static float out(const float* __restrict__ w, int e, const float (&h)[H]) {
-        const float* w2 = w + kW2 + e * H;
-        float s0 = w[kB2 + e], s1 = 0.f, s2 = 0.f, s3 = 0.f;
-#pragma unroll
-        for (int k = 0; k < H; k += 4) {
-            const float4 wo = *reinterpret_cast<const float4*>(w2 + k);
-            s0 = fmaf(h[k], wo.x, s0); s1 = fmaf(h[k + 1], wo.y, s1);
-            s2 = fmaf(h[k + 2], wo.z, s2); s3 = fmaf(h[k + 3], wo.w, s3);
-        }
-        return (s0 + s1) + (s2 + s3);
-    }
-
-    // Input gradient of MLP_g from the rows dg[o] = row[o * stride] (the lane's own d G rows, already in HBM), hidden units
-    // in chunks of HC so that a lane holds HC partial sums, not H:  dx += W1[:, chunk] ([pre > 0] * sum_o dg[o] W2T[o][chunk]).
-    template <int HC>
-    __device__ __forceinline__ static void bwd_input(const float* __restrict__ w, int Dy, const float* row, size_t stride,
-                                                     bool valid, const float (&x)[DX], float (&dx)[DX]) {
-        static_assert(H % HC == 0 && HC % 4 == 0, "hidden chunk");
-#pragma unroll 1
-        for (int kc = 0; kc < H; kc += HC) {
-            float dh[HC];
-#pragma unroll
-            for (int k = 0; k < HC; ++k) dh[k] = 0.f;
-#pragma unroll 1
-            for (int o = 0; o < Dy; ++o) {
-                const float dg = valid ? row[o * stride] : 0.f;
-                const float* w2 = w + kW2 + o * H + kc;
-#pragma unroll
-                for (int k = 0; k < HC; k += 4) {
-                    const float4 wo = *reinterpret_cast<const float4*>(w2 + k);
-                    dh[k] = fmaf(dg, wo.x, dh[k]); dh[k + 1] = fmaf(dg, wo.y, dh[k + 1]);
-                    dh[k + 2] = fmaf(dg, wo.z, dh[k + 2]); dh[k + 3] = fmaf(dg, wo.w, dh[k + 3]);
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < HC; k += 4) {
-                const float4 b = *reinterpret_cast<const float4*>(w + kB1 + kc + k);
-                float p0 = b.x, p1 = b.y, p2 = b.z, p3 = b.w;
-                float4 wi[DX];
-#pragma unroll
-                for (int d = 0; d < DX; ++d) {
-                    wi[d] = *reinterpret_cast<const float4*>(w + kW1 + d * H + kc + k);
-                    p0 = fmaf(x[d], wi[d].x, p0); p1 = fmaf(x[d], wi[d].y, p1);
-                    p2 = fmaf(x[d], wi[d].z, p2); p3 = fmaf(x[d], wi[d].w, p3);
-                }
-                const float v0 = p0 > 0.f ? dh[k] : 0.f, v1 = p1 > 0.f ? dh[k + 1] : 0.f;
-                const float v2 = p2 > 0.f ? dh[k + 2] : 0.f, v3 = p3 > 0.f ? dh[k + 3] : 0.f;
-#pragma unroll
-                for (int d = 0; d < DX; ++d)
-                    dx[d] = fmaf(v3, wi[d].w, fmaf(v2, wi[d].z, fmaf(v1, wi[d].y, fmaf(v0, wi[d].x, dx[d]))));
-            }
-        }
-    }
-};
 
 // proposal / transition constants of a step (filter_fwd.hip: StepK)
 template <int DX>
@@ -411,7 +306,7 @@ static int launch_fwd(const FwdArgs& a, hipStream_t stream) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Reverse filter (filter_bwd.hip's persistent kernel; upstream gradient: d lse only).  One workgroup per sequence walks
+// Reverse filter (filter_bwd.hip's persistent kernel; upstream gradients: d lse and, through the _ext entry point, d Fm / d logW).  One workgroup per sequence walks
 // t = T-1 .. 0.  What step t leaves for step t-1 is D[n] = d loss / d (MLP_q1(x_{t-1}[n]), MLP_f(x_{t-1}[n])), carried in the
 // parent's own registers: the children stage (ancestor, values) in LDS and every parent adds its children in child order.
 // Per-sequence sums (FAcc of filter_bwd.hip with a run-time Dy): [2 sets x 5 Dx | Dy].
@@ -428,7 +323,22 @@ struct BwdArgs {
     float *dP, *dF, *dG, *dmu2, *dm0, *dfm0;
     float* sacc;             // (B, 10 Dx + Dy) per-sequence sums
     float* dm2_rows;         // (T,B,Dx,N) per-particle d mu2 rows, summed over N afterwards
+    // psvo_filter_backward_wobs_ext (kernel instantiated with EXT = true; the plain form never reads these).  They sit behind
+    // everything else and are fetched from the kernel arguments where they are used (common.h: PSVO_ARG): held in SGPRs across
+    // the time loop they pushed the kernel into scratch.
+    const float* dFm_ext;    // (T,B,nparts,Dx,N) or null: d loss / d Fm from a backward simulation behind the filter
+    const float* dlogW_ext;  // (T,B,nparts,N) or null: d loss / d logW, likewise
+    int nparts;              // leading "parts" axis of the two
 };
+
+// nparts of the launch, re-read from the kernel arguments at its point of use (arg_ptr of common.h for an int)
+__device__ __forceinline__ int arg_nparts() {
+    unsigned off = (unsigned)offsetof(BwdArgs, nparts);
+    asm volatile("" : "+s"(off));
+    typedef const char __attribute__((address_space(4))) * kptr;
+    typedef const int __attribute__((address_space(4))) * iptr;
+    return *(iptr)((kptr)__builtin_amdgcn_kernarg_segment_ptr() + off);
+}
 
 template <int DX>
 struct Acc {
@@ -441,7 +351,7 @@ struct Acc {
     static constexpr int kSg = 2 * kSet;     // d sigma_g (Dy)
 };
 
-template <int DX, int H>
+template <int DX, int H, bool EXT>
 __global__ void __launch_bounds__(512) filter_bwd_wobs_kernel(const BwdArgs a) {
     using MQ = MlpLds<DX, H, DX, 1>;
     using MG = GLds<DX, H>;
@@ -534,6 +444,15 @@ __global__ void __launch_bounds__(512) filter_bwd_wobs_kernel(const BwdArgs a) {
         // ---- gradient w.r.t. logW_t[n] ------------------------------------------------------------
         const float sm = valid ? exp2_fast((lw_t - lse_t) * kLog2e) : 0.f;
         float dlw = dlse_t * sm;
+        if constexpr (EXT) {    // parts added in part order
+            const float* dlogW_ext = PSVO_ARG(BwdArgs, dlogW_ext);
+            if (dlogW_ext) {
+                const int np = arg_nparts();
+                float ext = 0.f;
+                for (int p = 0; p < np; ++p) ext += dlogW_ext[(tb * np + p) * N + n];
+                dlw += ext;
+            }
+        }
         if (!a.resample) {
             const float tot = block_sum(dlnw, red, wave, lane, nw);
             dlw += dlnw - sm * tot;
@@ -600,6 +519,20 @@ __global__ void __launch_bounds__(512) filter_bwd_wobs_kernel(const BwdArgs a) {
         for (int d = 0; d < DX; ++d) {
             dPn[d] = valid ? carryP[d] : 0.f;
             dFn[d] = (valid && !a.bootstrap) ? carryF[d] : 0.f;
+        }
+        if constexpr (EXT) {    // Fm is MLP_f(x_t), i.e. MLP_q1(x_t) when bootstrap; parts added in part order
+            const float* dFm_ext = PSVO_ARG(BwdArgs, dFm_ext);
+            if (dFm_ext) {
+                const int np = arg_nparts();
+#pragma unroll
+                for (int d = 0; d < DX; ++d) {
+                    float ext = 0.f;
+                    for (int p = 0; p < np; ++p) ext += dFm_ext[((tb * np + p) * DX + d) * N + n];
+                    // (two plain adds: a conditional lvalue would take the arrays' addresses and put them in scratch)
+                    if (valid && a.bootstrap) dPn[d] += ext;
+                    if (valid && !a.bootstrap) dFn[d] += ext;
+                }
+            }
         }
         if (valid) {
 #pragma unroll
@@ -776,7 +709,8 @@ static int launch_bwd(const BwdArgs& a, const BwdOut& o, hipStream_t stream) {
     const int NT = (a.N + 63) & ~63;
     const size_t lds = bwd_lds_bytes<DX, H>(NT, a.Dy, a.bootstrap != 0);
     clear_hip_error();
-    hipLaunchKernelGGL((filter_bwd_wobs_kernel<DX, H>), dim3(a.B), dim3(NT), lds, stream, a);
+    if (a.dFm_ext || a.dlogW_ext) hipLaunchKernelGGL((filter_bwd_wobs_kernel<DX, H, true>), dim3(a.B), dim3(NT), lds, stream, a);
+    else hipLaunchKernelGGL((filter_bwd_wobs_kernel<DX, H, false>), dim3(a.B), dim3(NT), lds, stream, a);
     if (a.two_q) {
         const long long rows = (long long)a.T * a.B * DX;
         hipLaunchKernelGGL(wobs_row_sum_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, a.dm2_rows, rows,
@@ -1051,13 +985,13 @@ extern "C" long long psvo_filter_wobs_ws_floats(int B, int T, int N, int Dx, int
     return (long long)B * (10 * Dx + Dy) + (long long)T * B * Dx * N;
 }
 
-extern "C" int psvo_filter_backward_wobs(
+extern "C" int psvo_filter_backward_wobs_ext(
     const psvo_desc* desc, const psvo_mlp* q1, const psvo_mlp* f, const psvo_mlp* g, const float* sig_q1,
     const float* sig_q2, const float* sig_f, const float* sig_g, const float* mu2, const float* m0, const float* sig0,
     const float* fm0, const float* fsig0, const float* obs, const float* eps, const float* X, const float* Fm,
-    const float* P1, const float* logW, const float* lse, const int32_t* idx, const float* dlse, float* dP, float* dF,
-    float* dG, float* dmu2, float* dm0, float* dfm0, float* dsig_q1, float* dsig_q2, float* dsig_f, float* dsig_g,
-    float* dsig0, float* dfsig0, float* ws, void* stream) {
+    const float* P1, const float* logW, const float* lse, const int32_t* idx, const float* dlse, int nparts,
+    const float* dFm_ext, const float* dlogW_ext, float* dP, float* dF, float* dG, float* dmu2, float* dm0, float* dfm0,
+    float* dsig_q1, float* dsig_q2, float* dsig_f, float* dsig_g, float* dsig0, float* dfsig0, float* ws, void* stream) {
     using namespace psvo;
     using namespace psvo::wobs;
     if (!desc || !q1 || !g || !sig_q1 || !sig_g || !m0 || !sig0 || !fm0 || !fsig0 || !obs || !eps || !X || !Fm || !logW ||
@@ -1067,6 +1001,7 @@ extern "C" int psvo_filter_backward_wobs(
     if (desc->two_q && (!mu2 || !sig_q2 || !dmu2)) return PSVO_ERR_INVALID;
     if (!desc->bootstrap && (!f || !sig_f || !P1 || !dF)) return PSVO_ERR_INVALID;
     if (desc->resample && !idx) return PSVO_ERR_INVALID;
+    if ((dFm_ext || dlogW_ext) && nparts <= 0) return PSVO_ERR_INVALID;
     if (!filter_shape_ok(desc)) return PSVO_ERR_UNSUPPORTED;
 
     BwdArgs a;
@@ -1076,12 +1011,25 @@ extern "C" int psvo_filter_backward_wobs(
     a.sig_q1 = sig_q1; a.sig_q2 = sig_q2; a.sig_f = sig_f; a.sig_g = sig_g;
     a.mu2 = mu2; a.m0 = m0; a.sig0 = sig0; a.fm0 = fm0; a.fsig0 = fsig0; a.obs = obs; a.eps = eps;
     a.X = X; a.Fm = Fm; a.P1 = P1; a.logW = logW; a.lse = lse; a.idx = idx; a.dlse = dlse;
+    a.nparts = nparts; a.dFm_ext = dFm_ext; a.dlogW_ext = dlogW_ext;
     a.dP = dP; a.dF = dF; a.dG = dG; a.dmu2 = dmu2; a.dm0 = dm0; a.dfm0 = dfm0;
     a.sacc = ws;
     a.dm2_rows = ws + (long long)desc->B * (10 * desc->Dx + desc->Dy);
     BwdOut o{dsig_q1, dsig_q2, dsig_f, dsig_g, dsig0, dfsig0};
     hipStream_t s = static_cast<hipStream_t>(stream);
     return dispatch_dx_h(desc->Dx, desc->H, [&](auto dx, auto h) { return launch_bwd<dx(), h()>(a, o, s); });
+}
+
+extern "C" int psvo_filter_backward_wobs(
+    const psvo_desc* desc, const psvo_mlp* q1, const psvo_mlp* f, const psvo_mlp* g, const float* sig_q1,
+    const float* sig_q2, const float* sig_f, const float* sig_g, const float* mu2, const float* m0, const float* sig0,
+    const float* fm0, const float* fsig0, const float* obs, const float* eps, const float* X, const float* Fm,
+    const float* P1, const float* logW, const float* lse, const int32_t* idx, const float* dlse, float* dP, float* dF,
+    float* dG, float* dmu2, float* dm0, float* dfm0, float* dsig_q1, float* dsig_q2, float* dsig_f, float* dsig_g,
+    float* dsig0, float* dfsig0, float* ws, void* stream) {
+    return psvo_filter_backward_wobs_ext(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, fm0, fsig0, obs, eps, X, Fm,
+                                         P1, logW, lse, idx, dlse, 0, nullptr, nullptr, dP, dF, dG, dmu2, dm0, dfm0, dsig_q1,
+                                         dsig_q2, dsig_f, dsig_g, dsig0, dfsig0, ws, stream);
 }
 
 extern "C" int psvo_mlp_wgrad_wobs_blocks(long long rows) {

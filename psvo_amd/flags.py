@@ -62,6 +62,8 @@ DEFINITIONS = [
     ("IWAE", bool, False, "Importance Weighted Auto-Encoder"),
     ("n_particles_for_BSim_proposal", int, 16, "sub-particles per trajectory in backward simulation proposal"),
     ("BSim_use_single_RNN", bool, False, "backward simulation proposal uses unidirectional RNN"),
+    # (not in the reference's registry) PSVO on observations wider than two: the wide filter, then the wide backward simulation
+    ("BSim_wide_obs", bool, False, "PSVO: run 3 <= Dy <= 32 on the wide-observation backward-simulation kernels"),
     # training (runner_flag.py:118-127)
     ("early_stop_patience", int, 200, "stop training early if validation set does not improve"),
     ("lr_reduce_patience", int, 30, "reduce learning rate when testing loss doesn't improve"),

@@ -289,8 +289,8 @@ def _bsim_wgrad(out, desc, f, g, q1_inv, x_next, gb):
 
 
 def bsim_forward(desc, filt, f, g, q1_inv, sig_f, sig_g, sig_q1inv, sig_bq2, bmu2, minit, sig_init,
-                 imean, isig, obs, eps_b, u_b=None, sel_in=None, save=False):
-    """psvo_bsim_forward.  `filt` is the dict returned by filter_forward.
+                 imean, isig, obs, eps_b, u_b=None, sel_in=None, save=False, entry="psvo_bsim_forward"):
+    """psvo_bsim_forward (`entry`: an entry point with the same contract).  `filt` is the dict returned by filter_forward.
     Returns dict(bwX, flp, glp, Omega, sel, score)."""
     lib = _lib.load()
     B, T, N, Dx = desc.B, desc.T, desc.N, desc.Dx
@@ -303,17 +303,23 @@ def bsim_forward(desc, filt, f, g, q1_inv, sig_f, sig_g, sig_q1inv, sig_bq2, bmu
     z = lambda *s: _empty(*s, device=dev)
     out = {"bwX": z(T, B, Dx, N), "flp": z(T, B, N), "glp": z(T, B, N), "Omega": z(T, B, N),
            "sel": _empty(T, B, N, device=dev, dtype=torch.int32), "score": z(B, N), **_bsim_saves(desc, dev, save)}
-    _mark("psvo_bsim_forward", 0)
-    st = lib.psvo_bsim_forward(
+    _mark(entry, 0)
+    st = getattr(lib, entry)(
         ctypes.byref(desc), _ptr(filt["X"]), _ptr(filt["Fm"]), _ptr(filt["logW"]), _ptr(filt["lse"]),
         ctypes.byref(fs), ctypes.byref(gs), ctypes.byref(qs),
         _ptr(sig_f), _ptr(sig_g), _ptr(sig_q1inv), _ptr(sig_bq2), _ptr(bmu2), _ptr(minit), _ptr(sig_init),
         _ptr(imean), _ptr(isig), _ptr(obs), _ptr(eps_b), _ptr(u_b), _ptr(sel_in),
         _ptr(out["bwX"]), _ptr(out["flp"]), _ptr(out["glp"]), _ptr(out["Omega"]), _ptr(out["sel"]),
         _ptr(out["score"]), _ptr(out["lam2"]), _ptr(out["om"]), _ptr(out["mu1"]), _stream())
-    _mark("psvo_bsim_forward", 1)
-    _lib.check(st, "psvo_bsim_forward")
+    _mark(entry, 1)
+    _lib.check(st, entry)
     return out
+
+
+def bsim_forward_wobs(*args, **kw):
+    """psvo_bsim_forward_wobs: the backward simulation for wide observations (3 <= Dy <= 32, one hidden layer); arguments,
+    outputs and layouts of bsim_forward."""
+    return bsim_forward(*args, entry="psvo_bsim_forward_wobs", **kw)
 
 
 def elbo_filter(desc, lse):
@@ -497,27 +503,32 @@ def split_mlp_grad(g, Din, H, Dout, layers=1):
 
 
 def filter_backward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, fm0, fsig0, obs, eps, filt,
-                    dlse=None, dFm=None, dlogW=None, gbufs=None, before_wgrad=None, defer_wgrad=False, wobs=False):
+                    dlse=None, dFm=None, dlogW=None, gbufs=None, before_wgrad=None, defer_wgrad=False, wobs=False,
+                    nparts=None, ext=False):
     """psvo_filter_backward + psvo_mlp_wgrad.  `filt` = forward outputs.  dFm (T,B,Dx,N) / dlogW (T,B,N)
-    are upstream gradients (or None).  Returns a dict of gradients.
-    wobs: psvo_filter_backward_wobs + psvo_mlp_wgrad_wobs for MLP_g (wide observations; upstream gradient dlse only)."""
+    are upstream gradients (or None); with nparts > 1 they come in parts, (T,B,nparts,Dx,N) / (T,B,nparts,N), which the
+    kernel adds in part order.  Returns a dict of gradients.
+    wobs: psvo_filter_backward_wobs + psvo_mlp_wgrad_wobs for MLP_g (wide observations); with dFm / dlogW -- a backward
+    simulation ran behind the wide filter -- or with ext=True, psvo_filter_backward_wobs_ext."""
     lib = _lib.load()
     B, T, N, Dx, Dy, H = desc.B, desc.T, desc.N, desc.Dx, desc.Dy, desc.H
     dev = eps.device
     q1s = _mlp_struct(q1, Dx, H, Dx, "q1")
     fs = None if desc.bootstrap else _mlp_struct(f, Dx, H, Dx, "f")
     gs = _mlp_struct(g, Dx, H, Dy, "g")
-    _chk(dlse, (T, B), "dlse"); _chk(dFm, (T, B, Dx, N), "dFm"); _chk(dlogW, (T, B, N), "dlogW")
+    if not wobs and (ext or nparts is not None):
+        raise ValueError("filter_backward: `nparts` / `ext` belong to the wide-observation route (wobs=True)")
+    parts = () if nparts in (None, 1) else (int(nparts),)
+    _chk(dlse, (T, B), "dlse"); _chk(dFm, (T, B) + parts + (Dx, N), "dFm"); _chk(dlogW, (T, B) + parts + (N,), "dlogW")
     z = lambda *s: _empty(*s, device=dev)
     out = {"dP": z(T, B, Dx, N), "dF": None if desc.bootstrap else z(T, B, Dx, N), "dG": z(T, B, Dy, N),
            "dmu2": z(T, B, Dx) if desc.two_q else None, "dm0": z(B, Dx), "dfm0": z(B, Dx),
            "dsig_q1": z(Dx), "dsig_q2": z(Dx), "dsig_f": z(Dx), "dsig_g": z(Dy), "dsig0": z(Dx), "dfsig0": z(Dx)}
-    name = "psvo_filter_backward_wobs" if wobs else "psvo_filter_backward"
-    if wobs and (dFm is not None or dlogW is not None):
-        raise ValueError("%s takes the upstream gradient of lse only (no backward simulation behind a wide filter)" % name)
+    nparts = (parts[0] if parts else 1) if (dFm is not None or dlogW is not None) else 0
+    ext = bool(ext or nparts)
+    name = ("psvo_filter_backward_wobs_ext" if ext else "psvo_filter_backward_wobs") if wobs else "psvo_filter_backward"
     sacc = z((lib.psvo_filter_wobs_ws_floats if wobs else lib.psvo_filter_ws_floats)(B, T, N, Dx, Dy))
-    nparts = 1 if (dFm is not None or dlogW is not None) else 0
-    upstream = (_ptr(dlse),) if wobs else (_ptr(dlse), nparts, _ptr(dFm), _ptr(dlogW))
+    upstream = (_ptr(dlse),) if (wobs and not ext) else (_ptr(dlse), nparts, _ptr(dFm), _ptr(dlogW))
     _mark(name, 0)
     with _fixed_order():
         st = getattr(lib, name)(
@@ -558,7 +569,7 @@ def filter_backward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0,
 
 def filter_backward_wobs(*args, **kw):
     """psvo_filter_backward_wobs + psvo_mlp_wgrad (q1, f) + psvo_mlp_wgrad_wobs (g): the reverse of filter_forward_wobs;
-    arguments and result of filter_backward without dFm / dlogW."""
+    arguments and result of filter_backward (dFm / dlogW given: psvo_filter_backward_wobs_ext)."""
     return filter_backward(*args, wobs=True, **kw)
 
 
@@ -962,6 +973,46 @@ def bsim_backward(desc, filt, f, g, q1_inv, sig_f, sig_g, sig_q1inv, sig_bq2, bm
         return out
     with _wgrad_on(wgrad_stream if gbufs is not None else None):
         wgrad()
+    return out
+
+
+def bsim_backward_wobs(desc, filt, f, g, q1_inv, sig_f, sig_g, sig_q1inv, sig_bq2, bmu2, minit, sig_init, imean, isig,
+                       obs, eps_b, bs, dscore):
+    """psvo_bsim_backward_wobs + psvo_mlp_wgrad (f, q1_inv) + psvo_mlp_wgrad_wobs (g): the reverse of bsim_forward_wobs.
+    `bs` = bsim_forward_wobs(..., save=True) outputs.  One stream; the result has bsim_backward's keys (no partials: the
+    entry point folds them itself)."""
+    lib = _lib.load()
+    B, T, N, M, Dx, Dy, H = desc.B, desc.T, desc.N, desc.M, desc.Dx, desc.Dy, desc.H
+    dev = eps_b.device
+    fs, gs, qs = _bsim_structs(desc, f, g, q1_inv)
+    _bsim_chk(desc, filt, sig_f, sig_g, sig_q1inv, sig_bq2, bmu2, minit, sig_init, imean, isig, obs, eps_b, None, None)
+    _chk(dscore, (B, N), "dscore")
+    _bsim_chk_saves(desc, bs, "bsim", (("bwX", (T, B, Dx, N)),))
+    _chk(bs["sel"], (T, B, N), "sel", torch.int32)
+    z = lambda *s: _empty(*s, device=dev)
+    out = {"xt": z(T, B, Dx, N, M), "dFt": z(T, B, Dx, N, M), "dGt": z(T, B, Dy, N, M), "dmu1": z(T, B, Dx, N),
+           "dFm": z(T, B, Dx, N), "dlogW": z(T, B, N), "dlse": z(T, B),
+           "dsig_f": z(Dx), "dsig_g": z(Dy), "dsig_q1inv": z(Dx), "dsig_bq2": z(Dx), "dsig_init": z(Dx), "disig": z(Dx)}
+    _chain_rows(out, z, T, B, Dx, N)
+    ws = z(max(1, lib.psvo_bsim_wobs_ws_floats(B, T, N, M, Dx, Dy)))
+    _mark("psvo_bsim_backward_wobs", 0)
+    st = lib.psvo_bsim_backward_wobs(
+        ctypes.byref(desc), _ptr(filt["Fm"]), _ptr(filt["logW"]), _ptr(filt["lse"]),
+        ctypes.byref(fs), ctypes.byref(gs), ctypes.byref(qs),
+        _ptr(sig_f), _ptr(sig_g), _ptr(sig_q1inv), _ptr(sig_bq2), _ptr(bmu2), _ptr(minit), _ptr(sig_init),
+        _ptr(imean), _ptr(isig), _ptr(obs), _ptr(eps_b), _ptr(bs["bwX"]), _ptr(bs["sel"]),
+        _ptr(bs["lam2"]), _ptr(bs["om"]), _ptr(bs["mu1"]), _ptr(dscore),
+        _ptr(out["xt"]), _ptr(out["dFt"]), _ptr(out["dGt"]), _ptr(out["dmu1"]),
+        _ptr(out["dbmu2_rows"]), _ptr(out["dminit_rows"]), _ptr(out["dimean_rows"]),
+        _ptr(out["dFm"]), _ptr(out["dlogW"]), _ptr(out["dlse"]),
+        _ptr(out["dsig_f"]), _ptr(out["dsig_g"]), _ptr(out["dsig_q1inv"]), _ptr(out["dsig_bq2"]), _ptr(out["dsig_init"]),
+        _ptr(out["disig"]), _ptr(ws), _stream())
+    _mark("psvo_bsim_backward_wobs", 1)
+    _lib.check(st, "psvo_bsim_backward_wobs")
+    # weight gradients from rows: MLP_g's through the wide-output kernel with L = N M rows per (t, b) segment
+    out["gf"] = mlp_wgrad(out["xt"][:T - 1], out["dFt"][:T - 1], f, Dx, H, Dx)
+    out["gg"] = mlp_wgrad(out["xt"], out["dGt"], g, Dx, H, Dy, wobs=True)
+    out["gq1inv"] = mlp_wgrad(bs["bwX"][1:], out["dmu1"][:T - 1], q1_inv, Dx, H, Dx)
     return out
 
 
