@@ -67,7 +67,11 @@ typedef struct {
     int32_t emission;   /* 0: g = N(MLP_g(x), sig_g) (tf_mvn).  1: FLAGS.poisson_emission -- the
                            reference's tf_poisson (src/distribution/poisson.py:27-50) is a UNIT-scale
                            normal whose mean is softplus(MLP_g(x)) + 1e-6: pass sig_g = ones; the
-                           dsig_g output is then meaningless                                    */
+                           dsig_g output is then meaningless.
+                           2: the count emission, a Poisson law per output -- wide-observation entry
+                           points only (see "Count emission" below); sig_g as for 1.
+                           Any other value: PSVO_ERR_UNSUPPORTED from every entry point that reads the
+                           field, ahead of its pointer checks ({0, 1} outside the wide entry points)  */
     int32_t layers;     /* hidden layers of ALL per-particle MLPs of the call: 0 or 1 = one (psvo_mlp.Wh / bh
                            ignored), 2 = two layers of width H each (FLAGS.q1_layers="64,64" ...,
                            src/transformation/MLP.py:24-38,50-54).  An MLP with fewer layers than the others
@@ -607,8 +611,20 @@ int psvo_filter_backward(const psvo_desc* desc,
  * (SVO, AESMC, IWAE); PSVO's backward simulation has its own wide entry points further down, PSVOwR's stays at Dy <= 2.
  * Envelope of the two filter entry points: 3 <= Dy <= 32 (a run-time bound, nothing is instantiated per width), Dx in {2,3,4},
  * H in {16,32,64} (narrower: zero-padded by the caller as above), N <= 512, one hidden layer (desc->layers <= 1), Gaussian and
- * Poisson emission, every bootstrap / two_q wiring, resampling on or off.  Anything else -- Dy <= 2 and Dy > 32 included --
- * returns PSVO_ERR_UNSUPPORTED before a device is touched.
+ * Poisson emission and the count emission, every bootstrap / two_q wiring, resampling on or off.  Anything else -- Dy <= 2 and
+ * Dy > 32 included -- returns PSVO_ERR_UNSUPPORTED before a device is touched.
+ *
+ * Count emission (desc->emission = 2; the wide entry points of this section and of the next, in their whole envelope).  With
+ * r = MLP_g(x) and lam_e = softplus(r_e) + 1e-6 (the mean of emission 1, threshold 20):
+ *     log g(y | x) = sum_{e = 0 .. Dy-1} [ y_e log lam_e - lam_e - log Gamma(y_e + 1) ]        (terms added in the order e = 0 .. Dy-1)
+ *     d log g / d r_e = (y_e / lam_e - 1) * sigmoid(r_e)
+ *   The log Gamma(y_e + 1) term is part of logW, lse, glp and so of the ELBO, which is then a Poisson log-likelihood bound.  It
+ *   is computed once per (step, sequence, output) by the lanes that stage the observation row -- in fp64, rounded once: the
+ *   fp32 nearest to the true value for every integer y, exactly 0 for y in {0, 1} -- and travels with the row through LDS.
+ *   sig_g: pass ones (not read); dsig_g comes back as zeros.  Observations must be finite, non-negative and integer-valued;
+ *   the caller checks that (psvo_amd/runner.py: check_counts).  For anything else the result is unspecified, but nothing is
+ *   addressed with an observation's value: no read or write leaves its buffer.  psvo_mlp_wgrad_wobs consumes the d G rows as
+ *   before.  Every other entry point that reads desc->emission answers PSVO_ERR_UNSUPPORTED for emission = 2.
  *
  * psvo_filter_forward_wobs: arguments, outputs, layouts and the draw rule of psvo_filter_forward (idx = the number of CDF
  *   entries <= u * total, clamped to N - 1; or teacher-forced idx_in), so that psvo_elbo_filter, psvo_ffbs_smooth and the host
@@ -658,7 +674,7 @@ int psvo_mlp_wgrad_wobs(long long S, int L, int Din, int H, int Dout, const floa
  * PSVO_ERR_UNSUPPORTED for Dy = 3, and psvo_filter_backward_wobs keeps its signature and its results bit for bit.
  * Envelope of the two backward-simulation entry points: 3 <= Dy <= 32 (a run-time bound, nothing is instantiated per width),
  * Dx in {2,3,4}, H in {16,32,64}, M in {4,8,16,32}, N <= 512, one hidden layer (desc->layers in {0, 1}), state-independent
- * scales, Gaussian and Poisson emission.  A missing required pointer, B <= 0, T < 2 or N <= 0 is PSVO_ERR_INVALID whatever the
+ * scales, Gaussian and Poisson emission and the count emission (desc->emission = 2, above).  A missing required pointer, B <= 0, T < 2 or N <= 0 is PSVO_ERR_INVALID whatever the
  * shape; anything else outside the envelope is PSVO_ERR_UNSUPPORTED; both come back before a device is touched.
  *
  * psvo_bsim_forward_wobs: contract, argument list, outputs and layouts of psvo_bsim_forward (bwX, flp, glp, Omega, sel_out,

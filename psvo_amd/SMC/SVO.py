@@ -55,6 +55,16 @@ class SVO:
         backward simulation on psvo_bsim_forward_wobs / psvo_bsim_backward_wobs.  What those kernels do not cover is refused
         here, up front.  Without the flag PSVO stays refused: making it the default is a one-line change here."""
         Dy = getattr(model, "Dy", cls._PLAIN_DY)          # (a bare model object without widths has nothing to route)
+        if getattr(model, "count_emission", False):
+            # the count emission (psvo_desc.emission = 2) exists in the wide-observation kernels only
+            if getattr(model, "poisson_emission", False):
+                raise ValueError("--count_emission with --poisson_emission: one emission at a time -- count_emission is the "
+                                 "Poisson likelihood of counts, poisson_emission the reference's unit-scale normal around "
+                                 "the rate")
+            if Dy <= cls._PLAIN_DY:
+                raise ValueError("--count_emission with Dy = %d: the count emission runs on the wide-observation kernels, which "
+                                 "take 3 <= Dy <= %d; the plain kernels (Dy <= %d) have no count form"
+                                 % (Dy, cls._WOBS_MAX_DY, cls._PLAIN_DY))
         if Dy <= cls._PLAIN_DY:
             return False
         limit = "observations wider than Dy = %d run on the wide-observation filter kernels" % cls._PLAIN_DY
@@ -261,7 +271,8 @@ class SVO:
         return ops.make_desc(self.batch_size, self.time, self.n_particles, M, self.model.Dx, self.model.Dy, H,
                              resample=self.resample_particles, two_q=self.model.use_2_q,
                              bootstrap=self.model.use_bootstrap,
-                             emission=int(getattr(self.model, "poisson_emission", False)),
+                             emission=(2 if getattr(self.model, "count_emission", False)
+                                       else int(getattr(self.model, "poisson_emission", False))),
                              layers=self._kernel_width()[2])
 
     def _randn(self, *shape, device):

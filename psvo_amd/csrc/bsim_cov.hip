@@ -1140,7 +1140,7 @@ static bool all_set(const BwdIo& p) {
 // Status of the arguments every entry point checks, in the order tests/test_abi.py pins.  ptrs_ok: its required pointers are set
 static int check_args(const psvo_desc* desc, bool ptrs_ok) {
     if (!desc) return PSVO_ERR_INVALID;
-    if (desc->layers > 1 || desc->layers < 0) return PSVO_ERR_UNSUPPORTED;
+    if (desc->layers > 1 || desc->layers < 0 || !desc_emission_ok(desc)) return PSVO_ERR_UNSUPPORTED;
     if (desc->B <= 0 || desc->T < 2 || desc->N <= 0 || desc->M <= 0 || !ptrs_ok) return PSVO_ERR_INVALID;
     if (desc->N > 1024 || desc->B > 65535) return PSVO_ERR_UNSUPPORTED;
     return PSVO_OK;

@@ -71,7 +71,9 @@ struct FwdArgs {
     float *lam2_all, *om_all, *mu1_all;
 };
 
-template <int DX, int H, int M>
+// CNT: the count emission (psvo_desc.emission = 2), a compile-time form as in filter_wobs.hip: 1 / sig_g is not used and the
+// log-factorial row of a step travels with its observation row
+template <int DX, int H, int M, bool CNT>
 __global__ void __launch_bounds__(256) bsim_wobs_fwd_kernel(const FwdArgs a) {
     using MQ = MlpLds<DX, H, DX, 1>;
     using MG = GLds<DX, H>;
@@ -97,13 +99,16 @@ __global__ void __launch_bounds__(256) bsim_wobs_fwd_kernel(const FwdArgs a) {
     float* isg = wg + MG::kSize;        // [kMaxDy] 1 / sig_g
     float* ybuf = isg + kMaxDy;         // [2][kMaxDy] observation rows of step t (t & 1) and t - 1
     float* tile = ybuf + 2 * kMaxDy;    // [2][NP][TS]
+    float* lfbuf = tile + 2 * NP * TS;  // CNT: [2][kMaxDy] log Gamma(y + 1) of the rows in ybuf
 
     MQ::load(wf, a.f, tid, NTB);
     MQ::load(wqi, a.q1inv, tid, NTB);
     MG::load(wg, a.g, Dy, tid, NTB);
     if (tid < Dy) {
-        isg[tid] = 1.f / a.sig_g[tid];
-        ybuf[((T - 1) & 1) * kMaxDy + tid] = a.obs[((size_t)(T - 1) * B + b) * Dy + tid];
+        if constexpr (!CNT) isg[tid] = 1.f / a.sig_g[tid];
+        const float y0 = a.obs[((size_t)(T - 1) * B + b) * Dy + tid];
+        ybuf[((T - 1) & 1) * kMaxDy + tid] = y0;
+        if constexpr (CNT) lfbuf[((T - 1) & 1) * kMaxDy + tid] = wobs::log_factorial(y0);
     }
 
     // ---- constants (bsim_fwd.hip) --------------------------------------------------------------------------------------
@@ -118,7 +123,9 @@ __global__ void __launch_bounds__(256) bsim_wobs_fwd_kernel(const FwdArgs a) {
         kf -= logf(s);
     }
     float lg = -Dy * kHalfLog2Pi;
-    for (int e = 0; e < Dy; ++e) lg -= logf(a.sig_g[e]);
+    if constexpr (!CNT) {
+        for (int e = 0; e < Dy; ++e) lg -= logf(a.sig_g[e]);
+    }
     float pc[DX], pic[DX], pi1[DX], pi2[DX];
     float kq = -DX * kHalfLog2Pi;
 #pragma unroll
@@ -256,14 +263,21 @@ __global__ void __launch_bounds__(256) bsim_wobs_fwd_kernel(const FwdArgs a) {
             float h[H];
             MG::hidden(wg_t, x, h);
             float acc = 0.f;
+            if constexpr (CNT) {     // y log lam - lam - log Gamma(y + 1), one term per output
+                const float* lf_t = lfbuf + (t & 1) * kMaxDy + zo;
 #pragma unroll 1
-            for (int e = 0; e < Dy; ++e) {
-                float gm = MG::out(wg_t, e, h);
-                if (a.emission) gm = emis_mean(gm);
-                const float z = (y_t[e] - gm) * isg[e];
-                acc = fmaf(z, z, acc);
+                for (int e = 0; e < Dy; ++e) acc += wobs::count_term(y_t[e], MG::out(wg_t, e, h)) - lf_t[e];
+                g_lp = acc;
+            } else {
+#pragma unroll 1
+                for (int e = 0; e < Dy; ++e) {
+                    float gm = MG::out(wg_t, e, h);
+                    if (a.emission) gm = emis_mean(gm);
+                    const float z = (y_t[e] - gm) * isg[e];
+                    acc = fmaf(z, z, acc);
+                }
+                g_lp = fmaf(-0.5f, acc, lg);
             }
-            g_lp = fmaf(-0.5f, acc, lg);
         }
 
         // ---- filter term: logsumexp_j( log f(x~ | X_{t-1}[j]) + W^_{t-1}[j] ), online in the log2 domain -----------------
@@ -345,24 +359,30 @@ __global__ void __launch_bounds__(256) bsim_wobs_fwd_kernel(const FwdArgs a) {
         sel_c = sel_n;
         if (t >= 2) stage_store(nxt);
         // the prefetched observation row goes to the half of ybuf that step t + 1 read (behind the barrier that ended it)
-        if (!tzero && tid < Dy) ybuf[((t - 1) & 1) * kMaxDy + tid] = y_n;
+        if (!tzero && tid < Dy) {
+            ybuf[((t - 1) & 1) * kMaxDy + tid] = y_n;
+            if constexpr (CNT) lfbuf[((t - 1) & 1) * kMaxDy + tid] = wobs::log_factorial(y_n);
+        }
         __syncthreads();
     }
     if (valid && lead) a.score[(size_t)b * N + n] = score;
 }
 
 template <int DX, int H>
-static size_t fwd_lds_bytes(int N) {
+static size_t fwd_lds_bytes(int N, bool count) {
     const int NP = (N + 7) & ~7;
-    return sizeof(float) * (2 * MlpLds<DX, H, DX, 1>::kSize + GLds<DX, H>::kSize + 3 * kMaxDy + 2 * (size_t)NP * (DX + 1));
+    return sizeof(float) * (2 * MlpLds<DX, H, DX, 1>::kSize + GLds<DX, H>::kSize + 3 * kMaxDy + 2 * (size_t)NP * (DX + 1) +
+                            (count ? 2 * kMaxDy : 0));
 }
 
 template <int DX, int H, int M>
 static int launch_fwd(const FwdArgs& a, hipStream_t stream) {
     const Geom ge = geometry(a.N, M);
-    const size_t lds = fwd_lds_bytes<DX, H>(a.N);
+    const bool count = a.emission == 2;
+    const size_t lds = fwd_lds_bytes<DX, H>(a.N, count);
     clear_hip_error();
-    hipLaunchKernelGGL((bsim_wobs_fwd_kernel<DX, H, M>), dim3(ge.nblk, a.B), dim3(ge.ntb), lds, stream, a);
+    if (count) hipLaunchKernelGGL((bsim_wobs_fwd_kernel<DX, H, M, true>), dim3(ge.nblk, a.B), dim3(ge.ntb), lds, stream, a);
+    else hipLaunchKernelGGL((bsim_wobs_fwd_kernel<DX, H, M, false>), dim3(ge.nblk, a.B), dim3(ge.ntb), lds, stream, a);
     return launch_status();
 }
 
@@ -385,7 +405,8 @@ struct BwdArgs {
     float *dFm_part, *dlogW_part, *sacc_part;     // workspace: (T,B,nblk,Dx,N), (T,B,nblk,N), (B,nblk,7 Dx + Dy)
 };
 
-template <int DX, int H, int M>
+// CNT: the count emission; its d G rows are d g_m (y / lam - 1) sigmoid(r), there is no d sig_g
+template <int DX, int H, int M, bool CNT>
 __global__ void __launch_bounds__(256) bsim_wobs_bwd_kernel(const BwdArgs a) {
     using MQ = MlpLds<DX, H, DX, 1>;
     using MG = GLds<DX, H>;
@@ -427,10 +448,12 @@ __global__ void __launch_bounds__(256) bsim_wobs_bwd_kernel(const BwdArgs a) {
     MQ::load(wqi, a.q1inv, tid, NTB);
     MG::load(wg, a.g, Dy, tid, NTB);
     if (tid < Dy) {
-        isg[tid] = 1.f / a.sig_g[tid];
+        if constexpr (!CNT) isg[tid] = 1.f / a.sig_g[tid];
         ybuf[tid] = a.obs[(size_t)b * Dy + tid];
     }
-    for (int e = 0; e < Dy; ++e) sg[e * NTB + tid] = 0.f;
+    if constexpr (!CNT) {
+        for (int e = 0; e < Dy; ++e) sg[e * NTB + tid] = 0.f;
+    }
 
     // ---- constants (bsim_bwd_impl.h).  Wave-uniform values would live in SGPRs beside some thirty array pointers, more than
     // a wave has: the constants sit in LDS and are read where they are used, the pointers are re-read from the kernel
@@ -553,15 +576,23 @@ __global__ void __launch_bounds__(256) bsim_wobs_bwd_kernel(const BwdArgs a) {
         {
             float h[H];
             MG::hidden(wg_t, x, h);
+            if constexpr (CNT) {
 #pragma unroll 1
-            for (int o = 0; o < Dy; ++o) {
-                float gm = MG::out(wg_t, o, h);
-                float dmean = 1.f;
-                if (a.emission) { dmean = emis_dmean(gm); gm = emis_mean(gm); }
-                const float is = isg[o];
-                const float z = (y_t[o] - gm) * is;
-                sg[o * NTB + tid] += dphi * (z * z - 1.f) * is;
-                if (valid) dGrow[o * gstride] = dphi * z * is * dmean;
+                for (int o = 0; o < Dy; ++o) {
+                    const float dr = dphi * wobs::count_dterm(y_t[o], MG::out(wg_t, o, h));
+                    if (valid) dGrow[o * gstride] = dr;
+                }
+            } else {
+#pragma unroll 1
+                for (int o = 0; o < Dy; ++o) {
+                    float gm = MG::out(wg_t, o, h);
+                    float dmean = 1.f;
+                    if (a.emission) { dmean = emis_dmean(gm); gm = emis_mean(gm); }
+                    const float is = isg[o];
+                    const float z = (y_t[o] - gm) * is;
+                    sg[o * NTB + tid] += dphi * (z * z - 1.f) * is;
+                    if (valid) dGrow[o * gstride] = dphi * z * is * dmean;
+                }
             }
         }
         // (second walk over the outputs: the lane reads its own d G row back, hidden units in chunks)
@@ -784,9 +815,11 @@ __global__ void __launch_bounds__(256) bsim_wobs_bwd_kernel(const BwdArgs a) {
         if (tid == 0) dst[i] = s;
     }
     __syncthreads();
-    if (tid < Dy) {
+    if (tid < Dy) {      // (count emission: no scale, zeros)
         float s = 0.f;
-        for (int i = 0; i < NTB; ++i) s += sg[tid * NTB + i];
+        if constexpr (!CNT) {
+            for (int i = 0; i < NTB; ++i) s += sg[tid * NTB + i];
+        }
         dst[AC::kSg + tid] = s;
     }
 }
@@ -874,7 +907,8 @@ static int launch_bwd(const BwdArgs& a, const BwdOut& o, hipStream_t stream) {
     const size_t lds = bwd_lds_bytes<DX, H>(a.N, ge.ntb, a.Dy);
     if (lds > 160 * 1024) return PSVO_ERR_UNSUPPORTED;
     clear_hip_error();
-    hipLaunchKernelGGL((bsim_wobs_bwd_kernel<DX, H, M>), dim3(ge.nblk, a.B), dim3(ge.ntb), lds, stream, a);
+    if (a.emission == 2) hipLaunchKernelGGL((bsim_wobs_bwd_kernel<DX, H, M, true>), dim3(ge.nblk, a.B), dim3(ge.ntb), lds, stream, a);
+    else hipLaunchKernelGGL((bsim_wobs_bwd_kernel<DX, H, M, false>), dim3(ge.nblk, a.B), dim3(ge.ntb), lds, stream, a);
     const long long TB = (long long)a.T * a.B;
     const long long nel = TB * (DX + 1) * a.N;
     const unsigned nfold = (unsigned)((nel + 255) / 256), nrow = (unsigned)((TB + 3) / 4);
@@ -933,6 +967,7 @@ extern "C" int psvo_bsim_forward_wobs(const psvo_desc* desc, const float* X, con
                                       void* stream) {
     using namespace psvo;
     using namespace psvo::wbs;
+    if (!desc_emission_ok(desc, 2)) return PSVO_ERR_UNSUPPORTED;
     if (!desc || !Fm || !logW || !lse || !f || !g || !q1_inv || !sig_f || !sig_g || !sig_q1inv || !sig_bq2 || !bmu2 ||
         !minit || !sig_init || !imean || !isig || !obs || !eps_b || !bwX || !flp || !glp || !Omega || !sel_out || !score)
         return PSVO_ERR_INVALID;
@@ -964,6 +999,7 @@ extern "C" int psvo_bsim_backward_wobs(
     float* dsig_q1inv, float* dsig_bq2, float* dsig_init, float* disig, float* ws, void* stream) {
     using namespace psvo;
     using namespace psvo::wbs;
+    if (!desc_emission_ok(desc, 2)) return PSVO_ERR_UNSUPPORTED;
     if (!desc || !Fm || !logW || !lse || !f || !g || !q1_inv || !sig_f || !sig_g || !sig_q1inv || !sig_bq2 || !bmu2 ||
         !minit || !sig_init || !imean || !isig || !obs || !eps_b || !bwX || !sel || !lam2_all || !om_all || !mu1_all ||
         !dscore || !xt || !dFt || !dGt || !dmu1 || !dbmu2_rows || !dminit_rows || !dimean_rows || !dFm || !dlogW || !dlse ||

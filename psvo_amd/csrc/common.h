@@ -47,6 +47,13 @@ inline int launch_status() {
 // shorter struct leaves there) is refused loudly by every entry point instead of silently running the one-layer kernels
 inline bool desc_layers_ok(const psvo_desc* d) { return !d || (d->layers >= 0 && d->layers <= 2); }
 
+// psvo_desc.emission: 0 = Gaussian, 1 = the reference's unit-scale normal around softplus + 1e-6, 2 = the count (Poisson)
+// emission, which only the wide-observation entry points have (max_emission = 2 there).  Anything else is refused like a bad
+// `layers`: no entry point runs another emission's kernels by default
+inline bool desc_emission_ok(const psvo_desc* d, int max_emission = 1) {
+    return !d || (d->emission >= 0 && d->emission <= max_emission);
+}
+
 // PSVO_TUNE_L2_SPLIT (psvo_set_tuning): two-layer builds of the backward-simulation kernels -- 0 (default): one lane per
 // (chain, m) whatever the problem size, 1: spread a chain over 2 M lanes when that gives two waves per SIMD, as the one-layer
 // builds do.  (With the H x H layer on the matrix pipe a second wave per SIMD shares that pipe and the per-row overheads

@@ -1163,7 +1163,7 @@ extern "C" int psvo_filter_forward_cov(const psvo_desc* desc, const psvo_mlp* q1
     using namespace psvo;
     using namespace psvo::cov;
     if (!desc_ok(desc)) return PSVO_ERR_INVALID;
-    if (desc->layers > 1 || desc->layers < 0) return PSVO_ERR_UNSUPPORTED;
+    if (desc->layers > 1 || desc->layers < 0 || !desc_emission_ok(desc)) return PSVO_ERR_UNSUPPORTED;
     if (!q1 || !g || !sigc_q1 || !sigc_g || !m0 || !sig0 || !fm0 || !fsig0 || !obs || !eps || !X || !Xanc || !Fm || !Fs ||
         !logW || !idx_out || !lse)
         return PSVO_ERR_INVALID;
@@ -1195,7 +1195,7 @@ extern "C" int psvo_filter_backward_cov(
     using namespace psvo;
     using namespace psvo::cov;
     if (!desc_ok(desc)) return PSVO_ERR_INVALID;
-    if (desc->layers > 1 || desc->layers < 0) return PSVO_ERR_UNSUPPORTED;
+    if (desc->layers > 1 || desc->layers < 0 || !desc_emission_ok(desc)) return PSVO_ERR_UNSUPPORTED;
     if (!q1 || !g || !sigc_q1 || !sigc_g || !m0 || !sig0 || !fm0 || !fsig0 || !obs || !eps || !X || !Fm || !Fs || !logW ||
         !lse || !dP || !dPs || !dG || !dGs || !dm0 || !dsig0 || !dfm0 || !dfsig0 || !dsigc_q1 || !dsigc_g || !ws)
         return PSVO_ERR_INVALID;

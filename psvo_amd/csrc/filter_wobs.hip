@@ -68,7 +68,9 @@ struct FwdArgs {
 // Forward filter: lane = particle, workgroup = sequence, t in-kernel (filter_fwd.hip's lane-per-particle kernel with the
 // emission walked over a run-time Dy).  Same outputs and draw rule: idx = #{k : cdf[k] <= u * total}, clamped to N - 1.
 // ---------------------------------------------------------------------------------------------
-template <int DX, int H>
+// CNT: the count emission (psvo_desc.emission = 2), a compile-time form so that the Gaussian / unit-normal instantiations keep
+// their code and registers.  1 / sig_g is not used; the log-factorial row of a step travels with its observation row.
+template <int DX, int H, bool CNT>
 __global__ void __launch_bounds__(512) filter_fwd_wobs_kernel(const FwdArgs a) {
     using MQ = MlpLds<DX, H, DX, 1>;
     using MG = GLds<DX, H>;
@@ -90,14 +92,17 @@ __global__ void __launch_bounds__(512) filter_fwd_wobs_kernel(const FwdArgs a) {
     float* sp = sx + DX * NT;           // [DX][NT] staged MLP_q1(X_t)
     float* sf = sp + DX * NT;           // [DX][NT] staged MLP_f(X_t) (unused when bootstrap)
     float* red = sf + DX * NT;          // 48 floats scratch
+    float* lfbuf = red + 48;            // CNT: [2][kMaxDy] log Gamma(y + 1) of the rows in ybuf
 
     MQ::load(wq1, a.q1, tid, NT);
     if (!a.bootstrap) MQ::load(wf, a.f, tid, NT);
     MG::load(wg, a.g, Dy, tid, NT);
     const float* wfm = a.bootstrap ? wq1 : wf;
     if (tid < Dy) {
-        isg[tid] = 1.f / a.sig_g[tid];
-        ybuf[tid] = a.obs[(size_t)b * Dy + tid];
+        if constexpr (!CNT) isg[tid] = 1.f / a.sig_g[tid];
+        const float y0 = a.obs[(size_t)b * Dy + tid];
+        ybuf[tid] = y0;
+        if constexpr (CNT) lfbuf[tid] = log_factorial(y0);
     }
 
     float sq1[DX], sq2[DX], sfv[DX], s0[DX], fs0[DX];
@@ -110,7 +115,9 @@ __global__ void __launch_bounds__(512) filter_fwd_wobs_kernel(const FwdArgs a) {
         fs0[d] = a.fsig0[d];
     }
     float lg = -Dy * kHalfLog2Pi;
-    for (int e = 0; e < Dy; ++e) lg -= logf(a.sig_g[e]);
+    if constexpr (!CNT) {
+        for (int e = 0; e < Dy; ++e) lg -= logf(a.sig_g[e]);
+    }
     const StepK<DX> K0 = make_stepk<DX>(s0, sq2, fs0, a.two_q != 0);
     const StepK<DX> K1 = make_stepk<DX>(sq1, sq2, sfv, a.two_q != 0);
     const float neg_logN = -logf((float)N);
@@ -175,14 +182,21 @@ __global__ void __launch_bounds__(512) filter_fwd_wobs_kernel(const FwdArgs a) {
             float h[H];
             MG::hidden(wg_t, x, h);
             float acc = 0.f;
+            if constexpr (CNT) {     // y log lam - lam - log Gamma(y + 1), one term per output
+                const float* lf_t = lfbuf + (t & 1) * kMaxDy + zo;
 #pragma unroll 1
-            for (int e = 0; e < Dy; ++e) {
-                float gm = MG::out(wg_t, e, h);
-                if (a.emission) gm = emis_mean(gm);
-                const float z = (y_t[e] - gm) * isg[e];
-                acc = fmaf(z, z, acc);
+                for (int e = 0; e < Dy; ++e) acc += count_term(y_t[e], MG::out(wg_t, e, h)) - lf_t[e];
+                g_lp = acc;
+            } else {
+#pragma unroll 1
+                for (int e = 0; e < Dy; ++e) {
+                    float gm = MG::out(wg_t, e, h);
+                    if (a.emission) gm = emis_mean(gm);
+                    const float z = (y_t[e] - gm) * isg[e];
+                    acc = fmaf(z, z, acc);
+                }
+                g_lp = fmaf(-0.5f, acc, lg);
             }
-            g_lp = fmaf(-0.5f, acc, lg);
         }
         float lw = f_lp + g_lp - q_lp + lnw;
         if (!valid) lw = ninf;
@@ -278,7 +292,10 @@ __global__ void __launch_bounds__(512) filter_fwd_wobs_kernel(const FwdArgs a) {
             lnw = lw - lse_t;
         }
         // the prefetched observation row goes to the half of ybuf that step t - 1 read (behind the barrier that ended it)
-        if (t + 1 < T && tid < Dy) ybuf[((t + 1) & 1) * kMaxDy + tid] = y_n;
+        if (t + 1 < T && tid < Dy) {
+            ybuf[((t + 1) & 1) * kMaxDy + tid] = y_n;
+            if constexpr (CNT) lfbuf[((t + 1) & 1) * kMaxDy + tid] = log_factorial(y_n);
+        }
         __syncthreads();  // staged tiles / red[] are rewritten next step; the next observation row is visible
 
 #pragma unroll
@@ -292,16 +309,19 @@ __global__ void __launch_bounds__(512) filter_fwd_wobs_kernel(const FwdArgs a) {
 }
 
 template <int DX, int H>
-static size_t fwd_lds_bytes(int NT) {
-    return sizeof(float) * (2 * MlpLds<DX, H, DX, 1>::kSize + GLds<DX, H>::kSize + 3 * kMaxDy + NT + 3 * DX * NT + 48);
+static size_t fwd_lds_bytes(int NT, bool count) {
+    return sizeof(float) * (2 * MlpLds<DX, H, DX, 1>::kSize + GLds<DX, H>::kSize + 3 * kMaxDy + NT + 3 * DX * NT + 48 +
+                            (count ? 2 * kMaxDy : 0));
 }
 
 template <int DX, int H>
 static int launch_fwd(const FwdArgs& a, hipStream_t stream) {
     const int NT = (a.N + 63) & ~63;
-    const size_t lds = fwd_lds_bytes<DX, H>(NT);
+    const bool count = a.emission == 2;
+    const size_t lds = fwd_lds_bytes<DX, H>(NT, count);
     clear_hip_error();
-    hipLaunchKernelGGL((filter_fwd_wobs_kernel<DX, H>), dim3(a.B), dim3(NT), lds, stream, a);
+    if (count) hipLaunchKernelGGL((filter_fwd_wobs_kernel<DX, H, true>), dim3(a.B), dim3(NT), lds, stream, a);
+    else hipLaunchKernelGGL((filter_fwd_wobs_kernel<DX, H, false>), dim3(a.B), dim3(NT), lds, stream, a);
     return launch_status();
 }
 
@@ -351,7 +371,8 @@ struct Acc {
     static constexpr int kSg = 2 * kSet;     // d sigma_g (Dy)
 };
 
-template <int DX, int H, bool EXT>
+// CNT: the count emission (as in the forward kernel); its d G rows are dlw (y / lam - 1) sigmoid(r), there is no d sig_g
+template <int DX, int H, bool EXT, bool CNT>
 __global__ void __launch_bounds__(512) filter_bwd_wobs_kernel(const BwdArgs a) {
     using MQ = MlpLds<DX, H, DX, 1>;
     using MG = GLds<DX, H>;
@@ -381,10 +402,12 @@ __global__ void __launch_bounds__(512) filter_bwd_wobs_kernel(const BwdArgs a) {
     MG::load(wg, a.g, Dy, tid, NT);
     const float* wfm = a.bootstrap ? wq1 : wf;
     if (tid < Dy) {
-        isg[tid] = 1.f / a.sig_g[tid];
+        if constexpr (!CNT) isg[tid] = 1.f / a.sig_g[tid];
         ybuf[((T - 1) & 1) * kMaxDy + tid] = a.obs[((size_t)(T - 1) * B + b) * Dy + tid];
     }
-    for (int e = 0; e < Dy; ++e) sg[e * NT + tid] = 0.f;
+    if constexpr (!CNT) {
+        for (int e = 0; e < Dy; ++e) sg[e * NT + tid] = 0.f;
+    }
     if (tid == 0) {
         float sq1[DX], sq2[DX], sfv[DX], s0[DX], fs0[DX];
 #pragma unroll
@@ -433,13 +456,23 @@ __global__ void __launch_bounds__(512) filter_bwd_wobs_kernel(const BwdArgs a) {
         const float* K = kst + (first ? 0 : 5 * DX) + zo;
 
         float y_n = 0.f;
-        if (t >= 1 && tid < Dy) y_n = a.obs[(tb - B) * Dy + tid];       // next step's observation row, in flight during this one
+        if (t >= 1 && tid < Dy) {       // next step's observation row, in flight during this one
+            if constexpr (CNT) y_n = PSVO_ARG(BwdArgs, obs)[(tb - B) * Dy + tid];      // (see dlse below)
+            else y_n = a.obs[(tb - B) * Dy + tid];
+        }
 
         float x[DX];
 #pragma unroll
         for (int d = 0; d < DX; ++d) x[d] = a.X[(tb * DX + d) * N + n];
         const float lw_t = a.logW[tb * N + n], lse_t = a.lse[tb];
-        const float dlse_t = a.dlse ? a.dlse[tb] : 0.f;
+        float dlse_t;
+        if constexpr (CNT) {    // (dlse and obs re-read from the kernel arguments where they are used, as the _ext pointers are:
+            // held across the time loop they left a dead 64-byte spill slot, i.e. a scratch allocation, in five EXT forms)
+            const float* dlse = PSVO_ARG(BwdArgs, dlse);
+            dlse_t = dlse ? dlse[tb] : 0.f;
+        } else {
+            dlse_t = a.dlse ? a.dlse[tb] : 0.f;
+        }
 
         // ---- gradient w.r.t. logW_t[n] ------------------------------------------------------------
         const float sm = valid ? exp2_fast((lw_t - lse_t) * kLog2e) : 0.f;
@@ -467,15 +500,23 @@ __global__ void __launch_bounds__(512) filter_bwd_wobs_kernel(const BwdArgs a) {
         {
             float h[H];
             MG::hidden(wg_t, x, h);
+            if constexpr (CNT) {
 #pragma unroll 1
-            for (int o = 0; o < Dy; ++o) {
-                float gm = MG::out(wg_t, o, h);
-                float dmean = 1.f;
-                if (a.emission) { dmean = emis_dmean(gm); gm = emis_mean(gm); }
-                const float is = isg[o];
-                const float z = (y_t[o] - gm) * is;
-                sg[o * NT + tid] += dlw * (z * z - 1.f) * is;
-                if (valid) a.dG[(tb * Dy + o) * N + n] = dlw * z * is * dmean;
+                for (int o = 0; o < Dy; ++o) {
+                    const float dr = dlw * count_dterm(y_t[o], MG::out(wg_t, o, h));
+                    if (valid) a.dG[(tb * Dy + o) * N + n] = dr;
+                }
+            } else {
+#pragma unroll 1
+                for (int o = 0; o < Dy; ++o) {
+                    float gm = MG::out(wg_t, o, h);
+                    float dmean = 1.f;
+                    if (a.emission) { dmean = emis_dmean(gm); gm = emis_mean(gm); }
+                    const float is = isg[o];
+                    const float z = (y_t[o] - gm) * is;
+                    sg[o * NT + tid] += dlw * (z * z - 1.f) * is;
+                    if (valid) a.dG[(tb * Dy + o) * N + n] = dlw * z * is * dmean;
+                }
             }
         }
         // (second walk over the outputs: the lane reads its own d G rows back -- H partial sums beside the H activations
@@ -625,9 +666,11 @@ __global__ void __launch_bounds__(512) filter_bwd_wobs_kernel(const BwdArgs a) {
         if (tid == 0) a.sacc[(size_t)b * NACC + AC::kSet + i] = s;
     }
     __syncthreads();
-    if (tid < Dy) {      // lane columns of d sig_g, in lane order
+    if (tid < Dy) {      // lane columns of d sig_g, in lane order (count emission: no scale, zeros)
         float s = 0.f;
-        for (int i = 0; i < N; ++i) s += sg[tid * NT + i];
+        if constexpr (!CNT) {
+            for (int i = 0; i < N; ++i) s += sg[tid * NT + i];
+        }
         a.sacc[(size_t)b * NACC + AC::kSg + tid] = s;
     }
 }
@@ -709,8 +752,14 @@ static int launch_bwd(const BwdArgs& a, const BwdOut& o, hipStream_t stream) {
     const int NT = (a.N + 63) & ~63;
     const size_t lds = bwd_lds_bytes<DX, H>(NT, a.Dy, a.bootstrap != 0);
     clear_hip_error();
-    if (a.dFm_ext || a.dlogW_ext) hipLaunchKernelGGL((filter_bwd_wobs_kernel<DX, H, true>), dim3(a.B), dim3(NT), lds, stream, a);
-    else hipLaunchKernelGGL((filter_bwd_wobs_kernel<DX, H, false>), dim3(a.B), dim3(NT), lds, stream, a);
+    const bool ext = a.dFm_ext || a.dlogW_ext;
+    if (a.emission == 2) {
+        if (ext) hipLaunchKernelGGL((filter_bwd_wobs_kernel<DX, H, true, true>), dim3(a.B), dim3(NT), lds, stream, a);
+        else hipLaunchKernelGGL((filter_bwd_wobs_kernel<DX, H, false, true>), dim3(a.B), dim3(NT), lds, stream, a);
+    } else {
+        if (ext) hipLaunchKernelGGL((filter_bwd_wobs_kernel<DX, H, true, false>), dim3(a.B), dim3(NT), lds, stream, a);
+        else hipLaunchKernelGGL((filter_bwd_wobs_kernel<DX, H, false, false>), dim3(a.B), dim3(NT), lds, stream, a);
+    }
     if (a.two_q) {
         const long long rows = (long long)a.T * a.B * DX;
         hipLaunchKernelGGL(wobs_row_sum_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, a.dm2_rows, rows,
@@ -960,6 +1009,7 @@ extern "C" int psvo_filter_forward_wobs(const psvo_desc* desc, const psvo_mlp* q
                                         int32_t* idx_out, float* lse, void* stream) {
     using namespace psvo;
     using namespace psvo::wobs;
+    if (!desc_emission_ok(desc, 2)) return PSVO_ERR_UNSUPPORTED;
     if (!desc || !q1 || !g || !sig_q1 || !sig_g || !m0 || !sig0 || !fm0 || !fsig0 || !obs || !eps || !X || !Xanc || !Fm ||
         !logW || !idx_out || !lse)
         return PSVO_ERR_INVALID;
@@ -994,6 +1044,7 @@ extern "C" int psvo_filter_backward_wobs_ext(
     float* dsig_q1, float* dsig_q2, float* dsig_f, float* dsig_g, float* dsig0, float* dfsig0, float* ws, void* stream) {
     using namespace psvo;
     using namespace psvo::wobs;
+    if (!desc_emission_ok(desc, 2)) return PSVO_ERR_UNSUPPORTED;
     if (!desc || !q1 || !g || !sig_q1 || !sig_g || !m0 || !sig0 || !fm0 || !fsig0 || !obs || !eps || !X || !Fm || !logW ||
         !lse || !dP || !dG || !dm0 || !dfm0 || !dsig_q1 || !dsig_q2 || !dsig_f || !dsig_g || !dsig0 || !dfsig0 || !ws)
         return PSVO_ERR_INVALID;

@@ -20,6 +20,38 @@ __device__ __forceinline__ float block_sum(float v, float* red, int wave, int la
     return s;
 }
 
+// Count emission (psvo_desc.emission = 2): log Gamma(y + 1) of an observed count.  Called by the lanes that stage the next
+// step's observation row, once per (step, sequence, output), never per particle.  Evaluated in fp64 and rounded once, so the
+// result is the fp32 nearest to the true value for every integer y (exactly 0 for y in {0, 1}): y < 8 takes log(y!) of the
+// exact product, y >= 8 the Stirling series at n = y + 1 with three correction terms (next term 1 / (1680 n^7) < 1.3e-10).
+// No table, hence no index: whatever y holds (negative, fractional, not finite), nothing is addressed with it.
+__device__ __forceinline__ float log_factorial(float y) {
+    const double n = (double)y + 1.0;
+    double p = 1.0;
+#pragma unroll
+    for (int k = 2; k < 8; ++k) p *= (y >= (float)k) ? (double)k : 1.0;
+    const bool small = !(y >= 8.f);
+    const double l = log(small ? p : n);
+    const double i = 1.0 / n, i2 = i * i;
+    const double series = i * (1.0 / 12.0 - i2 * (1.0 / 360.0 - i2 * (1.0 / 1260.0)));
+    return (float)(small ? l : (n - 0.5) * l - n + 0.9189385332046727418 + series);
+}
+
+// one term of the count log-density, without the log-factorial: y log lam - lam, lam = emis_mean(r) (common.h)
+__device__ __forceinline__ float count_term(float y, float r) {
+    const float lam = emis_mean(r);
+    return fmaf(y, logf(lam), -lam);
+}
+
+// d log g / d r = (y / lam - 1) sigmoid(r), written (y - lam) / lam: no cancellation where the rate fits the count.  Both
+// quotients are hardware reciprocals (1 ulp): an IEEE division is a dozen instructions and a pair of lane masks each, which the
+// reverse kernels have no scalar registers for
+__device__ __forceinline__ float count_dterm(float y, float r) {
+    const float lam = emis_mean(r);
+    const float sig = __builtin_amdgcn_rcpf(1.f + expf(-r));     // emis_dmean
+    return (y - lam) * __builtin_amdgcn_rcpf(lam) * sig;
+}
+
 // LDS image of MLP_g: W1[DX][H] | b1[H] | W2T[Dy][H] | b2[Dy]   (room for Dy = 32)
 template <int DX, int H>
 struct GLds {

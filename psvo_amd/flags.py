@@ -64,6 +64,9 @@ DEFINITIONS = [
     ("BSim_use_single_RNN", bool, False, "backward simulation proposal uses unidirectional RNN"),
     # (not in the reference's registry) PSVO on observations wider than two: the wide filter, then the wide backward simulation
     ("BSim_wide_obs", bool, False, "PSVO: run 3 <= Dy <= 32 on the wide-observation backward-simulation kernels"),
+    # (not in the reference's registry) a real Poisson likelihood of counts; --poisson_emission keeps its reference meaning, a
+    # unit-scale normal around the rate.  Wide-observation kernels only (3 <= Dy <= 32)
+    ("count_emission", bool, False, "emission is a Poisson law of counts with rate softplus(MLP_g(x)) + 1e-6 (3 <= Dy <= 32)"),
     # training (runner_flag.py:118-127)
     ("early_stop_patience", int, 200, "stop training early if validation set does not improve"),
     ("lr_reduce_patience", int, 30, "reduce learning rate when testing loss doesn't improve"),

@@ -8,7 +8,7 @@ import torch
 from torch import nn
 
 from .distribution.mvn import tf_mvn
-from .distribution.poisson import tf_poisson
+from .distribution.poisson import count_poisson, tf_poisson
 from .transformation.MLP import MLP_transformation
 
 
@@ -148,6 +148,7 @@ class SSM(nn.Module):
         self.output_cov, self.diag_cov = FLAGS.output_cov, FLAGS.diag_cov
         self.use_bootstrap, self.use_2_q = FLAGS.use_bootstrap, FLAGS.use_2_q
         self.poisson_emission = FLAGS.poisson_emission
+        self.count_emission = bool(getattr(FLAGS, "count_emission", False))      # (not in the reference)
         self.X0_use_separate_RNN, self.use_stack_rnn = FLAGS.X0_use_separate_RNN, FLAGS.use_stack_rnn
         self.PSVO, self.PSVOwR, self.SVO = FLAGS.PSVO, getattr(FLAGS, "PSVOwR", False), FLAGS.SVO
         self.BSim_use_single_RNN = FLAGS.BSim_use_single_RNN
@@ -200,7 +201,9 @@ class SSM(nn.Module):
             self.f_dist = self.q1_dist
         else:
             self.f_dist = tf_mvn(self.f_tran, self.f_sigma_init, self.f_sigma_min, "f_dist")
-        if self.poisson_emission:                            # model.py:153-155
+        if self.count_emission:                              # a Poisson law of counts (psvo_desc.emission = 2)
+            self.g_dist = count_poisson(self.g_tran, "g_dist")
+        elif self.poisson_emission:                          # model.py:153-155
             self.g_dist = tf_poisson(self.g_tran, "g_dist")
         else:
             self.g_dist = tf_mvn(self.g_tran, self.g_sigma_init, self.g_sigma_min, "g_dist")

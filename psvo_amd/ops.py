@@ -166,7 +166,7 @@ def make_desc(B, T, N, M, Dx, Dy, H, resample=True, two_q=True, bootstrap=True, 
     d.B, d.T, d.N, d.M, d.Dx, d.Dy, d.H = B, T, N, M, Dx, Dy, H
     d.layers = int(layers)            # hidden layers of every per-particle MLP of the call (1 or 2)
     d.resample, d.two_q, d.bootstrap = int(resample), int(two_q), int(bootstrap)
-    d.emission = int(emission)        # 1: tf_poisson emission (unit-scale normal, softplus mean)
+    d.emission = int(emission)        # 1: tf_poisson emission (unit-scale normal, softplus mean); 2: count (Poisson) emission, wide kernels
     return d
 
 

@@ -29,7 +29,7 @@ from .SMC.PSVO import PSVO
 from .SMC.PSVOwR import PSVOwR
 from .SMC.SVO import SVO
 from .trainer import trainer
-from .utils.data_generator import generate_dataset
+from .utils.data_generator import PoissonEmitter, count_loading, generate_dataset
 from .utils.data_loader import load_data
 
 # flag name -> objective class, in the reference's order of precedence (src/runner.py:70-81)
@@ -46,15 +46,36 @@ def _device():
 
 def _dataset(FLAGS):
     """(hidden_train, hidden_test, obs_train, obs_test); updates the flags that describe the data"""
+    count = bool(getattr(FLAGS, "count_emission", False))
     if FLAGS.generateTrainingData:
-        data = generate_dataset(FLAGS.n_train, FLAGS.n_test, FLAGS.time, model="fhn", Dy=FLAGS.Dy, lb=-2.5, ub=2.5)
+        # (count emission: Poisson counts of the FHN latent through a fixed loading, data_generator.count_loading)
+        g = PoissonEmitter(*count_loading(FLAGS.Dy, 2)) if count else None
+        data = generate_dataset(FLAGS.n_train, FLAGS.n_test, FLAGS.time, model="fhn", Dy=FLAGS.Dy, g=g, lb=-2.5, ub=2.5)
     else:
         data = load_data(FLAGS.datadir + FLAGS.datadict, FLAGS.Dx, FLAGS.isPython2, FLAGS.q_uses_true_X)
         obs_train, obs_test = data[2], data[3]
         FLAGS.n_train, FLAGS.n_test, FLAGS.time = obs_train.shape[0], obs_test.shape[0], obs_test.shape[1]
+    if count:
+        check_counts(data[2], "obs_train")
+        check_counts(data[3], "obs_test")
     FLAGS.MSE_steps = min(FLAGS.MSE_steps, FLAGS.time - 1)
     FLAGS.saving_num = min(FLAGS.saving_num, FLAGS.n_train, FLAGS.n_test)
     return data
+
+
+def check_counts(obs, name="obs"):
+    """--count_emission scores observations with a Poisson law: they must be finite, non-negative and integer-valued
+    (checked once, on the host, when the data set is prepared; the kernels do not check)"""
+    a = np.asarray(obs, dtype=np.float64)
+    if not np.isfinite(a).all():
+        raise ValueError("--count_emission: %s holds non-finite values (first at index %s)"
+                         % (name, tuple(int(i) for i in np.argwhere(~np.isfinite(a))[0])))
+    if a.size and a.min() < 0:
+        raise ValueError("--count_emission: %s holds negative values (minimum %r); counts are >= 0" % (name, float(a.min())))
+    frac = a != np.floor(a)
+    if frac.any():
+        raise ValueError("--count_emission: %s holds non-integer values (first: %r at index %s); counts are integers"
+                         % (name, float(a[frac][0]), tuple(int(i) for i in np.argwhere(frac)[0])))
 
 
 def _objective(model, FLAGS):

@@ -12,6 +12,7 @@ Contract kept from the reference (cited lines: its files)
   * order of the random draws (it fixes the data for a given np.random.seed): per sequence -- training sequences first -- the
     initial state x_0 ~ U(lb, ub)^Dx, then one emission draw per time step, t = 0 first;
   * `f` / `g` may be supplied: anything with a `.sample(x)` method (the reference's distribution objects) or a plain callable.
+PoissonEmitter is such a `g`: counts y ~ Poisson(softplus(C x + d)) for the count emission (FLAGS.count_emission).
 """
 import numpy as np
 from scipy.integrate import odeint
@@ -54,6 +55,30 @@ class _LinearGaussian:
     def sample(self, x):
         mean = self._G @ x
         return mean + self._chol @ np.random.randn(mean.shape[0])
+
+
+class PoissonEmitter:
+    """x -> Poisson(softplus(C x + d)): counts, drawn from numpy's GLOBAL generator like the Gaussian emission (not in the
+    reference's generator; its numpy `poisson.sample` draws np.random.poisson the same way).  Usable as `g=` of
+    generate_dataset; `rate(x)` is the mean."""
+
+    def __init__(self, C, d):
+        self._C, self._d = np.asarray(C, dtype=float), np.asarray(d, dtype=float)
+
+    def rate(self, x):
+        return np.logaddexp(0.0, self._C @ np.asarray(x, dtype=float) + self._d)
+
+    def sample(self, x):
+        return np.random.poisson(self.rate(x)).astype(float)
+
+
+def count_loading(Dy, Dx=2):
+    """(C (Dy, Dx), d (Dy,)) of the runner's generated count data: row k of C is (cos, sin)(2 pi k / Dy) -- the outputs look at
+    the first two latent coordinates from Dy evenly spaced directions, further columns are zero -- and d = 1"""
+    ang = 2.0 * np.pi * np.arange(Dy) / Dy
+    C = np.zeros((Dy, Dx))
+    C[:, 0], C[:, 1] = np.cos(ang), np.sin(ang)
+    return C, np.ones(Dy)
 
 
 _MODELS = {   # name: (Dx, transition step, its parameters, emission matrix, emission variance)
