@@ -33,26 +33,10 @@
 namespace psvo {
 PSVO_TIMERS_DEFINE(bsim_bwd2)
 
-// Every array of the kernel is reached through a GLOBAL-address-space pointer (gptr): base (SGPR pair) + 32-bit byte offset
-// then compiles to the saddr form (global_load_dword v, v_off, s[base:base+1]).  A pointer that arg_block (common.h) hands
-// out as an integer is a generic pointer to hipcc, and a dereference of it is a FLAT access: it builds a 64-bit address on
-// the VALU and counts on lgkmcnt as well as vmcnt, so that every LDS wait behind a prefetch (s_waitcnt lgkmcnt(0)) waited
-// for the prefetched words too.  No access of this unit may go through a plain pointer.
-template <class T>
-using gptr = T __attribute__((address_space(1)))*;
-template <class T>
-__device__ __forceinline__ gptr<T> as_global(T* p) { return (gptr<T>)p; }
-template <class T>
-__device__ __forceinline__ gptr<T> as_global(unsigned long long p) { return (gptr<T>)p; }
-__device__ __forceinline__ float ldf(gptr<const float> base, unsigned off) {
-    return *reinterpret_cast<gptr<const float>>(reinterpret_cast<gptr<const char>>(base) + off);
-}
-__device__ __forceinline__ int ldi(gptr<const int32_t> base, unsigned off) {
-    return *reinterpret_cast<gptr<const int32_t>>(reinterpret_cast<gptr<const char>>(base) + off);
-}
-__device__ __forceinline__ void stf(gptr<float> base, unsigned off, float v) {
-    *reinterpret_cast<gptr<float>>(reinterpret_cast<gptr<char>>(base) + off) = v;
-}
+// Every array of the kernel is reached through a GLOBAL-address-space pointer (common.h: gptr, ldf / ldi / stf).  A pointer
+// that arg_block (common.h) hands out as an integer is a generic pointer to hipcc, and a dereference of it is a FLAT access:
+// it builds a 64-bit address on the VALU and counts on lgkmcnt as well as vmcnt, so that every LDS wait behind a prefetch
+// (s_waitcnt lgkmcnt(0)) waited for the prefetched words too.  No access of this unit may go through a plain pointer.
 // pointer argument re-read at its point of use (common.h: PSVO_ARG), as a global pointer
 #define PSVO_GARG(args_type, field) ::psvo::as_global(PSVO_ARG(args_type, field))
 

@@ -14,6 +14,13 @@
 //   * the forward tile of step t-1 -- F'_j = MLP_f(X_{t-1}[j]) * r and W'_j = normalised log
 //     weight, both pre-scaled into the log2 domain -- is staged in LDS (N * 16 B; 2 KB at N=128),
 //     double-buffered, prefetched from HBM one step ahead.  The tile is never materialised.
+//   * prefetch: step t requests, at its top, the inputs of step t-1 (eps, bmu2, obs, the uniform or the forced index) and
+//     the raw tile of step t-2, and waits for all of them in ONE place, the `settle` in the rotation that ends the step
+//     (in front of its output stores); no s_waitcnt vmcnt stands between the two.  Every load is issued in every step on
+//     every path: the uniform and the forced index come through one base chosen in front of the loop, a thread's tile
+//     entries are a launch-uniform number of register sets with the entry index clamped, and where there is no step t-1
+//     or tile t-2 left the bases stand still and the words are dropped.  Addresses are 64-bit scalar bases that move by a
+//     constant per step plus a constant 32-bit lane offset (saddr form): no multiply by t, no limit on an array's size.
 //   * pair arithmetic: v = W'_j - sum_d (x'_d - F'_jd)^2  (log2 domain) in packed f32 (two sub-particles per
 //     instruction); log-sum-exp in blocks of 16 tile entries: all v of a block and its maximum first, then one
 //     rescale of the running sums and the block's exponentials (the tile is padded with W' = -inf to whole blocks).
@@ -60,8 +67,13 @@ __device__ __forceinline__ void lse2_merge(float& m, float& s, float m2, float s
 // walk over the forward particles and the hidden units of every MLP evaluation, so a chain step is
 // spread over 2*M lanes.  At C* (65536 (chain, m) pairs = one wave per SIMD, where a lone wave issues
 // one VALU op per 4 cycles) this doubles the resident waves per SIMD.
+// (Two hidden layers, Dx = 2, Dy = 1, H = 32: the kernels that fit two waves per SIMD, 256 registers, keep doing so -- left
+//  alone hipcc takes 276 with the constants and the settle pairs below.  <2,1,32,4,1> does not fit without scratch and is
+//  left at one wave.)
 template <int DX, int DY, int H, int M, int HS>
-__global__ void __launch_bounds__(256) bsim_fwd_kernel(const BsimArgs a) {
+constexpr int kBsimFwdWaves = (PSVO_L == 2 && DX == 2 && DY == 1 && H == 32 && !(M == 4 && HS == 1)) ? 2 : 1;
+template <int DX, int DY, int H, int M, int HS>
+__global__ void __launch_bounds__(256, (kBsimFwdWaves<DX, DY, H, M, HS>)) bsim_fwd_kernel(const BsimArgs a) {
     using MQ = MlpLds<DX, H, DX, PSVO_L>;
     using MG = MlpLds<DX, H, DY, PSVO_L>;
     constexpr int PS = TileSlot<DX>::kFloats;
@@ -135,32 +147,75 @@ __global__ void __launch_bounds__(256) bsim_fwd_kernel(const BsimArgs a) {
         im[d] = a.imean[b * DX + d];
         mi[d] = a.minit[b * DX + d];
     }
-    const float logM = logf((float)M);
+    float logM = logf((float)M);
     const float ninf = -__builtin_huge_valf();
+    // the constants every step reads live in VGPRs (common.h: keep_in_vgpr): the scalar registers go to the array bases and
+    // their strides.  (s_init, is_init, i_isig, im, mi, kinit, kiota are read in the first / last step only.)
+    keep_in_vgpr(isf); keep_in_vgpr(rp); keep_in_vgpr(isg); keep_in_vgpr(pc); keep_in_vgpr(pic); keep_in_vgpr(pi1);
+    keep_in_vgpr(pi2); keep_in_vgpr(kf); keep_in_vgpr(kg); keep_in_vgpr(kq); keep_in_vgpr(logM);
+
+    // ---- addresses -----------------------------------------------------------------------------------
+    // Every array is reached as  base (64-bit, wave-uniform: scalar registers) + 32-bit byte offset of the lane  -- the saddr
+    // form, global_load_dword v, v_off, s[base:base+1].  The base points at the array's row (t, b) and moves back by the
+    // row stride of the array's SHAPE once per step (two scalar adds); the lane's offset inside a row never changes and is
+    // below 1 MiB for every shape the ABI admits (N <= 1024).  No multiply by t in the loop, and no limit on the size of an
+    // array.  Three groups of bases travel one behind the other: the outputs at step t, the inputs at t - 1, the tile at t - 2.
+    typedef unsigned long long u64;
+    const u64 NM = (u64)N * M;
+    // row strides (bytes) of (T,B), (T,B,N), (T,B,DX), (T,B,DY), (T,B,DX,N): below 2^32 (B <= 65535, N <= 1024); (T,B,N,M), (T,B,DX,N,M)
+    const unsigned s_1 = 4u * B, s_n = s_1 * N, s_d = s_1 * DX, s_k = s_1 * DY, s_dn = s_n * DX;
+    const u64 s_nm = s_1 * NM, s_dnm = s_nm * DX;
+    const u64 r_1 = 4ull * ((u64)(T - 1) * B + b);                   // byte offset of row (T-1, b) in a (T,B) array
+    const unsigned o_n = 4u * n, o_nm = 4u * (n * M + m), sN4 = 4u * N, sNM4 = 4u * N * M;   // lane offsets inside a row
+    // (the offsets do not change from step to step: `here` keeps their zero-extension, which hipcc would hoist out of the
+    //  loop as a 64-bit register pair, in the block of the access, where it folds into the saddr form)
+    auto here = [](unsigned o) { asm volatile("" : "+v"(o)); return o; };
+    auto here_s = [](int v) { asm volatile("" : "+s"(v)); return v; };      // (the same for a wave-uniform value)
+    const bool forced = a.sel_in != nullptr;
+    // inputs of the step that is requested next (sel_in and u_b are both 4-byte words of shape (T,B,N): one base, chosen once)
+    u64 p_eps = (u64)a.eps_b + r_1 * (DX * NM), p_bmu = (u64)a.bmu2 + r_1 * DX, p_obs = (u64)a.obs + r_1 * DY,
+        p_us = (forced ? (u64)a.sel_in : (u64)a.u_b) + r_1 * N;
+    // forward tile that is requested next (T >= 2: the ABI refuses T = 1)
+    u64 p_Fm = (u64)a.Fm + (r_1 - s_1) * (DX * N), p_logW = (u64)a.logW + (r_1 - s_1) * N, p_lse = (u64)a.lse + (r_1 - s_1);
+    // outputs of the current step (the optional saves may be null: their bases are then never dereferenced)
+    // which stores the lane makes, as bits of ONE register tested where they are used: as booleans they are lane masks, a
+    // pair of scalar registers each, live across the whole loop (and with the bases in scalar registers, spilled to lanes)
+    constexpr unsigned kOut = 1u, kMu1 = 2u, kLam2 = 4u, kOm = 8u;
+    const unsigned lane_flags = (valid && lead ? kOut : 0u) | (a.mu1_all && valid && lead ? kMu1 : 0u) |
+                                (a.lam2_all && valid && hpart == 0 ? kLam2 : 0u) | (a.om_all && valid && hpart == 0 ? kOm : 0u);
+    auto stores = [&](unsigned bit) { return (here(lane_flags) & bit) != 0u; };
+    u64 p_bwX = (u64)a.bwX + r_1 * (DX * N), p_mu1 = (u64)a.mu1_all + r_1 * (DX * N), p_glp = (u64)a.glp + r_1 * N,
+        p_Om = (u64)a.Omega + r_1 * N, p_selo = (u64)a.sel_out + r_1 * N, p_flp = (u64)a.flp + r_1 * N,
+        p_lam2 = (u64)a.lam2_all + r_1 * NM, p_omall = (u64)a.om_all + r_1 * NM;
 
     // ---- forward-tile staging -----------------------------------------------------------------
     // The global loads of step t-2's tile are issued at the top of step t and only *consumed* (scaled and
     // written to LDS) at its end: nothing between depends on them, so their latency hides behind the step.
+    // A thread carries up to kMaxStage entries; how many is the same for the whole launch (nsets), and inside a set every
+    // lane loads (a clamped entry where it has none), so that no load stands in a divergent region.
+    const int nsets = (NP + NTB - 1) / NTB;
     float st[kMaxStage][DX + 1], st_l = 0.f;
-    auto stage_load = [&](int tt) {  // global -> registers (raw), forward step tt
-        const size_t tb = (size_t)tt * B + b;
-        st_l = a.lse[tb];
+#pragma unroll
+    for (int r = 0; r < kMaxStage; ++r)
+#pragma unroll
+        for (int d = 0; d <= DX; ++d) st[r][d] = 0.f;
+    auto stage_load = [&]() {  // global -> registers (raw), the forward step p_Fm / p_logW / p_lse point at
+        st_l = ldf(as_global<const float>(p_lse), 0u);
 #pragma unroll
         for (int r = 0; r < kMaxStage; ++r) {
-            const int j = tid + r * NTB;
-            if (j < NP) {
-                const int jc = j < N ? j : N - 1;
+            if (r == 0 || r < here_s(nsets)) {
+                const unsigned oj = here(4u * (unsigned)min(tid + r * NTB, N - 1));
 #pragma unroll
-                for (int d = 0; d < DX; ++d) st[r][d] = a.Fm[(tb * DX + d) * N + jc];
-                st[r][DX] = a.logW[tb * N + jc];
+                for (int d = 0; d < DX; ++d) st[r][d] = ldf(as_global<const float>(p_Fm), oj + d * sN4);
+                st[r][DX] = ldf(as_global<const float>(p_logW), oj);
             }
         }
     };
     auto stage_store = [&](float* buf) {  // registers -> LDS: F' = Fm * rho, W' = (logW - lse) * log2(e)
 #pragma unroll
         for (int r = 0; r < kMaxStage; ++r) {
-            const int j = tid + r * NTB;
-            if (j < NP) {
+            const int j = (int)here(tid) + r * NTB;      // (compared here and now: no lane mask lives across the step)
+            if ((r == 0 || r < here_s(nsets)) && j < NP) {
                 float F[DX];
 #pragma unroll
                 for (int d = 0; d < DX; ++d) F[d] = st[r][d] * rp[d];
@@ -180,27 +235,62 @@ __global__ void __launch_bounds__(256) bsim_fwd_kernel(const BsimArgs a) {
         }
     };
 
-    if (T >= 2) {
-        stage_load(T - 2);
-        stage_store(tile);
-    }
-
     // ---- per-step inputs, prefetched one step ahead ----------------------------------------------
-    float eps_c[DX], bmu_c[DX], obs_c[DY], u_c = 0.f;
-    int sel_c = 0;
-    auto load_inputs = [&](int t, float (&e)[DX], float (&bm)[DX], float (&o)[DY], float& uu, int& ss) {
-        const size_t tb = (size_t)t * B + b;
+    struct StepIn {
+        float eps[DX], bmu[DX], obs[DY];
+        int us;      // the uniform of the draw (bits of a float) or, teacher-forced, the index itself
+    };
+    auto load_inputs = [&](StepIn& s) {      // (issue only; the bases already point at the step to load)
 #pragma unroll
         for (int d = 0; d < DX; ++d) {
-            e[d] = a.eps_b[((tb * DX + d) * N + n) * M + m];
-            bm[d] = a.bmu2[tb * DX + d];
+            s.eps[d] = ldf(as_global<const float>(p_eps), here(o_nm) + d * sNM4);
+            s.bmu[d] = ldf(as_global<const float>(p_bmu), 4u * d);
         }
 #pragma unroll
-        for (int k = 0; k < DY; ++k) o[k] = a.obs[tb * DY + k];
-        if (a.sel_in) ss = a.sel_in[tb * N + n];
-        else uu = a.u_b[tb * N + n];
+        for (int k = 0; k < DY; ++k) s.obs[k] = ldf(as_global<const float>(p_obs), 4u * k);
+        s.us = ldi(as_global<const int32_t>(p_us), here(o_n));
     };
-    load_inputs(T - 1, eps_c, bmu_c, obs_c, u_c, sel_c);
+    // The wave waits for the words it requested in ONE place: `settle`, at the end of the step that requested them (in front
+    // of the loop for step T-1 and the first tile).  The empty asm reads every word, so the s_waitcnt that guards them
+    // stands there, and redefines it, so nothing later has a load to wait for.  Left to its own counting hipcc waits at the
+    // first use, which for the words of step t is BEHIND the requests of step t - 1, and has to assume there the path with
+    // the fewest requests: the wave then sat out the round trip of loads it had just issued, at the top of every step.
+    // Every path of the loop passes through the settle, and every load of a step is issued on every path to it.
+    // The words pass through the asm as aligned register PAIRS, so that each is loaded into a pair of its own.  A lone
+    // register may end up as the unused half of a packed operand of the pair loop (v_pk_fma_f32 with op_sel_hi: the
+    // broadcast W'), and hipcc guards the whole operand pair: a vmcnt(0) in the middle of the pair loop.
+    auto settle = [&](StepIn& s) {
+        constexpr int kW = 2 * DX + DY + 2 + kMaxStage * (DX + 1);
+        float us = __int_as_float(s.us), pad = 0.f;
+        float* w[kW + 1];
+        int k = 0;
+#pragma unroll
+        for (int d = 0; d < DX; ++d) w[k++] = &s.eps[d];
+#pragma unroll
+        for (int d = 0; d < DX; ++d) w[k++] = &s.bmu[d];
+#pragma unroll
+        for (int e = 0; e < DY; ++e) w[k++] = &s.obs[e];
+        w[k++] = &us;
+        w[k++] = &st_l;
+#pragma unroll
+        for (int r = 0; r < kMaxStage; ++r)
+#pragma unroll
+            for (int d = 0; d <= DX; ++d) w[k++] = &st[r][d];
+        w[k++] = &pad;
+#pragma unroll
+        for (int i = 0; i + 1 < kW + 1; i += 2) {
+            f2 p = f2{*w[i], *w[i + 1]};
+            asm volatile("" : "+v"(p));
+            *w[i] = p.x;
+            *w[i + 1] = p.y;
+        }
+        s.us = __float_as_int(us);
+    };
+    StepIn cur_in;
+    load_inputs(cur_in);
+    stage_load();
+    settle(cur_in);
+    stage_store(tile);
     __syncthreads();
 
     float xp[DX];  // x_{t+1} of this chain (same in all M lanes)
@@ -213,16 +303,22 @@ __global__ void __launch_bounds__(256) bsim_fwd_kernel(const BsimArgs a) {
     // the T-2 steps in between carry none of their branches
     auto step = [&](auto last_tag, auto zero_tag, const int t) {
         SEC(0);   // loop overhead / barrier tail
-        const size_t tb = (size_t)t * B + b;
         const float* cur = tile + ((T - 1 - t) & 1) * NP * PS;
         float* nxt = tile + ((T - t) & 1) * NP * PS;
         const bool last = last_tag;                 // (compile-time constants in the peeled instantiations)
         const bool tzero = zero_tag;
-
-        float eps_n[DX], bmu_n[DX], obs_n[DY], u_n = 0.f;
-        int sel_n = 0;
-        if (!tzero) load_inputs(t - 1, eps_n, bmu_n, obs_n, u_n, sel_n);
-        if (t >= 2) stage_load(t - 2);
+        // the peeled step t = 0 requests nothing; everywhere else every load is issued in every step.  Where there is no
+        // step t - 1 (the unpeeled loop at t = 0) or no tile t - 2 (t <= 1) the bases stay where they are: the words of the
+        // row they point at are requested once more and dropped.
+        constexpr bool kNoPrefetch = std::is_same<decltype(zero_tag), std::true_type>::value;
+        StepIn nxt_in;
+        if constexpr (!kNoPrefetch) {
+            const bool in_step = kPeel || t >= 1, tile_step = t >= 2;
+            p_eps -= in_step ? s_dnm : 0; p_bmu -= in_step ? s_d : 0; p_obs -= in_step ? s_k : 0; p_us -= in_step ? s_n : 0;
+            load_inputs(nxt_in);
+            p_Fm -= tile_step ? s_dn : 0; p_logW -= tile_step ? s_n : 0; p_lse -= tile_step ? s_1 : 0;
+            stage_load();
+        }
 
         SEC(1);   // issue of the prefetch loads
         // ---- proposal ---------------------------------------------------------------------------
@@ -232,12 +328,12 @@ __global__ void __launch_bounds__(256) bsim_fwd_kernel(const BsimArgs a) {
 #pragma unroll
             for (int d = 0; d < DX; ++d) {
                 mu[d] = mi[d];
-                x[d] = fmaf(s_init[d], eps_c[d], mu[d]);
+                x[d] = fmaf(s_init[d], cur_in.eps[d], mu[d]);
             }
             q_lp = diag_lp<DX>(x, mu, is_init, kinit);
-            if (a.mu1_all && valid && lead) {
+            if (stores(kMu1)) {
 #pragma unroll
-                for (int d = 0; d < DX; ++d) a.mu1_all[(tb * DX + d) * N + n] = 0.f;
+                for (int d = 0; d < DX; ++d) stf(as_global<float>(p_mu1), here(o_n) + d * sN4, 0.f);
             }
         } else {
             float m1[DX], mu[DX];
@@ -247,14 +343,14 @@ __global__ void __launch_bounds__(256) bsim_fwd_kernel(const BsimArgs a) {
 #pragma unroll
                 for (int d = 0; d < DX; ++d) m1[d] = group_sum<kQS>(m1[d]);
             }
-            if (a.mu1_all && valid && lead) {
+            if (stores(kMu1)) {
 #pragma unroll
-                for (int d = 0; d < DX; ++d) a.mu1_all[(tb * DX + d) * N + n] = m1[d];
+                for (int d = 0; d < DX; ++d) stf(as_global<float>(p_mu1), here(o_n) + d * sN4, m1[d]);
             }
 #pragma unroll
             for (int d = 0; d < DX; ++d) {
-                mu[d] = pc[d] * fmaf(pi1[d], m1[d], pi2[d] * bmu_c[d]);
-                x[d] = fmaf(pc[d], eps_c[d], mu[d]);
+                mu[d] = pc[d] * fmaf(pi1[d], m1[d], pi2[d] * cur_in.bmu[d]);
+                x[d] = fmaf(pc[d], cur_in.eps[d], mu[d]);
             }
             q_lp = diag_lp<DX>(x, mu, pic, kq);
         }
@@ -285,7 +381,7 @@ __global__ void __launch_bounds__(256) bsim_fwd_kernel(const BsimArgs a) {
 #pragma unroll
             for (int k = 0; k < DY; ++k) gm[k] = emis_mean(gm[k]);
         }
-        const float g_lp = diag_lp<DY>(obs_c, gm, isg, kg);
+        const float g_lp = diag_lp<DY>(cur_in.obs, gm, isg, kg);
 
         SEC(3);   // MLP_f, MLP_g, densities
         // ---- filter term: logsumexp_j( log f(x~ | X_{t-1}[j]) + W^_{t-1}[j] ) -----------------------
@@ -391,7 +487,7 @@ __global__ void __launch_bounds__(256) bsim_fwd_kernel(const BsimArgs a) {
             }
             const float lam2 = lm + log2_fast(ls);
             lam = fmaf(kLn2, lam2, kf);
-            if (a.lam2_all && valid && hpart == 0) a.lam2_all[(tb * N + n) * M + m] = lam2;
+            if (stores(kLam2)) stf(as_global<float>(p_lam2), here(o_nm), lam2);
         } else {
             lam = diag_lp<DX>(x, im, i_isig, kiota);  // t = 0: q0 / f density at mu_0 (PSVO.py:169-175)
         }
@@ -404,12 +500,12 @@ __global__ void __launch_bounds__(256) bsim_fwd_kernel(const BsimArgs a) {
         const float cdfv = group_incl_scan<M>(pw, m);  // inclusive scan across the chain's M lanes
         const float total = __shfl(cdfv, gbase + M - 1);
         const float omega = om_raw - fmaf(kLn2, log2_fast(total), omx);
-        if (a.om_all && valid && hpart == 0) a.om_all[(tb * N + n) * M + m] = omega;
+        if (stores(kOm)) stf(as_global<float>(p_omall), here(o_nm), omega);
         int sel;
-        if (a.sel_in) {
-            sel = sel_c;
+        if (forced) {
+            sel = cur_in.us;
         } else {
-            const unsigned long long bal = __ballot(cdfv <= u_c * total);
+            const unsigned long long bal = __ballot(cdfv <= __int_as_float(cur_in.us) * total);
             const unsigned long long mask = (M == 64) ? ~0ull : (((1ull << M) - 1ull) << gbase);
             sel = min((int)__popcll(bal & mask), M - 1);
         }
@@ -425,31 +521,31 @@ __global__ void __launch_bounds__(256) bsim_fwd_kernel(const BsimArgs a) {
         const float lam_s = __shfl(lam, src);
         const float Om = om_s + q_s + logM;
 
-        if (valid && lead) {
+        // the words requested at the top of this step become the next step's here, in front of the step's own output
+        // stores: the wait covers the loads and none of the stores behind it
+        if constexpr (!kNoPrefetch) {
+            settle(nxt_in);
+            cur_in = nxt_in;
+        }
+        if (stores(kOut)) {
+            const unsigned on = here(o_n);
 #pragma unroll
-            for (int d = 0; d < DX; ++d) a.bwX[(tb * DX + d) * N + n] = xs[d];
-            a.glp[tb * N + n] = g_s;
-            a.Omega[tb * N + n] = Om;
-            a.sel_out[tb * N + n] = sel;
-            if (!last) a.flp[(tb + B) * N + n] = phi_s;     // f_log_probs[t+1]
-            if (tzero) a.flp[(size_t)b * N + n] = lam_s;    // f_log_probs[0] = f_init
+            for (int d = 0; d < DX; ++d) stf(as_global<float>(p_bwX), on + d * sN4, xs[d]);
+            stf(as_global<float>(p_glp), on, g_s);
+            stf(as_global<float>(p_Om), on, Om);
+            sti(as_global<int32_t>(p_selo), on, sel);
+            if (!last) stf(as_global<float>(p_flp + s_n), on, phi_s);     // f_log_probs[t+1]
+            if (tzero) stf(as_global<float>(p_flp), on, lam_s);           // f_log_probs[0] = f_init
         }
         score += g_s - Om + (last ? 0.f : phi_s) + (tzero ? lam_s : 0.f);
-
 #pragma unroll
-        for (int d = 0; d < DX; ++d) {
-            xp[d] = xs[d];
-            eps_c[d] = eps_n[d];
-            bmu_c[d] = bmu_n[d];
-        }
-#pragma unroll
-        for (int k = 0; k < DY; ++k) obs_c[k] = obs_n[k];
-        u_c = u_n;
-        sel_c = sel_n;
+        for (int d = 0; d < DX; ++d) xp[d] = xs[d];
 
-        SEC(7);   // gather of the selected sub-particle, output stores
+        SEC(7);   // gather of the selected sub-particle, settle of the prefetched words, output stores
         if (t >= 2) stage_store(nxt);
         __syncthreads();
+        // the outputs' bases move on to step t - 1
+        p_bwX -= s_dn; p_mu1 -= s_dn; p_glp -= s_n; p_Om -= s_n; p_selo -= s_n; p_flp -= s_n; p_lam2 -= s_nm; p_omall -= s_nm;
         SEC(8);   // tile store + barrier
     };
     if constexpr (kPeel) {

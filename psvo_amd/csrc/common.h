@@ -204,6 +204,29 @@ __device__ __forceinline__ void keep_in_vgpr(float (&x)[K]) {
     for (int i = 0; i < K; ++i) asm volatile("" : "+v"(x[i]));
 }
 
+// GLOBAL-address-space pointers for the persistent kernels: base (SGPR pair) + 32-bit byte offset compiles to the saddr
+// form (global_load_dword v, v_off, s[base:base+1]): no 64-bit address arithmetic on the VALU, and the access counts on
+// vmcnt alone (a FLAT access through a generic pointer counts on lgkmcnt as well, so that every LDS wait behind it waits
+// for it too).  The base is a pointer or the integer a kernel keeps and advances per time step.
+template <class T>
+using gptr = T __attribute__((address_space(1)))*;
+template <class T>
+__device__ __forceinline__ gptr<T> as_global(T* p) { return (gptr<T>)p; }
+template <class T>
+__device__ __forceinline__ gptr<T> as_global(unsigned long long p) { return (gptr<T>)p; }
+__device__ __forceinline__ float ldf(gptr<const float> base, unsigned off) {
+    return *reinterpret_cast<gptr<const float>>(reinterpret_cast<gptr<const char>>(base) + off);
+}
+__device__ __forceinline__ int ldi(gptr<const int32_t> base, unsigned off) {
+    return *reinterpret_cast<gptr<const int32_t>>(reinterpret_cast<gptr<const char>>(base) + off);
+}
+__device__ __forceinline__ void stf(gptr<float> base, unsigned off, float v) {
+    *reinterpret_cast<gptr<float>>(reinterpret_cast<gptr<char>>(base) + off) = v;
+}
+__device__ __forceinline__ void sti(gptr<int32_t> base, unsigned off, int v) {
+    *reinterpret_cast<gptr<int32_t>>(reinterpret_cast<gptr<char>>(base) + off) = v;
+}
+
 // Re-read a POINTER kernel argument from the kernarg segment at its point of use.  The persistent kernels take 20-30
 // array pointers; hipcc loads them all into SGPRs in the prologue and keeps them live across the time loop (two SGPRs
 // each), which is what overflows the 102 SGPRs of a wave.  Routed through this helper an argument costs one s_load_dwordx2
