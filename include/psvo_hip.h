@@ -474,6 +474,9 @@ int psvo_bsim_forward(const psvo_desc* desc,
  *            dFm (T,B,Dx,N), dlogW (T,B,N) = d loss / d (Fm, logW) of the forward filter -> psvo_filter_backward, and the
  *            scale gradients dsig_f, dsig_q1inv, dsig_bq2, dsig_init, disig (Dx), dsig_g (Dy);
  *            dlse (T,B) or NULL = -sum_n dlogW[t,b,n] = d loss / d lse of the forward filter (ABI 5).
+ *            Alignment: none is required.  The fold moves 16 bytes per access when N % 4 == 0 and dFm_part, dlogW_part,
+ *            dFm and dlogW are all 16-byte aligned, 4 bytes otherwise; every element adds its workgroups in the same order
+ *            either way, so the results do not depend on which is taken.
  * ------------------------------------------------------------------------------------------- */
 int psvo_bsim_blocks(const psvo_desc* desc);      /* nblk for this problem under the current PSVO_TUNE_BSIM_BWD setting */
 int psvo_bsim_acc_size(int Dx, int Dy);
@@ -694,6 +697,9 @@ int psvo_mlp_wgrad_wobs(long long S, int L, int Din, int H, int Dout, const floa
  *   scale sums are per-lane values folded lanes first (DPP scan), then waves, then (sequence, workgroup) rows in order;
  *   d sig_g[e] is one column per lane folded in lane order.  Two runs of the same inputs are bit-identical whatever
  *   PSVO_TUNE_DETERMINISTIC is.
+ *   The fold behind the kernel is psvo_bsim_backward_fold's, with its alignment rule: 16-byte accesses when N % 4 == 0 and the
+ *   partials carved out of `ws` (at ws and ws + T B nblk Dx N floats), dFm and dlogW are all 16-byte aligned, 4-byte accesses
+ *   otherwise, with the same results.
  * psvo_filter_backward_wobs_ext: psvo_filter_backward_wobs with the upstream gradients dFm_ext (T,B,nparts,Dx,N) and
  *   dlogW_ext (T,B,nparts,N) of psvo_filter_backward (NULL = 0; nparts >= 1 when either is given), added in part order.
  *   With both NULL its outputs equal psvo_filter_backward_wobs bit for bit (that entry point forwards with 0, NULL, NULL).

@@ -1,4 +1,5 @@
-// Small entry points of the C ABI: version/status strings and the per-sequence ELBO reductions.
+// Small entry points of the C ABI: version/status strings and the per-sequence ELBO reductions; and the small kernels that
+// several units launch behind their own (row sum, partial folds, the finalize steps of the reverse passes: common.h).
 #include "common.h"
 
 namespace psvo {
@@ -130,6 +131,202 @@ __global__ void reduce_rows_kernel(const float* __restrict__ part, int nrows, lo
     s = wave_sum(s);
     if (threadIdx.x == 0) out[p] = accumulate ? out[p] + s : s;
 }
+void launch_reduce_rows(const float* part, int nrows, long long stride, int n, float* out, int accumulate, hipStream_t stream) {
+    hipLaunchKernelGGL(reduce_rows_kernel, dim3(n), dim3(64), 0, stream, part, nrows, stride, n, out, accumulate);
+}
+
+// out[r] = sum_l in[r * L + l]: one wave per row, lanes stride over the row and fold with the DPP scan
+__global__ void __launch_bounds__(256) row_sum_kernel(const float* __restrict__ in, long long rows, int L,
+                                                      float* __restrict__ out) {
+    const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    const int lane = threadIdx.x & 63;
+    float s = 0.f;
+    for (int l = lane; l < L; l += 64) s += in[r * L + l];
+    s = wave_sum(s);
+    if (lane == 0) out[r] = s;
+}
+void launch_row_sum(const float* in, long long rows, int L, float* out, hipStream_t stream) {
+    hipLaunchKernelGGL(row_sum_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, in, rows, L, out);
+}
+
+// sacc[b][i] = sum_t part[t][b][i]: one wave per (b, i) strides over t and sums its lanes in a fixed order
+__global__ void __launch_bounds__(256) step_fold_kernel(const float* __restrict__ part, int T, int B, int NACC,
+                                                        float* __restrict__ sacc) {
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int i = wave; i < NACC; i += 4) {
+        float v = 0.f;
+        for (int t = lane; t < T; t += 64) v += part[((size_t)t * B + b) * NACC + i];
+        v = wave_sum(v);
+        if (lane == 0) sacc[(size_t)b * NACC + i] = v;
+    }
+}
+void launch_step_fold(const float* part, int T, int B, int nacc, float* sacc, hipStream_t stream) {
+    hipLaunchKernelGGL(step_fold_kernel, dim3(B), dim3(256), 0, stream, part, T, B, nacc, sacc);
+}
+
+// Filter reverse passes: fold the (B, 10 Dx + Dy) sums into gradients of the scale vectors, sequences in order.
+//   two_q: the product-of-Gaussians step (common.h: pog_scale_grad), sig_q2 collecting both sets;  else: d s1 = Sc
+template <int DX>
+__global__ void filter_bwd_finalize(const float* __restrict__ sacc, int B, int Dy, int two_q, int bootstrap,
+                                    const float* sig_q1, const float* sig_q2, const float* sig0, int same0,
+                                    float* dsig_q1, float* dsig_q2, float* dsig_f, float* dsig_g, float* dsig0,
+                                    float* dfsig0) {
+    using AC = FAcc<DX>;
+    const int NACC = AC::kSg + Dy;
+    // one lane per slot: its total is the serial sum over the sequences, in order; the Dx lanes below take them from LDS
+    // (with the ten sums of a dimension walked by its own lane the filter-only step measured 1 % longer:
+    //  profiles/shared_reverse_helpers.md)
+    __shared__ float tot[10 * DX + 32];
+    for (int i = threadIdx.x; i < NACC; i += 64) {
+        float v = 0.f;
+        for (int b = 0; b < B; ++b) v += sacc[(size_t)b * NACC + i];
+        tot[i] = v;
+    }
+    __syncthreads();
+    const int d = threadIdx.x;
+    if (d < DX) {
+        float ds2 = 0.f;
+        for (int set = 0; set < 2; ++set) {  // set 0: t = 0 (sig0), set 1: t >= 1 (sig_q1)
+            const int P = set * AC::kSet;
+            const float s1 = set ? sig_q1[d] : sig0[d];
+            float ds1;
+            if (two_q) {
+                float d2;
+                pog_scale_grad(s1, sig_q2[d], tot[P + AC::kSc + d], tot[P + AC::kSmm1 + d], tot[P + AC::kSmb + d],
+                               tot[P + AC::kSmm + d], ds1, d2);
+                ds2 += d2;
+            } else {
+                ds1 = tot[P + AC::kSc + d];
+            }
+            const float dfs = tot[P + AC::kSfs + d];
+            if (set) {
+                dsig_q1[d] = ds1 + (bootstrap ? dfs : 0.f);
+                dsig_f[d] = bootstrap ? 0.f : dfs;
+            } else {
+                dsig0[d] = same0 ? ds1 + dfs : ds1;      // (fsig0 aliasing sig0: the sum, as for m0 / fm0)
+                dfsig0[d] = same0 ? 0.f : dfs;
+            }
+        }
+        dsig_q2[d] = ds2;
+    }
+    if (d < Dy) dsig_g[d] = tot[AC::kSg + d];
+}
+int launch_filter_bwd_finalize(int Dx, const FilterFinalizeArgs& a, hipStream_t stream) {
+    return pick_dx(Dx, [&](auto dx) {
+        hipLaunchKernelGGL((filter_bwd_finalize<dx()>), dim3(1), dim3(64), 0, stream, a.sacc, a.B, a.Dy, a.two_q,
+                           a.bootstrap, a.sig_q1, a.sig_q2, a.sig0, a.same0, a.dsig_q1, a.dsig_q2, a.dsig_f, a.dsig_g,
+                           a.dsig0, a.dfsig0);
+        return PSVO_OK;
+    });
+}
+
+// Backward-simulation reverse passes, ONE launch behind the reverse kernel: blocks [0, nfold) add the per-workgroup partials
+// of d Fm / d logW (what the filter's reverse pass waits for) in workgroup order; blocks [nfold, gridDim.x - 1) form d lse;
+// the last block folds the (rows, 7 Dx + Dy) partial sums, rows in (sequence, workgroup) order, into the scale gradients.
+// VEC4: four outputs per thread with 16-byte accesses (the launcher sized the grid for it and checked N % 4 == 0 and the
+// alignment of the four arrays); every output adds its workgroups in the same order either way.
+template <int DX>
+__global__ void __launch_bounds__(256) bsim_bwd_fold_finalize(
+    const float* __restrict__ dFm_part, const float* __restrict__ dlogW_part, long long TB, int nblk, int N, int Dy,
+    float* __restrict__ dFm, float* __restrict__ dlogW, const float* __restrict__ sacc, int rows, const float* sig_q1inv,
+    const float* sig_bq2, float* dsig_f, float* dsig_g, float* dsig_q1inv, float* dsig_bq2, float* dsig_init,
+    float* disig, float* __restrict__ dlse, unsigned nfold, int vec4) {
+    using AC = BAcc<DX>;
+    if (blockIdx.x >= nfold && blockIdx.x + 1 < gridDim.x) {
+        // d lse[t, b] = -sum_j d logW^[t, b, j]: the normaliser's share of the filter term's gradient (W^ = logW - lse).  It is
+        // zero analytically (sum_j d W^_j = sum_m d Lambda_m = 0 per chain) and ~1e-7 of the terms in fp32; TF's autodiff --
+        // like any autodiff of the reference's graph -- carries it, and it is what keeps the filter's reverse pass
+        // well-conditioned when the forward particles have left the data range (the softmax-weighted subtraction in
+        // psvo_filter_backward then cancels the common part of d logW_j exactly instead of to 1e-7: measured on
+        // tests/golden/fhn_illconditioned_state.npz, the emission network's gradient error drops 100 x to the fp32 oracle's).
+        // One wave per (t, b) row, straight from the per-workgroup partials, concurrently with the fold blocks.
+        const long long tb = (long long)(blockIdx.x - nfold) * 4 + (threadIdx.x >> 6);
+        if (tb < TB) {
+            const float* p = dlogW_part + tb * nblk * N;
+            float v = 0.f;
+            for (int i = threadIdx.x & 63; i < nblk * N; i += 64) v += p[i];
+            v = wave_sum(v);
+            if ((threadIdx.x & 63) == 0) dlse[tb] = -v;
+        }
+        return;
+    }
+    if (blockIdx.x + 1 < gridDim.x) {
+        const long long rowF = (long long)DX * N, nF = TB * rowF, nW = TB * N;
+        long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+        if (vec4) {
+            e *= 4;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (e < nF) {
+                const long long tb = e / rowF;
+                const float* p = dFm_part + tb * nblk * rowF + (e - tb * rowF);
+                for (int k = 0; k < nblk; ++k) {
+                    const float4 q = *reinterpret_cast<const float4*>(p + k * rowF);
+                    v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w;
+                }
+                *reinterpret_cast<float4*>(dFm + e) = v;
+            } else if (e < nF + nW) {
+                e -= nF;
+                const long long tb = e / N;
+                const float* p = dlogW_part + tb * nblk * N + (e - tb * N);
+                for (int k = 0; k < nblk; ++k) {
+                    const float4 q = *reinterpret_cast<const float4*>(p + (long long)k * N);
+                    v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w;
+                }
+                *reinterpret_cast<float4*>(dlogW + e) = v;
+            }
+            return;
+        }
+        if (e < nF) {            // d Fm (T, B, Dx, N) from (T, B, nblk, Dx, N)
+            const long long tb = e / rowF;
+            const float* p = dFm_part + tb * nblk * rowF + (e - tb * rowF);
+            float v = 0.f;
+            for (int k = 0; k < nblk; ++k) v += p[k * rowF];
+            dFm[e] = v;
+        } else if (e < nF + nW) {   // d logW (T, B, N) from (T, B, nblk, N)
+            e -= nF;
+            const long long tb = e / N;
+            const float* p = dlogW_part + tb * nblk * N + (e - tb * N);
+            float v = 0.f;
+            for (int k = 0; k < nblk; ++k) v += p[(long long)k * N];
+            dlogW[e] = v;
+        }
+        return;
+    }
+    __shared__ float tot[7 * DX + 32];
+    const int NACC = AC::kSg + Dy;
+    const int d = threadIdx.x, lane = d & 63, wave = d >> 6;
+    for (int k = wave; k < NACC; k += 4) {  // lanes stride over the (sequence, workgroup) rows
+        float v = 0.f;
+        for (int r = lane; r < rows; r += 64) v += sacc[(size_t)r * NACC + k];
+        v = wave_sum(v);
+        if (lane == 0) tot[k] = v;
+    }
+    __syncthreads();
+    if (d < DX) {
+        pog_scale_grad(sig_q1inv[d], sig_bq2[d], tot[AC::kSc + d], tot[AC::kSmm1 + d], tot[AC::kSmb + d], tot[AC::kSmm + d],
+                       dsig_q1inv[d], dsig_bq2[d]);
+        dsig_f[d] = tot[AC::kSf + d];
+        dsig_init[d] = tot[AC::kSinit + d];
+        disig[d] = tot[AC::kSiota + d];
+    }
+    if (d < Dy) dsig_g[d] = tot[AC::kSg + d];
+}
+int launch_bsim_bwd_fold_finalize(int Dx, const BsimFoldArgs& a, hipStream_t stream) {
+    // the 16-byte path only where it can be seen to be sound: whole float4s per row and all four arrays aligned
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(a.dFm_part) | reinterpret_cast<uintptr_t>(a.dlogW_part) |
+                           reinterpret_cast<uintptr_t>(a.dFm) | reinterpret_cast<uintptr_t>(a.dlogW);
+    const int vec4 = (a.N & 3) == 0 && (bits & 15) == 0;
+    const long long TB = (long long)a.T * a.B;
+    const long long n = TB * (Dx + 1) * a.N / (vec4 ? 4 : 1);
+    const unsigned nfold = (unsigned)((n + 255) / 256), nrow = a.dlse ? (unsigned)((TB + 3) / 4) : 0u;
+    return pick_dx(Dx, [&](auto dx) {
+        hipLaunchKernelGGL((bsim_bwd_fold_finalize<dx()>), dim3(nfold + nrow + 1), dim3(256), 0, stream, a.dFm_part,
+                           a.dlogW_part, TB, a.nblk, a.N, a.Dy, a.dFm, a.dlogW, a.sacc, a.rows, a.sig_q1inv, a.sig_bq2,
+                           a.dsig_f, a.dsig_g, a.dsig_q1inv, a.dsig_bq2, a.dsig_init, a.disig, a.dlse, nfold, vec4);
+        return PSVO_OK;
+    });
+}
 
 // sigma = max(softplus(raw), min) with NaN -> 0 first (reference src/distribution/mvn.py:80-90)
 __global__ void sigma_fwd_kernel(const float* __restrict__ raw, const float* __restrict__ mins, float* __restrict__ sig,
@@ -159,8 +356,7 @@ extern "C" int psvo_reduce_rows(const float* part, int nrows, long long stride, 
                                 void* stream) {
     if (!part || !out || nrows <= 0 || n <= 0) return PSVO_ERR_INVALID;
     psvo::clear_hip_error();
-    hipLaunchKernelGGL(psvo::reduce_rows_kernel, dim3(n), dim3(64), 0, static_cast<hipStream_t>(stream), part, nrows,
-                       stride, n, out, accumulate);
+    psvo::launch_reduce_rows(part, nrows, stride, n, out, accumulate, static_cast<hipStream_t>(stream));
     return psvo::launch_status();
 }
 

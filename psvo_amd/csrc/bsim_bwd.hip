@@ -146,19 +146,13 @@ extern "C" int psvo_bsim_backward_fold(const psvo_desc* desc, const float* dFm_p
         !dsig_g || !dsig_q1inv || !dsig_bq2 || !dsig_init || !disig)
         return PSVO_ERR_INVALID;
     if (desc->B <= 0 || desc->T < 2 || desc->N <= 0 || desc->M <= 0) return PSVO_ERR_INVALID;
-    BsimBwdArgs a{};
-    a.B = desc->B; a.T = desc->T; a.N = desc->N;
-    a.dFm_part = const_cast<float*>(dFm_part); a.dlogW_part = const_cast<float*>(dlogW_part);
-    a.sacc_part = const_cast<float*>(sacc_part);
-    a.sig_q1inv = sig_q1inv; a.sig_bq2 = sig_bq2;
-    BsimBwdOut o{dsig_f, dsig_g, dsig_q1inv, dsig_bq2, dsig_init, disig, dFm, dlogW, dlse};
+    if (desc->Dy < 1 || desc->Dy > 2) return PSVO_ERR_UNSUPPORTED;      // (the plain widths; wide ones: psvo_bsim_backward_wobs)
     const int nblk = psvo_bsim_blocks(desc);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    return pick_dx(desc->Dx, [&](auto dx) {
-        return pick_dy(desc->Dy, [&](auto dy) {
-            clear_hip_error();
-            launch_bsim_fold_finalize<decltype(dx)::value, dy()>(a, o, nblk, s);
-            return launch_status();
-        });
-    });
+    if (nblk < 0) return nblk;      // (a descriptor psvo_bsim_blocks refuses is refused here too, before any launch)
+    clear_hip_error();
+    const int st = launch_bsim_bwd_fold_finalize(
+        desc->Dx, {dFm_part, dlogW_part, desc->T, desc->B, nblk, desc->N, desc->Dy, dFm, dlogW, dlse, sacc_part, desc->B * nblk,
+                   sig_q1inv, sig_bq2, dsig_f, dsig_g, dsig_q1inv, dsig_bq2, dsig_init, disig},
+        static_cast<hipStream_t>(stream));
+    return st == PSVO_OK ? launch_status() : st;
 }

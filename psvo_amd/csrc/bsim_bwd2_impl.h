@@ -141,7 +141,8 @@ template <int DX, int DY, int H, int M, int JM>
 __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) {
     using MQ = MlpLds<DX, H, DX, 1>;
     using MG = MlpLds<DX, H, DY, 1>;
-    using AC = BAcc<DX, DY>;
+    using AC = BAcc<DX>;
+    constexpr int kN = AC::kSg + DY;
     constexpr int PS = (JM == 3) ? 20 : (DX == 4 && JM == 0) ? 5 : BTileSlot<DX>::kFloats;   // floats per tile entry
     constexpr int FO = (JM == 3) ? 16 : 0;    // F'_0, F'_1 inside a slot (JM >= 2)
     constexpr int NA = DX + 1;            // per-j accumulators: d F' (DX) and d W^
@@ -346,7 +347,7 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
     //  share a CU at N = 512.)
     constexpr bool kAccLds = (DX >= 3);
     constexpr int kRowsA = 2 * DX + DY, kRowsB = 5 * DX, kSlotsB = 8;      // (at most 8 chains per wave: M = 4)
-    float acc[kAccLds ? 1 : AC::kN];
+    float acc[kAccLds ? 1 : kN];
     float* const accA = red + 16 + wave * (kRowsA * 32 + kRowsB * kSlotsB);     // [nwv][kRowsA][32] + [kRowsB][8]
     float* const accB = accA + kRowsA * 32;
     auto acc_is_lead = [](int k) { return k < 4 * DX || (k >= 5 * DX && k < 6 * DX); };
@@ -359,7 +360,7 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
         for (int i = lane; i < kRowsA * 32 + kRowsB * kSlotsB; i += 64) accA[i] = 0.f;
     } else {
 #pragma unroll
-        for (int i = 0; i < AC::kN; ++i) acc[i] = 0.f;
+        for (int i = 0; i < kN; ++i) acc[i] = 0.f;
     }
     // (every caller is a part-0 lane -- one per (chain, m) -- and the per-chain sums come from the chain's lead lane alone)
     auto acc_add = [&](int k, float v) {
@@ -997,14 +998,14 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
     }
 
     // ---- scalar accumulators: reduce over the workgroup ---------------------------------------------------------------
-    for (int i = 0; i < AC::kN; ++i) {
+    for (int i = 0; i < kN; ++i) {
         float v = 0.f;
         if constexpr (kAccLds) {
             if (acc_is_lead(i)) v = lane < kSlotsB ? accB[acc_row(i) * kSlotsB + lane] : 0.f;
             else v = lane < 32 ? accA[acc_row(i) * 32 + lane] : 0.f;
         } else {
 #pragma unroll
-            for (int k = 0; k < AC::kN; ++k) v = (k == i) ? acc[k] : v;
+            for (int k = 0; k < kN; ++k) v = (k == i) ? acc[k] : v;
         }
         v = wave_sum(v);
         if (lane == 0) red[wave] = v;
@@ -1012,7 +1013,7 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
         if (tid == 0) {
             float s = 0.f;
             for (int w = 0; w < nwv; ++w) s += red[w];
-            as_global(a.sacc_part)[((size_t)b * nblk + blk) * AC::kN + i] = s;
+            as_global(a.sacc_part)[((size_t)b * nblk + blk) * kN + i] = s;
         }
         __syncthreads();
     }

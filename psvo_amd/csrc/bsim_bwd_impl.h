@@ -48,19 +48,6 @@ struct BsimBwdArgs {
     int skew;        // phase offset (shader-clock cycles) of every other resident workgroup: common.h, phase_skew()
 };
 
-template <int DX, int DY>
-struct BAcc {
-    static constexpr int kSc = 0;           // PoG: direct d c
-    static constexpr int kSmm1 = DX;        // sum dmu * mu1
-    static constexpr int kSmb = 2 * DX;     // sum dmu * bmu2
-    static constexpr int kSmm = 3 * DX;     // sum dmu * mu
-    static constexpr int kSf = 4 * DX;      // d sigma_f
-    static constexpr int kSinit = 5 * DX;   // d sigma_init
-    static constexpr int kSiota = 6 * DX;   // d isig
-    static constexpr int kSg = 7 * DX;      // d sigma_g (DY)
-    static constexpr int kN = 7 * DX + DY;
-};
-
 template <int DX>
 struct BTileSlot {
     static constexpr int kFloats = (DX <= 3) ? 4 : 8;
@@ -122,7 +109,8 @@ template <int DX, int DY, int H, int M, int CH, int HS>
 __global__ void __launch_bounds__(256, HS) bsim_bwd_kernel(const BsimBwdArgs a) {
     using MQ = MlpLds<DX, H, DX, PSVO_L>;
     using MG = MlpLds<DX, H, DY, PSVO_L>;
-    using AC = BAcc<DX, DY>;
+    using AC = BAcc<DX>;
+    constexpr int kN = AC::kSg + DY;
     constexpr int PS = BTileSlot<DX>::kFloats;
     constexpr bool kRolled = true;
     constexpr int NA = DX + 1;  // per-j accumulators: dF (DX) and dW
@@ -245,9 +233,9 @@ __global__ void __launch_bounds__(256, HS) bsim_bwd_kernel(const BsimBwdArgs a) 
     }
     __syncthreads();
 
-    float acc[AC::kN];
+    float acc[kN];
 #pragma unroll
-    for (int i = 0; i < AC::kN; ++i) acc[i] = 0.f;
+    for (int i = 0; i < kN; ++i) acc[i] = 0.f;
     float dX[DX];  // d loss / d bwX_t of this chain (all M lanes hold the same value)
 #pragma unroll
     for (int d = 0; d < DX; ++d) dX[d] = 0.f;
@@ -608,133 +596,28 @@ __global__ void __launch_bounds__(256, HS) bsim_bwd_kernel(const BsimBwdArgs a) 
     }
 
     // ---- scalar accumulators: reduce over the workgroup ---------------------------------------------------------------
-    for (int i = 0; i < AC::kN; ++i) {
+    for (int i = 0; i < kN; ++i) {
         float v = 0.f;
 #pragma unroll
-        for (int k = 0; k < AC::kN; ++k) v = (k == i) ? acc[k] : v;
+        for (int k = 0; k < kN; ++k) v = (k == i) ? acc[k] : v;
         v = wave_sum(v);
         if (lane == 0) red[wave] = v;
         __syncthreads();
         if (tid == 0) {
             float s = 0.f;
             for (int w = 0; w < nwv; ++w) s += red[w];
-            a.sacc_part[((size_t)b * nblk + blk) * AC::kN + i] = s;
+            a.sacc_part[((size_t)b * nblk + blk) * kN + i] = s;
         }
         __syncthreads();
     }
 }
 }  // inline namespace PSVO_LNS
 
-// After the reverse kernel, ONE launch: blocks 0 .. gridDim.x - 2 fold the per-workgroup partials of d Fm / d logW (what the
-// filter's reverse pass waits for) in workgroup order; the last block folds the (B * nblk, NACC) partial sums into the scale
-// gradients (see filter_bwd_finalize for the PoG algebra), one accumulator per wave at a time.
-template <int DX, int DY>
-__global__ void __launch_bounds__(256) bsim_bwd_fold_finalize(
-    const float* __restrict__ dFm_part, const float* __restrict__ dlogW_part, long long TB, int nblk, int N,
-    float* __restrict__ dFm, float* __restrict__ dlogW, const float* __restrict__ sacc, int rows, const float* sig_q1inv,
-    const float* sig_bq2, float* dsig_f, float* dsig_g, float* dsig_q1inv, float* dsig_bq2, float* dsig_init,
-    float* disig, float* __restrict__ dlse, unsigned nfold) {
-    using AC = BAcc<DX, DY>;
-    if (blockIdx.x >= nfold && blockIdx.x + 1 < gridDim.x) {
-        // d lse[t, b] = -sum_j d logW^[t, b, j]: the normaliser's share of the filter term's gradient (W^ = logW - lse).  It is
-        // zero analytically (sum_j d W^_j = sum_m d Lambda_m = 0 per chain) and ~1e-7 of the terms in fp32; TF's autodiff --
-        // like any autodiff of the reference's graph -- carries it, and it is what keeps the filter's reverse pass
-        // well-conditioned when the forward particles have left the data range (the softmax-weighted subtraction in
-        // psvo_filter_backward then cancels the common part of d logW_j exactly instead of to 1e-7: measured on
-        // tests/golden/fhn_illconditioned_state.npz, the emission network's gradient error drops 100 x to the fp32 oracle's).
-        // One wave per (t, b) row, straight from the per-workgroup partials, concurrently with the fold blocks.
-        const long long tb = (long long)(blockIdx.x - nfold) * 4 + (threadIdx.x >> 6);
-        if (tb < TB) {
-            const float* p = dlogW_part + tb * nblk * N;
-            float v = 0.f;
-            for (int i = threadIdx.x & 63; i < nblk * N; i += 64) v += p[i];
-            v = wave_sum(v);
-            if ((threadIdx.x & 63) == 0) dlse[tb] = -v;
-        }
-        return;
-    }
-    if (blockIdx.x + 1 < gridDim.x) {
-        const long long rowF = (long long)DX * N, nF = TB * rowF, nW = TB * N;
-        long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-        if ((N & 3) == 0) {      // four outputs per thread (the launcher sized the grid for it): 16-byte loads
-            e *= 4;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (e < nF) {
-                const long long tb = e / rowF;
-                const float* p = dFm_part + tb * nblk * rowF + (e - tb * rowF);
-                for (int k = 0; k < nblk; ++k) {
-                    const float4 q = *reinterpret_cast<const float4*>(p + k * rowF);
-                    v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w;
-                }
-                *reinterpret_cast<float4*>(dFm + e) = v;
-            } else if (e < nF + nW) {
-                e -= nF;
-                const long long tb = e / N;
-                const float* p = dlogW_part + tb * nblk * N + (e - tb * N);
-                for (int k = 0; k < nblk; ++k) {
-                    const float4 q = *reinterpret_cast<const float4*>(p + (long long)k * N);
-                    v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w;
-                }
-                *reinterpret_cast<float4*>(dlogW + e) = v;
-            }
-            return;
-        }
-        if (e < nF) {            // d Fm (T, B, Dx, N) from (T, B, nblk, Dx, N)
-            const long long tb = e / rowF;
-            const float* p = dFm_part + tb * nblk * rowF + (e - tb * rowF);
-            float v = 0.f;
-            for (int k = 0; k < nblk; ++k) v += p[k * rowF];
-            dFm[e] = v;
-        } else if (e < nF + nW) {   // d logW (T, B, N) from (T, B, nblk, N)
-            e -= nF;
-            const long long tb = e / N;
-            const float* p = dlogW_part + tb * nblk * N + (e - tb * N);
-            float v = 0.f;
-            for (int k = 0; k < nblk; ++k) v += p[(long long)k * N];
-            dlogW[e] = v;
-        }
-        return;
-    }
-    __shared__ float tot[AC::kN];
-    const int d = threadIdx.x, lane = d & 63, wave = d >> 6;
-    for (int k = wave; k < AC::kN; k += 4) {  // lanes stride over the (sequence, workgroup) rows
-        float v = 0.f;
-        for (int r = lane; r < rows; r += 64) v += sacc[(size_t)r * AC::kN + k];
-        v = wave_sum(v);
-        if (lane == 0) tot[k] = v;
-    }
-    __syncthreads();
-    auto total = [&](int k) { return tot[k]; };
-    if (d < DX) {
-        const float i1 = 1.f / sig_q1inv[d], i2 = 1.f / sig_bq2[d];
-        const float c = 1.f / (i1 + i2);
-        const float dc = total(AC::kSc + d) + total(AC::kSmm + d) / c;
-        const float di1 = c * total(AC::kSmm1 + d) - c * c * dc;
-        const float di2 = c * total(AC::kSmb + d) - c * c * dc;
-        dsig_q1inv[d] = -i1 * i1 * di1;
-        dsig_bq2[d] = -i2 * i2 * di2;
-        dsig_f[d] = total(AC::kSf + d);
-        dsig_init[d] = total(AC::kSinit + d);
-        disig[d] = total(AC::kSiota + d);
-    }
-    if (d < DY) dsig_g[d] = total(AC::kSg + d);
-}
-
 struct BsimBwdOut {
     float *dsig_f, *dsig_g, *dsig_q1inv, *dsig_bq2, *dsig_init, *disig;
     float *dFm, *dlogW;     // folded over the workgroups (the reverse kernels write a.dFm_part / a.dlogW_part)
-    float* dlse;            // (T,B) or NULL: -sum_j d logW (see bsim_bwd_fold_finalize)
+    float* dlse;            // (T,B) or NULL: -sum_j d logW (api.hip: bsim_bwd_fold_finalize)
 };
-
-template <int DX, int DY>
-static inline void launch_bsim_fold_finalize(const BsimBwdArgs& a, const BsimBwdOut& o, int nblk, hipStream_t stream) {
-    const long long TB = (long long)a.T * a.B;
-    const long long n = TB * (DX + 1) * a.N / ((a.N & 3) == 0 ? 4 : 1);   // (threads: four outputs each when N % 4 == 0)
-    const unsigned nfold = (unsigned)((n + 255) / 256), nrow = o.dlse ? (unsigned)((TB + 3) / 4) : 0u;
-    hipLaunchKernelGGL((bsim_bwd_fold_finalize<DX, DY>), dim3(nfold + nrow + 1), dim3(256), 0, stream,
-                       a.dFm_part, a.dlogW_part, TB, nblk, a.N, o.dFm, o.dlogW, a.sacc_part, a.B * nblk, a.sig_q1inv,
-                       a.sig_bq2, o.dsig_f, o.dsig_g, o.dsig_q1inv, o.dsig_bq2, o.dsig_init, o.disig, o.dlse, nfold);
-}
 
 static inline void bsim_geometry(int B, int N, int M, int H, int Dx, int& HS, int& NTB, int& cpb, int& nblk, int layers = 1) {
     // fewer than two waves per SIMD (1024 SIMDs) with one lane per (chain, m): spread a chain over 2M lanes.
@@ -753,7 +636,6 @@ template <int DX, int DY, int H, int M>
 static int launch_bsim_bwd(const BsimBwdArgs& a, const BsimBwdOut& o, hipStream_t stream) {
     using MQ = MlpLds<DX, H, DX, PSVO_L>;
     using MG = MlpLds<DX, H, DY, PSVO_L>;
-    using AC = BAcc<DX, DY>;
     constexpr int PS = BTileSlot<DX>::kFloats;
     int HS, NTB, cpb, nblk;
     bsim_geometry(a.B, a.N, M, H, DX, HS, NTB, cpb, nblk, PSVO_L);
@@ -777,7 +659,6 @@ static int launch_bsim_bwd(const BsimBwdArgs& a, const BsimBwdOut& o, hipStream_
         hipLaunchKernelGGL((bsim_bwd_kernel<DX, DY, H, M, 16, 1>), dim3(nblk, a.B), dim3(NTB), lds, stream, a);
     }
     (void)o;
-    (void)AC::kN;
     return launch_status();
 }
 

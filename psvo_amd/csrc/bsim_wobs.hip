@@ -17,17 +17,16 @@
 //   * pair phase with j on the lanes of a 16-lane row (bsim_cov.hip): per-item sums (d x~) in registers, reduced over the row
 //     with four DPP rotations; per-j sums (d F'_j, d W^_j) reduced over the four rows with two swap-adds and stored, one
 //     writer per (wave, q, j), into a wave-private LDS copy; the copies are added in wave order into per-workgroup partials
-//     (T,B,nblk,..) in the workspace, which bsim_wobs_fold adds in workgroup order;
+//     (T,B,nblk,..) in the workspace, which bsim_bwd_fold_finalize (api.hip) adds in workgroup order;
 //   * the emission walks the outputs once to write the d G row and the lane's column of d sig_g (LDS, [Dy][lanes], folded in
 //     lane order after the time loop), then reads the row back to accumulate d h for 16 or 32 hidden units at a time -- the
 //     register remedy of the wide reverse filter;
-//   * the other scale sums are per-lane registers folded by wobs::block_sum (lanes by the DPP scan, waves in wave order).
+//   * the other scale sums are per-lane registers folded by block_sum (lanes by the DPP scan, waves in wave order).
 #include "wobs_common.h"
 
 namespace psvo {
 namespace wbs {
 
-using wobs::block_sum;
 using wobs::GLds;
 using wobs::kMaxDy;
 
@@ -43,19 +42,6 @@ static Geom geometry(int N, int M) {
     const int cpb = NTB / M;
     return {NTB, cpb, (N + cpb - 1) / cpb};
 }
-
-// per-workgroup scale sums (BAcc of bsim_bwd_impl.h with a run-time Dy): 7 Dx values, then d sigma_g (Dy)
-template <int DX>
-struct Acc {
-    static constexpr int kSc = 0;           // PoG: direct d c
-    static constexpr int kSmm1 = DX;        // sum dmu * mu1
-    static constexpr int kSmb = 2 * DX;     // sum dmu * bmu2
-    static constexpr int kSmm = 3 * DX;     // sum dmu * mu
-    static constexpr int kSf = 4 * DX;      // d sigma_f
-    static constexpr int kSinit = 5 * DX;   // d sigma_init
-    static constexpr int kSiota = 6 * DX;   // d isig
-    static constexpr int kSg = 7 * DX;      // d sigma_g (Dy)
-};
 
 struct FwdArgs {
     int B, T, N, Dy, emission;
@@ -410,7 +396,7 @@ template <int DX, int H, int M, bool CNT>
 __global__ void __launch_bounds__(256) bsim_wobs_bwd_kernel(const BwdArgs a) {
     using MQ = MlpLds<DX, H, DX, 1>;
     using MG = GLds<DX, H>;
-    using AC = Acc<DX>;
+    using AC = BAcc<DX>;
     constexpr int TS = DX + 1;
     constexpr int NA = DX + 1;                // per-j sums: d F' (DX), d W^
     constexpr int NI = DX + 2;                // floats per item of the pair phase: x' (DX), lam2, d lam
@@ -831,72 +817,6 @@ static size_t bwd_lds_bytes(int N, int NTB, int Dy) {
                             (size_t)nwv * (DX + 1) * NP + 4 * 64 * (DX + 2) + (size_t)Dy * NTB + 12 * DX);
 }
 
-// Adds the per-workgroup partials in workgroup order: blocks [0, nfold) d Fm (T,B,Dx,N) and d logW (T,B,N), blocks
-// [nfold, nfold + nrow) d lse[t,b] = -sum_j d logW[t,b,j] (one wave per row; see bsim_bwd_fold_finalize on why it is passed on),
-// the last block the scale gradients (bsim_bwd_fold_finalize's PoG algebra, rows in (sequence, workgroup) order).
-template <int DX>
-__global__ void __launch_bounds__(256) bsim_wobs_fold(const float* __restrict__ dFm_part, const float* __restrict__ dlogW_part,
-                                                      long long TB, int nblk, int N, int Dy, float* __restrict__ dFm,
-                                                      float* __restrict__ dlogW, float* __restrict__ dlse,
-                                                      const float* __restrict__ sacc, int rows, const float* sig_q1inv,
-                                                      const float* sig_bq2, float* dsig_f, float* dsig_g, float* dsig_q1inv,
-                                                      float* dsig_bq2, float* dsig_init, float* disig, unsigned nfold) {
-    using AC = Acc<DX>;
-    const long long rowF = (long long)DX * N, nF = TB * rowF, nW = TB * N;
-    if (blockIdx.x < nfold) {
-        long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-        if (e < nF) {
-            const long long tb = e / rowF;
-            const float* p = dFm_part + tb * nblk * rowF + (e - tb * rowF);
-            float v = 0.f;
-            for (int k = 0; k < nblk; ++k) v += p[k * rowF];
-            dFm[e] = v;
-        } else if (e < nF + nW) {
-            e -= nF;
-            const long long tb = e / N;
-            const float* p = dlogW_part + tb * nblk * N + (e - tb * N);
-            float v = 0.f;
-            for (int k = 0; k < nblk; ++k) v += p[(long long)k * N];
-            dlogW[e] = v;
-        }
-        return;
-    }
-    if (blockIdx.x + 1 < gridDim.x) {
-        const long long tb = (long long)(blockIdx.x - nfold) * 4 + (threadIdx.x >> 6);
-        if (tb < TB) {
-            const float* p = dlogW_part + tb * nblk * N;
-            float v = 0.f;
-            for (int i = threadIdx.x & 63; i < nblk * N; i += 64) v += p[i];
-            v = wave_sum(v);
-            if ((threadIdx.x & 63) == 0) dlse[tb] = -v;
-        }
-        return;
-    }
-    __shared__ float tot[7 * DX + kMaxDy];
-    const int NACC = 7 * DX + Dy;
-    const int d = threadIdx.x, lane = d & 63, wave = d >> 6;
-    for (int k = wave; k < NACC; k += 4) {      // lanes stride over the (sequence, workgroup) rows
-        float v = 0.f;
-        for (int r = lane; r < rows; r += 64) v += sacc[(size_t)r * NACC + k];
-        v = wave_sum(v);
-        if (lane == 0) tot[k] = v;
-    }
-    __syncthreads();
-    if (d < DX) {
-        const float i1 = 1.f / sig_q1inv[d], i2 = 1.f / sig_bq2[d];
-        const float c = 1.f / (i1 + i2);
-        const float dc = tot[AC::kSc + d] + tot[AC::kSmm + d] / c;
-        const float di1 = c * tot[AC::kSmm1 + d] - c * c * dc;
-        const float di2 = c * tot[AC::kSmb + d] - c * c * dc;
-        dsig_q1inv[d] = -i1 * i1 * di1;
-        dsig_bq2[d] = -i2 * i2 * di2;
-        dsig_f[d] = tot[AC::kSf + d];
-        dsig_init[d] = tot[AC::kSinit + d];
-        disig[d] = tot[AC::kSiota + d];
-    }
-    if (d < Dy) dsig_g[d] = tot[AC::kSg + d];
-}
-
 struct BwdOut {
     float *dFm, *dlogW, *dlse, *dsig_f, *dsig_g, *dsig_q1inv, *dsig_bq2, *dsig_init, *disig;
 };
@@ -909,12 +829,10 @@ static int launch_bwd(const BwdArgs& a, const BwdOut& o, hipStream_t stream) {
     clear_hip_error();
     if (a.emission == 2) hipLaunchKernelGGL((bsim_wobs_bwd_kernel<DX, H, M, true>), dim3(ge.nblk, a.B), dim3(ge.ntb), lds, stream, a);
     else hipLaunchKernelGGL((bsim_wobs_bwd_kernel<DX, H, M, false>), dim3(ge.nblk, a.B), dim3(ge.ntb), lds, stream, a);
-    const long long TB = (long long)a.T * a.B;
-    const long long nel = TB * (DX + 1) * a.N;
-    const unsigned nfold = (unsigned)((nel + 255) / 256), nrow = (unsigned)((TB + 3) / 4);
-    hipLaunchKernelGGL((bsim_wobs_fold<DX>), dim3(nfold + nrow + 1), dim3(256), 0, stream, a.dFm_part, a.dlogW_part, TB, ge.nblk,
-                       a.N, a.Dy, o.dFm, o.dlogW, o.dlse, a.sacc_part, a.B * ge.nblk, a.sig_q1inv, a.sig_bq2, o.dsig_f, o.dsig_g,
-                       o.dsig_q1inv, o.dsig_bq2, o.dsig_init, o.disig, nfold);
+    // (DX is a template value inside the envelope: the status can only be PSVO_OK)
+    (void)launch_bsim_bwd_fold_finalize(DX, {a.dFm_part, a.dlogW_part, a.T, a.B, ge.nblk, a.N, a.Dy, o.dFm, o.dlogW, o.dlse, a.sacc_part,
+                                       a.B * ge.nblk, a.sig_q1inv, a.sig_bq2, o.dsig_f, o.dsig_g, o.dsig_q1inv, o.dsig_bq2,
+                                       o.dsig_init, o.disig}, stream);
     return launch_status();
 }
 

@@ -834,5 +834,160 @@ __device__ __forceinline__ float block_max(float v, float* red, int slot, int wa
     for (int i = 1; i < nw; ++i) m = fmaxf(m, r[i]);
     return m;
 }
+// sum of `v` over the workgroup in a fixed order (lanes by the DPP scan, waves in wave order), result in every lane;
+// `red` has 16 floats
+__device__ __forceinline__ float block_sum(float v, float* red, int wave, int lane, int nw) {
+    v = wave_sum(v);
+    if (nw == 1) return v;
+    if (lane == 0) red[wave] = v;
+    __syncthreads();
+    float s = 0.f;
+    for (int i = 0; i < nw; ++i) s += red[i];
+    __syncthreads();
+    return s;
+}
+
+// ---------------------------------------------------------------------------------------------
+// What the filter and backward-simulation units share around their time loops: the proposal constants of a step, the
+// slots of the scale sums, the product-of-Gaussians step that ends every reverse pass, and the small reductions that
+// run in launches of their own (kernels in api.hip, reached through the host functions declared here).
+// ---------------------------------------------------------------------------------------------
+// proposal / transition constants of a step
+template <int DX>
+struct StepK {
+    float c[DX];    // proposal scale
+    float ic[DX];   // 1 / c
+    float i1[DX];   // 1 / s1
+    float i2[DX];   // 1 / s2 (two_q)
+    float ifs[DX];  // 1 / transition scale
+    float lq, lf;   // -sum(log scale) - D/2 log(2 pi) of proposal / transition
+};
+
+template <int DX>
+__device__ __forceinline__ StepK<DX> make_stepk(const float* s1, const float* s2, const float* fs, bool two_q) {
+    StepK<DX> K;
+    float lq = -DX * kHalfLog2Pi, lf = -DX * kHalfLog2Pi;
+#pragma unroll
+    for (int d = 0; d < DX; ++d) {
+        K.i1[d] = 1.f / s1[d];
+        if (two_q) {
+            K.i2[d] = 1.f / s2[d];
+            K.ic[d] = K.i1[d] + K.i2[d];
+            K.c[d] = 1.f / K.ic[d];
+        } else {
+            K.i2[d] = 0.f;
+            K.ic[d] = K.i1[d];
+            K.c[d] = s1[d];
+        }
+        K.ifs[d] = 1.f / fs[d];
+        lq -= logf(K.c[d]);
+        lf -= logf(fs[d]);
+    }
+    K.lq = lq;
+    K.lf = lf;
+    return K;
+}
+
+// The same constants without lq / lf, for the plain reverse filter kernels, which read neither.  Written out a second time on
+// purpose: handed the full struct, or a copy of its five arrays, those kernels compile to other spills in their two-layer
+// instantiations (the unread members move the register allocation of `K = first ? K0 : K1`), and
+// filter_bwd_lpp_kernel<3, 1, 64> then measured 0.6 % slower (profiles/shared_reverse_helpers.md).  A change of the rule
+// above is a change here.
+template <int DX>
+struct StepKR {
+    float c[DX], ic[DX], i1[DX], i2[DX], ifs[DX];
+};
+template <int DX>
+__device__ __forceinline__ StepKR<DX> make_stepkr(const float* s1, const float* s2, const float* fs, bool two_q) {
+    StepKR<DX> K;
+#pragma unroll
+    for (int d = 0; d < DX; ++d) {
+        K.i1[d] = 1.f / s1[d];
+        if (two_q) {
+            K.i2[d] = 1.f / s2[d];
+            K.ic[d] = K.i1[d] + K.i2[d];
+            K.c[d] = 1.f / K.ic[d];
+        } else {
+            K.i2[d] = 0.f;
+            K.ic[d] = K.i1[d];
+            K.c[d] = s1[d];
+        }
+        K.ifs[d] = 1.f / fs[d];
+    }
+    return K;
+}
+
+// per-sequence scale sums of the reverse filter (psvo_filter_acc_size): per-dimension sums, one set for t = 0 and one for
+// t >= 1, then d sigma_g (Dy values: kSg + Dy slots in all)
+template <int DX>
+struct FAcc {
+    static constexpr int kSc = 0;            // direct d c
+    static constexpr int kSmm1 = DX;         // sum dmu * mean1
+    static constexpr int kSmb = 2 * DX;      // sum dmu * mu2
+    static constexpr int kSmm = 3 * DX;      // sum dmu * mu
+    static constexpr int kSfs = 4 * DX;      // direct d (transition scale)
+    static constexpr int kSet = 5 * DX;
+    static constexpr int kSg = 2 * kSet;     // d sigma_g (Dy)
+};
+
+// per-workgroup scale sums of the reverse backward simulation (psvo_bsim_acc_size; PSVOwR: per cluster member):
+// kSg + Dy slots
+template <int DX>
+struct BAcc {
+    static constexpr int kSc = 0;           // PoG: direct d c
+    static constexpr int kSmm1 = DX;        // sum dmu * mu1
+    static constexpr int kSmb = 2 * DX;     // sum dmu * bmu2
+    static constexpr int kSmm = 3 * DX;     // sum dmu * mu
+    static constexpr int kSf = 4 * DX;      // d sigma_f
+    static constexpr int kSinit = 5 * DX;   // d sigma_init
+    static constexpr int kSiota = 6 * DX;   // d isig
+    static constexpr int kSg = 7 * DX;      // d sigma_g (Dy)
+};
+
+// Product of Gaussians, c = 1 / (1/s1 + 1/s2): gradients of the two scales from the sums of a reverse pass,
+//   d c = Sc + Smm / c;  d(1/s1) = c Smm1 - c^2 dc;  d(1/s2) = c Smb - c^2 dc;  d s = -(1/s)^2 d(1/s)
+// (this expression order is the one every result so far was computed with; the build has -ffp-contract=off)
+__device__ __forceinline__ void pog_scale_grad(float s1, float s2, float Sc, float Smm1, float Smb, float Smm, float& ds1,
+                                               float& ds2) {
+    const float i1 = 1.f / s1, i2 = 1.f / s2;
+    const float c = 1.f / (i1 + i2);
+    const float dc = Sc + Smm / c;
+    const float di1 = c * Smm1 - c * c * dc;
+    const float di2 = c * Smb - c * c * dc;
+    ds1 = -i1 * i1 * di1;
+    ds2 = -i2 * i2 * di2;
+}
+
+// Host side of the shared reductions (api.hip).  None clears or reads the launch status: the caller does.  The two that are
+// instantiated per Dx return PSVO_ERR_UNSUPPORTED, without a launch, for a Dx outside the envelope.
+// out[r] = sum_l in[r * L + l], one wave per row, 4 rows per workgroup
+void launch_row_sum(const float* in, long long rows, int L, float* out, hipStream_t stream);
+// out[p] (+)= sum_r part[r * stride + p], p < n: one wave per output, lanes stride over the rows (psvo_reduce_rows; the
+// weight-gradient folds call it with stride = n)
+void launch_reduce_rows(const float* part, int nrows, long long stride, int n, float* out, int accumulate, hipStream_t stream);
+// sacc[b][i] = sum_t part[t][b][i], i < nacc: the per-step partial sums of the affine-scan reverse filters
+void launch_step_fold(const float* part, int T, int B, int nacc, float* sacc, hipStream_t stream);
+// filter reverse passes: the (B, 10 Dx + Dy) sums into the gradients of the scale vectors, sequences in order
+struct FilterFinalizeArgs {
+    const float* sacc;
+    int B, Dy, two_q, bootstrap;
+    const float *sig_q1, *sig_q2, *sig0;
+    int same0;      // fsig0 is sig0: d sig0 receives both gradients, d fsig0 zeros (as for m0 / fm0)
+    float *dsig_q1, *dsig_q2, *dsig_f, *dsig_g, *dsig0, *dfsig0;
+};
+int launch_filter_bwd_finalize(int Dx, const FilterFinalizeArgs& a, hipStream_t stream);
+// backward-simulation reverse passes, one launch: the per-workgroup partials of d Fm (T,B,nblk,Dx,N) / d logW (T,B,nblk,N)
+// added in workgroup order, d lse[t,b] = -sum_j d logW[t,b,j] (dlse may be null), and the (rows, 7 Dx + Dy) sums into the
+// gradients of the scale vectors
+struct BsimFoldArgs {
+    const float *dFm_part, *dlogW_part;
+    int T, B, nblk, N, Dy;
+    float *dFm, *dlogW, *dlse;
+    const float* sacc;
+    int rows;
+    const float *sig_q1inv, *sig_bq2;
+    float *dsig_f, *dsig_g, *dsig_q1inv, *dsig_bq2, *dsig_init, *disig;
+};
+int launch_bsim_bwd_fold_finalize(int Dx, const BsimFoldArgs& a, hipStream_t stream);
 
 }  // namespace psvo

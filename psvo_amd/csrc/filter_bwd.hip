@@ -35,7 +35,7 @@ struct FilterBwdArgs {
     const float* dlogW_ext;  // (T,B,nparts,N) or null
     float *dP, *dF, *dG, *dmu2, *dm0, *dfm0;
     float* sacc;             // (B, NACC) per-sequence scalar accumulators (see finalize)
-    float* dm2_rows;         // (T,B,Dx,N) per-particle d mu2 rows, summed over N by row_sum_kernel afterwards
+    float* dm2_rows;         // (T,B,Dx,N) per-particle d mu2 rows, summed over N by row_sum_kernel (api.hip) afterwards
     int wave_copies;         // filter_bwd_kernel: one scatter-target copy per wave (set by the launcher when LDS has room)
     float* scanAB;           // affine-scan path: (T,B,N,REC) records (16-byte aligned); part: (T,B,NACC) per-step partial sums
     float* scanPart;
@@ -56,56 +56,6 @@ static FilterWsLayout filter_ws_layout(int B, int T, int N, int Dx, int Dy) {
     return {sums, rec, rec + recs, end + 4 + recs + (long long)T * B * nacc};
 }
 
-template <int DX, int DY>
-struct FAcc {
-    // per-dimension sums, one set for t >= 1 and one for t = 0
-    static constexpr int kSc = 0;            // direct d c
-    static constexpr int kSmm1 = DX;         // sum dmu * mean1
-    static constexpr int kSmb = 2 * DX;      // sum dmu * mu2
-    static constexpr int kSmm = 3 * DX;      // sum dmu * mu
-    static constexpr int kSfs = 4 * DX;      // direct d (transition scale)
-    static constexpr int kSet = 5 * DX;
-    static constexpr int kSg = 2 * kSet;     // d sigma_g (DY)
-    static constexpr int kN = 2 * kSet + DY;
-};
-
-template <int DX>
-struct BStepK {
-    float c[DX], ic[DX], i1[DX], i2[DX], ifs[DX];
-};
-
-template <int DX>
-__device__ __forceinline__ BStepK<DX> make_bstepk(const float* s1, const float* s2, const float* fs, bool two_q) {
-    BStepK<DX> K;
-#pragma unroll
-    for (int d = 0; d < DX; ++d) {
-        K.i1[d] = 1.f / s1[d];
-        if (two_q) {
-            K.i2[d] = 1.f / s2[d];
-            K.ic[d] = K.i1[d] + K.i2[d];
-            K.c[d] = 1.f / K.ic[d];
-        } else {
-            K.i2[d] = 0.f;
-            K.ic[d] = K.i1[d];
-            K.c[d] = s1[d];
-        }
-        K.ifs[d] = 1.f / fs[d];
-    }
-    return K;
-}
-
-// sum of `v` over the whole workgroup, result in every lane; `red` has 16 floats
-__device__ __forceinline__ float block_sum(float v, float* red, int wave, int lane, int nw) {
-    v = wave_sum(v);
-    if (nw == 1) return v;
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    float s = 0.f;
-    for (int i = 0; i < nw; ++i) s += red[i];
-    __syncthreads();
-    return s;
-}
-
 // DET (PSVO_TUNE_DETERMINISTIC, where the launcher finds no room for a double-buffered copy per wave: N > 256): ONE buffer of
 // c = a.det_copies copies (1 <= c <= waves, the most that fit).  Every lane reads and clears its own entries of all copies (in
 // copy order), a barrier, then wave w adds into copy w % c in phase w / c, ceil(waves / c) phases separated by barriers --
@@ -116,7 +66,8 @@ template <int DX, int DY, int H, int MAXT, bool DET = false>
 __global__ void __launch_bounds__(MAXT) filter_bwd_kernel(const FilterBwdArgs a) {
     using MQ = MlpLds<DX, H, DX, PSVO_L>;
     using MG = MlpLds<DX, H, DY, PSVO_L>;
-    using AC = FAcc<DX, DY>;
+    using AC = FAcc<DX>;
+    constexpr int kN = AC::kSg + DY;
     // one wave per SIMD (<= 256 lanes): let the compiler keep the loop-invariant MLP weights in VGPRs
     constexpr bool kRolled = (MAXT > 256) || (MlpLds<DX, H, DX, PSVO_L>::kSize + MlpLds<DX, H, DY, PSVO_L>::kSize > 330);
     constexpr int NBUF = DET ? 1 : 2;     // scatter-target buffers (double-buffered over t; DET: one, behind a barrier)
@@ -156,12 +107,12 @@ __global__ void __launch_bounds__(MAXT) filter_bwd_kernel(const FilterBwdArgs a)
     }
 #pragma unroll
     for (int e = 0; e < DY; ++e) isg[e] = 1.f / a.sig_g[e];
-    const BStepK<DX> K0 = make_bstepk<DX>(s0, sq2, fs0, a.two_q != 0);
-    const BStepK<DX> K1 = make_bstepk<DX>(sq1, sq2, sfv, a.two_q != 0);
+    const StepKR<DX> K0 = make_stepkr<DX>(s0, sq2, fs0, a.two_q != 0);
+    const StepKR<DX> K1 = make_stepkr<DX>(sq1, sq2, sfv, a.two_q != 0);
 
-    float acc[AC::kN];
+    float acc[kN];
 #pragma unroll
-    for (int i = 0; i < AC::kN; ++i) acc[i] = 0.f;
+    for (int i = 0; i < kN; ++i) acc[i] = 0.f;
     float dlnw = 0.f;  // IWAE: gradient w.r.t. the normalised log-weight carried into step t+1
 
     // Per-step inputs are software-prefetched: everything of step t-1 is requested at the top of step t,
@@ -232,7 +183,7 @@ __global__ void __launch_bounds__(MAXT) filter_bwd_kernel(const FilterBwdArgs a)
         SEC(0);
         const size_t tb = (size_t)t * B + b;
         const bool first = (t == 0);
-        const BStepK<DX> K = first ? K0 : K1;
+        const StepKR<DX> K = first ? K0 : K1;
         float inc[AC::kSet];  // this step's contribution to the per-dimension sums (set chosen below)
 #pragma unroll
         for (int i = 0; i < AC::kSet; ++i) inc[i] = 0.f;
@@ -464,9 +415,9 @@ __global__ void __launch_bounds__(MAXT) filter_bwd_kernel(const FilterBwdArgs a)
 
     // ---- per-sequence scalar accumulators ---------------------------------------------------------------
 #pragma unroll
-    for (int i = 0; i < AC::kN; ++i) {
+    for (int i = 0; i < kN; ++i) {
         const float s = block_sum(acc[i], red, wave, lane, nw);
-        if (tid == 0) a.sacc[(size_t)b * AC::kN + i] = s;
+        if (tid == 0) a.sacc[(size_t)b * kN + i] = s;
     }
 }
 
@@ -481,7 +432,8 @@ template <int DX, int DY, int H>
 __global__ void __launch_bounds__(512) filter_bwd_lpp_kernel(const FilterBwdArgs a) {
     using MQ = MlpLds<DX, H, DX, PSVO_L>;
     using MG = MlpLds<DX, H, DY, PSVO_L>;
-    using AC = FAcc<DX, DY>;
+    using AC = FAcc<DX>;
+    constexpr int kN = AC::kSg + DY;
     constexpr int P = 4;
     extern __shared__ __attribute__((aligned(16))) float smem[];
 
@@ -525,12 +477,12 @@ __global__ void __launch_bounds__(512) filter_bwd_lpp_kernel(const FilterBwdArgs
     }
 #pragma unroll
     for (int e = 0; e < DY; ++e) isg[e] = 1.f / a.sig_g[e];
-    const BStepK<DX> K0 = make_bstepk<DX>(s0, sq2, fs0, a.two_q != 0);
-    const BStepK<DX> K1 = make_bstepk<DX>(sq1, sq2, sfv, a.two_q != 0);
+    const StepKR<DX> K0 = make_stepkr<DX>(s0, sq2, fs0, a.two_q != 0);
+    const StepKR<DX> K1 = make_stepkr<DX>(sq1, sq2, sfv, a.two_q != 0);
 
-    float acc[AC::kN];
+    float acc[kN];
 #pragma unroll
-    for (int i = 0; i < AC::kN; ++i) acc[i] = 0.f;
+    for (int i = 0; i < kN; ++i) acc[i] = 0.f;
     float dlnw = 0.f;
 
     float m0r[DX], fm0r[DX];
@@ -675,7 +627,7 @@ __global__ void __launch_bounds__(512) filter_bwd_lpp_kernel(const FilterBwdArgs
         SEC(0);   // (lpp) loop overhead
         const size_t tb = (size_t)t * B + b;
         constexpr bool first = decltype(first_tag)::value;
-        const BStepK<DX> K = first ? K0 : K1;
+        const StepKR<DX> K = first ? K0 : K1;
         float inc[AC::kSet];
 #pragma unroll
         for (int i = 0; i < AC::kSet; ++i) inc[i] = 0.f;
@@ -888,71 +840,10 @@ __global__ void __launch_bounds__(512) filter_bwd_lpp_kernel(const FilterBwdArgs
     step(std::true_type{}, 0);
 
 #pragma unroll
-    for (int i = 0; i < AC::kN; ++i) {
+    for (int i = 0; i < kN; ++i) {
         const float s = block_sum(valid ? acc[i] : 0.f, red, wave, lane, nw);
-        if (tid == 0) a.sacc[(size_t)b * AC::kN + i] = s;
+        if (tid == 0) a.sacc[(size_t)b * kN + i] = s;
     }
-}
-
-// Finalize: fold the (B, NACC) sums into gradients of the scale vectors.
-//   two_q: c = 1/(1/s1 + 1/s2);  d c = Sc + Smm / c;  d(1/s1) = c*Smm1 - c^2 dc;  d(1/s2) = c*Smb - c^2 dc
-//   else : d s1 = Sc
-template <int DX, int DY>
-__global__ void filter_bwd_finalize(const float* __restrict__ sacc, int B, int two_q, int bootstrap,
-                                    const float* sig_q1, const float* sig_q2, const float* sig0, int same0,
-                                    float* dsig_q1, float* dsig_q2, float* dsig_f, float* dsig_g, float* dsig0,
-                                    float* dfsig0) {
-    using AC = FAcc<DX, DY>;
-    const int d = threadIdx.x;
-    if (d < DX) {
-        float S[2 * AC::kSet];
-        for (int i = 0; i < 2 * AC::kSet; ++i) S[i] = 0.f;
-        for (int b = 0; b < B; ++b)
-            for (int i = 0; i < 2 * AC::kSet; ++i) S[i] += sacc[(size_t)b * AC::kN + i];
-        float ds2 = 0.f;
-        for (int set = 0; set < 2; ++set) {  // set 0: t = 0 (sig0), set 1: t >= 1 (sig_q1)
-            const float* P = S + set * AC::kSet;
-            const float s1 = set ? sig_q1[d] : sig0[d];
-            float ds1;
-            if (two_q) {
-                const float i1 = 1.f / s1, i2 = 1.f / sig_q2[d];
-                const float c = 1.f / (i1 + i2);
-                const float dc = P[AC::kSc + d] + P[AC::kSmm + d] / c;
-                const float di1 = c * P[AC::kSmm1 + d] - c * c * dc;
-                const float di2 = c * P[AC::kSmb + d] - c * c * dc;
-                ds1 = -i1 * i1 * di1;
-                ds2 += -i2 * i2 * di2;
-            } else {
-                ds1 = P[AC::kSc + d];
-            }
-            const float dfs = P[AC::kSfs + d];
-            if (set) {
-                dsig_q1[d] = ds1 + (bootstrap ? dfs : 0.f);
-                dsig_f[d] = bootstrap ? 0.f : dfs;
-            } else {
-                dsig0[d] = same0 ? ds1 + dfs : ds1;      // (fsig0 aliasing sig0: the sum, as for m0 / fm0)
-                dfsig0[d] = same0 ? 0.f : dfs;
-            }
-        }
-        dsig_q2[d] = ds2;
-    }
-    if (d < DY) {
-        float s = 0.f;
-        for (int b = 0; b < B; ++b) s += sacc[(size_t)b * AC::kN + AC::kSg + d];
-        dsig_g[d] = s;
-    }
-}
-
-// out[r] = sum_l in[r * L + l]: one wave per row
-__global__ void __launch_bounds__(256) row_sum_kernel(const float* __restrict__ in, long long rows, int L,
-                                                      float* __restrict__ out) {
-    const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= rows) return;
-    const int lane = threadIdx.x & 63;
-    float s = 0.f;
-    for (int l = lane; l < L; l += 64) s += in[r * L + l];
-    s = wave_sum(s);
-    if (lane == 0) out[r] = s;
 }
 
 #if PSVO_L == 1
@@ -974,7 +865,7 @@ __global__ void __launch_bounds__(256) row_sum_kernel(const float* __restrict__ 
 //      again one workgroup per (t, sequence).
 // The persistent kernel spends 7 800 cycles per step on ONE workgroup per sequence (32 of 256 CUs at C*, 8 at C5) and only a
 // quarter of that is MLP arithmetic; here the serial part is ~10 instructions per particle and step.
-// Sums are fixed-order (per-step partials folded over t by fbs_fold_kernel; LDS adds of one wave are applied in lane order).
+// Sums are fixed-order (per-step partials folded over t by step_fold_kernel; LDS adds of one wave are applied in lane order).
 // ---------------------------------------------------------------------------------------------
 // One record per (t, sequence, particle), stored as float4 planes [(t, sequence), float4 index, particle] so that the scan reads it
 // with 16-byte loads that are contiguous over the lanes:
@@ -1170,7 +1061,8 @@ template <int DX, int DY, int H>
 __global__ void __launch_bounds__(512) fbs_rows_kernel(const FilterBwdArgs a) {
     using MQ = MlpLds<DX, H, DX, 1>;
     using MG = MlpLds<DX, H, DY, 1>;
-    using AC = FAcc<DX, DY>;
+    using AC = FAcc<DX>;
+    constexpr int kN = AC::kSg + DY;
     constexpr bool kRolled = true;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, NT = blockDim.x, nw = NT >> 6;
@@ -1190,7 +1082,7 @@ __global__ void __launch_bounds__(512) fbs_rows_kernel(const FilterBwdArgs a) {
         s2[d] = a.two_q ? a.sig_q2[d] : 1.f;
         fs[d] = first ? a.fsig0[d] : a.sig_q1[d];
     }
-    const BStepK<DX> K = make_bstepk<DX>(s1, s2, fs, a.two_q != 0);
+    const StepKR<DX> K = make_stepkr<DX>(s1, s2, fs, a.two_q != 0);
     float x[DX], e[DX], m2[DX], y[DY], mean1[DX], fmean[DX], dPn[DX];
     const int anc = first ? n : a.idx[(tb - B) * N + n];
 #pragma unroll
@@ -1212,9 +1104,9 @@ __global__ void __launch_bounds__(512) fbs_rows_kernel(const FilterBwdArgs a) {
     for (int d = 0; d < DX; ++d) mu[d] = a.two_q ? K.c[d] * fmaf(K.i1[d], mean1[d], K.i2[d] * m2[d]) : mean1[d];
     __syncthreads();
 
-    float acc[AC::kN];
+    float acc[kN];
 #pragma unroll
-    for (int i = 0; i < AC::kN; ++i) acc[i] = 0.f;
+    for (int i = 0; i < kN; ++i) acc[i] = 0.f;
     float inc[AC::kSet];
 #pragma unroll
     for (int i = 0; i < AC::kSet; ++i) inc[i] = 0.f;
@@ -1266,31 +1158,31 @@ __global__ void __launch_bounds__(512) fbs_rows_kernel(const FilterBwdArgs a) {
     for (int i = 0; i < AC::kSet; ++i) acc[(first ? 0 : AC::kSet) + i] = inc[i];
     // ---- this step's partial of the per-sequence sums (fixed order: lanes, then waves) ----------------------------------
 #pragma unroll
-    for (int i = 0; i < AC::kN; ++i) {
+    for (int i = 0; i < kN; ++i) {
         const float v = wave_sum(acc[i]);
-        if (lane == 0) red[wave * AC::kN + i] = v;
+        if (lane == 0) red[wave * kN + i] = v;
     }
     if (first) {
 #pragma unroll
         for (int d = 0; d < DX; ++d) {
             const float v1 = wave_sum(dmean1[d]), v2 = wave_sum(dfmean[d]);
             if (lane == 0) {
-                red[nw * AC::kN + wave * 2 * DX + d] = v1;
-                red[nw * AC::kN + wave * 2 * DX + DX + d] = v2;
+                red[nw * kN + wave * 2 * DX + d] = v1;
+                red[nw * kN + wave * 2 * DX + DX + d] = v2;
             }
         }
     }
     __syncthreads();
-    if (tid < AC::kN) {
+    if (tid < kN) {
         float v = 0.f;
-        for (int w = 0; w < nw; ++w) v += red[w * AC::kN + tid];
-        a.scanPart[tb * AC::kN + tid] = v;
+        for (int w = 0; w < nw; ++w) v += red[w * kN + tid];
+        a.scanPart[tb * kN + tid] = v;
     }
     if (first && tid < DX) {
         float v1 = 0.f, v2 = 0.f;
         for (int w = 0; w < nw; ++w) {
-            v1 += red[nw * AC::kN + w * 2 * DX + tid];
-            v2 += red[nw * AC::kN + w * 2 * DX + DX + tid];
+            v1 += red[nw * kN + w * 2 * DX + tid];
+            v2 += red[nw * kN + w * 2 * DX + DX + tid];
         }
         const bool same0 = (a.fm0 == a.m0);
         a.dm0[b * DX + tid] = same0 ? v1 + v2 : v1;
@@ -1298,23 +1190,12 @@ __global__ void __launch_bounds__(512) fbs_rows_kernel(const FilterBwdArgs a) {
     }
 }
 
-// sacc[b][i] = sum_t part[t][b][i]: one wave per (b, i) strides over t and sums its lanes in a fixed order
-__global__ void __launch_bounds__(256) fbs_fold_kernel(const float* __restrict__ part, int T, int B, int NACC,
-                                                       float* __restrict__ sacc) {
-    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int i = wave; i < NACC; i += 4) {
-        float v = 0.f;
-        for (int t = lane; t < T; t += 64) v += part[((size_t)t * B + b) * NACC + i];
-        v = wave_sum(v);
-        if (lane == 0) sacc[(size_t)b * NACC + i] = v;
-    }
-}
-
 template <int DX, int DY, int H>
 static void launch_filter_bwd_scan(const FilterBwdArgs& a, hipStream_t stream) {
     using MQ = MlpLds<DX, H, DX, 1>;
     using MG = MlpLds<DX, H, DY, 1>;
-    using AC = FAcc<DX, DY>;
+    using AC = FAcc<DX>;
+    constexpr int kN = AC::kSg + DY;
     const int NT = (a.N + 63) & ~63;
     const size_t ldsw = sizeof(float) * (MQ::kSize + MG::kSize);
     hipLaunchKernelGGL((fbs_coeff_kernel<DX, DY, H>), dim3(a.T, a.B), dim3(NT), ldsw, stream, a);
@@ -1325,9 +1206,9 @@ static void launch_filter_bwd_scan(const FilterBwdArgs& a, hipStream_t stream) {
     else if (a.N <= 128) hipLaunchKernelGGL((fbs_scan_kernel<DX, 1, 2, D2>), dim3(a.B), dim3(64), ldss, stream, a);
     else if (a.N <= 256) hipLaunchKernelGGL((fbs_scan_kernel<DX, 4, 1, D1>), dim3(a.B), dim3(256), ldss, stream, a);
     else hipLaunchKernelGGL((fbs_scan_kernel<DX, 4, 2, D2>), dim3(a.B), dim3(256), ldss, stream, a);
-    const size_t ldsr = ldsw + sizeof(float) * ((NT / 64) * (AC::kN + 2 * DX) + 16);
+    const size_t ldsr = ldsw + sizeof(float) * ((NT / 64) * (kN + 2 * DX) + 16);
     hipLaunchKernelGGL((fbs_rows_kernel<DX, DY, H>), dim3(a.T, a.B), dim3(NT), ldsr, stream, a);
-    hipLaunchKernelGGL(fbs_fold_kernel, dim3(a.B), dim3(256), 0, stream, a.scanPart, a.T, a.B, AC::kN, a.sacc);
+    launch_step_fold(a.scanPart, a.T, a.B, kN, a.sacc, stream);
 }
 #endif   // PSVO_L == 1
 
@@ -1386,12 +1267,11 @@ static int launch_filter_bwd(const FilterBwdArgs& a, const FilterBwdOut& o, hipS
     else
         hipLaunchKernelGGL((filter_bwd_kernel<DX, DY, H, 512>), dim3(a.B), dim3(NT), lds, stream, aw);
     if (a.two_q) {
-        const long long rows = (long long)a.T * a.B * DX;
-        hipLaunchKernelGGL(row_sum_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, a.dm2_rows, rows,
-                           a.N, a.dmu2);
+        launch_row_sum(a.dm2_rows, (long long)a.T * a.B * DX, a.N, a.dmu2, stream);
     }
-    hipLaunchKernelGGL((filter_bwd_finalize<DX, DY>), dim3(1), dim3(64), 0, stream, a.sacc, a.B, a.two_q, a.bootstrap,
-                       a.sig_q1, a.sig_q2, a.sig0, (int)(a.fsig0 == a.sig0), o.dsig_q1, o.dsig_q2, o.dsig_f, o.dsig_g, o.dsig0, o.dfsig0);
+    // (DX is a template value inside the envelope: the status can only be PSVO_OK)
+    (void)launch_filter_bwd_finalize(DX, {a.sacc, a.B, DY, a.two_q, a.bootstrap, a.sig_q1, a.sig_q2, a.sig0, (int)(a.fsig0 == a.sig0),
+                                    o.dsig_q1, o.dsig_q2, o.dsig_f, o.dsig_g, o.dsig0, o.dfsig0}, stream);
     return launch_status();
 }
 

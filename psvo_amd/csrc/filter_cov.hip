@@ -300,17 +300,6 @@ struct BwdArgs {
     int det_copies;    // filter_cov_bwd_kernel<.., DET = true>: scatter-target copies, 1 .. waves (filter_bwd.hip)
 };
 
-__device__ __forceinline__ float block_sum(float v, float* red, int wave, int lane, int nw) {
-    v = wave_sum(v);
-    if (nw == 1) return v;
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    float s = 0.f;
-    for (int i = 0; i < nw; ++i) s += red[i];
-    __syncthreads();
-    return s;
-}
-
 // DET (PSVO_TUNE_DETERMINISTIC): the scatter targets in ONE buffer of a.det_copies copies instead of one double-buffered shared
 // copy, added into in phases -- the scheme of psvo::l1::filter_bwd_kernel<.., DET = true> (filter_bwd.hip), which see.
 template <int DX, int DY, int H, int MAXT, bool DET = false>
@@ -670,18 +659,6 @@ __global__ void cov_finalize(const float* __restrict__ sacc, int B, int DX, int 
     if (i < DX) dsc_q1[i] = s;
     else if (i < 2 * DX) { if (!bootstrap && dsc_f) dsc_f[i - DX] = s; }
     else dsc_g[i - 2 * DX] = s;
-}
-
-// out[r] = sum_l in[r * L + l]: one wave per row
-__global__ void __launch_bounds__(256) cov_row_sum(const float* __restrict__ in, long long rows, int L,
-                                                   float* __restrict__ out) {
-    const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= rows) return;
-    const int lane = threadIdx.x & 63;
-    float s = 0.f;
-    for (int l = lane; l < L; l += 64) s += in[r * L + l];
-    s = wave_sum(s);
-    if (lane == 0) out[r] = s;
 }
 
 template <int DX, int DY, int H>
@@ -1062,17 +1039,6 @@ __global__ void __launch_bounds__(512) fcs_rows_kernel(const BwdArgs a) {
     }
 }
 
-// sacc[b][i] = sum_t part[t][b][i]: one wave per (b, i)
-__global__ void __launch_bounds__(256) fcs_fold_kernel(const float* __restrict__ part, int T, int B, int NA, float* __restrict__ sacc) {
-    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int i = wave; i < NA; i += 4) {
-        float v = 0.f;
-        for (int t = lane; t < T; t += 64) v += part[((size_t)t * B + b) * NA + i];
-        v = wave_sum(v);
-        if (lane == 0) sacc[(size_t)b * NA + i] = v;
-    }
-}
-
 template <int DX, int DY, int H>
 static void launch_bwd_scan(const BwdArgs& a, hipStream_t stream) {
     using MQ = MlpLds<DX, H, 2 * DX, 1>;
@@ -1089,7 +1055,7 @@ static void launch_bwd_scan(const BwdArgs& a, hipStream_t stream) {
     else hipLaunchKernelGGL((fcs_scan_kernel<DX, 4, 2, D2>), dim3(a.B), dim3(256), ldss, stream, a);
     const size_t ldsr = ldsw + sizeof(float) * ((NT / 64) * (2 * DX + DY + 4 * DX) + 16);
     hipLaunchKernelGGL((fcs_rows_kernel<DX, DY, H>), dim3(a.T, a.B), dim3(NT), ldsr, stream, a);
-    hipLaunchKernelGGL(fcs_fold_kernel, dim3(a.B), dim3(256), 0, stream, a.scanPart, a.T, a.B, 2 * DX + DY, a.sacc);
+    launch_step_fold(a.scanPart, a.T, a.B, 2 * DX + DY, a.sacc, stream);
 }
 
 struct BwdOut {
@@ -1121,9 +1087,8 @@ static int launch_bwd(const BwdArgs& a, const BwdOut& o, hipStream_t stream) {
     else hipLaunchKernelGGL((filter_cov_bwd_kernel<DX, DY, H, 512>), dim3(a.B), dim3(NT), lds, stream, a);
     if (a.two_q) {
         const long long rows = (long long)a.T * a.B * DX;
-        const unsigned nb = (unsigned)((rows + 3) / 4);
-        hipLaunchKernelGGL(cov_row_sum, dim3(nb), dim3(256), 0, stream, a.dm2_rows, rows, a.N, o.dmu2);
-        hipLaunchKernelGGL(cov_row_sum, dim3(nb), dim3(256), 0, stream, a.ds2_rows, rows, a.N, o.dsig2);
+        launch_row_sum(a.dm2_rows, rows, a.N, o.dmu2, stream);
+        launch_row_sum(a.ds2_rows, rows, a.N, o.dsig2, stream);
     }
     hipLaunchKernelGGL(cov_finalize, dim3(1), dim3(64), 0, stream, a.sacc, a.B, DX, DY, a.bootstrap, o.dsc_q1, o.dsc_f,
                        o.dsc_g);

@@ -27,41 +27,6 @@ struct FilterArgs {
     float* lse;
 };
 
-template <int DX>
-struct StepK {
-    float c[DX];    // proposal scale
-    float ic[DX];   // 1 / c
-    float i1[DX];   // 1 / s1
-    float i2[DX];   // 1 / s2 (two_q)
-    float ifs[DX];  // 1 / transition scale
-    float lq, lf;   // -sum(log scale) - D/2 log(2 pi) of proposal / transition
-};
-
-template <int DX>
-__device__ __forceinline__ StepK<DX> make_stepk(const float* s1, const float* s2, const float* fs, bool two_q) {
-    StepK<DX> K;
-    float lq = -DX * kHalfLog2Pi, lf = -DX * kHalfLog2Pi;
-#pragma unroll
-    for (int d = 0; d < DX; ++d) {
-        K.i1[d] = 1.f / s1[d];
-        if (two_q) {
-            K.i2[d] = 1.f / s2[d];
-            K.ic[d] = K.i1[d] + K.i2[d];
-            K.c[d] = 1.f / K.ic[d];
-        } else {
-            K.i2[d] = 0.f;
-            K.ic[d] = K.i1[d];
-            K.c[d] = s1[d];
-        }
-        K.ifs[d] = 1.f / fs[d];
-        lq -= logf(K.c[d]);
-        lf -= logf(fs[d]);
-    }
-    K.lq = lq;
-    K.lf = lf;
-    return K;
-}
-
 // EM: emission variant fixed at compile time (0 / 1) or read from the arguments (2).  The one-wave-per-SIMD build
 // (MAXT = 256) keeps every MLP weight in VGPRs only without the extra branch in its time loop, so it is compiled both ways.
 template <int DX, int DY, int H, int MAXT, int EM = 2>

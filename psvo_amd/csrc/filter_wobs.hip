@@ -20,38 +20,6 @@
 namespace psvo {
 namespace wobs {
 
-// proposal / transition constants of a step (filter_fwd.hip: StepK)
-template <int DX>
-struct StepK {
-    float c[DX], ic[DX], i1[DX], i2[DX], ifs[DX];
-    float lq, lf;
-};
-
-template <int DX>
-__device__ __forceinline__ StepK<DX> make_stepk(const float* s1, const float* s2, const float* fs, bool two_q) {
-    StepK<DX> K;
-    float lq = -DX * kHalfLog2Pi, lf = -DX * kHalfLog2Pi;
-#pragma unroll
-    for (int d = 0; d < DX; ++d) {
-        K.i1[d] = 1.f / s1[d];
-        if (two_q) {
-            K.i2[d] = 1.f / s2[d];
-            K.ic[d] = K.i1[d] + K.i2[d];
-            K.c[d] = 1.f / K.ic[d];
-        } else {
-            K.i2[d] = 0.f;
-            K.ic[d] = K.i1[d];
-            K.c[d] = s1[d];
-        }
-        K.ifs[d] = 1.f / fs[d];
-        lq -= logf(K.c[d]);
-        lf -= logf(fs[d]);
-    }
-    K.lq = lq;
-    K.lf = lf;
-    return K;
-}
-
 struct FwdArgs {
     int B, T, N, Dy;
     int resample, two_q, bootstrap, emission;
@@ -329,7 +297,7 @@ static int launch_fwd(const FwdArgs& a, hipStream_t stream) {
 // Reverse filter (filter_bwd.hip's persistent kernel; upstream gradients: d lse and, through the _ext entry point, d Fm / d logW).  One workgroup per sequence walks
 // t = T-1 .. 0.  What step t leaves for step t-1 is D[n] = d loss / d (MLP_q1(x_{t-1}[n]), MLP_f(x_{t-1}[n])), carried in the
 // parent's own registers: the children stage (ancestor, values) in LDS and every parent adds its children in child order.
-// Per-sequence sums (FAcc of filter_bwd.hip with a run-time Dy): [2 sets x 5 Dx | Dy].
+// Per-sequence sums (common.h: FAcc): [2 sets x 5 Dx | Dy].
 // ---------------------------------------------------------------------------------------------
 struct BwdArgs {
     int B, T, N, Dy;
@@ -360,23 +328,12 @@ __device__ __forceinline__ int arg_nparts() {
     return *(iptr)((kptr)__builtin_amdgcn_kernarg_segment_ptr() + off);
 }
 
-template <int DX>
-struct Acc {
-    static constexpr int kSc = 0;            // direct d c
-    static constexpr int kSmm1 = DX;         // sum dmu * mean1
-    static constexpr int kSmb = 2 * DX;      // sum dmu * mu2
-    static constexpr int kSmm = 3 * DX;      // sum dmu * mu
-    static constexpr int kSfs = 4 * DX;      // direct d (transition scale)
-    static constexpr int kSet = 5 * DX;
-    static constexpr int kSg = 2 * kSet;     // d sigma_g (Dy)
-};
-
 // CNT: the count emission (as in the forward kernel); its d G rows are dlw (y / lam - 1) sigmoid(r), there is no d sig_g
 template <int DX, int H, bool EXT, bool CNT>
 __global__ void __launch_bounds__(512) filter_bwd_wobs_kernel(const BwdArgs a) {
     using MQ = MlpLds<DX, H, DX, 1>;
     using MG = GLds<DX, H>;
-    using AC = Acc<DX>;
+    using AC = FAcc<DX>;
     extern __shared__ __attribute__((aligned(16))) float smem[];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -675,68 +632,6 @@ __global__ void __launch_bounds__(512) filter_bwd_wobs_kernel(const BwdArgs a) {
     }
 }
 
-// Fold the (B, 10 Dx + Dy) sums into gradients of the scale vectors, sequences in order (filter_bwd.hip: filter_bwd_finalize)
-template <int DX>
-__global__ void filter_bwd_wobs_finalize(const float* __restrict__ sacc, int B, int Dy, int two_q, int bootstrap,
-                                         const float* sig_q1, const float* sig_q2, const float* sig0, int same0,
-                                         float* dsig_q1, float* dsig_q2, float* dsig_f, float* dsig_g, float* dsig0,
-                                         float* dfsig0) {
-    using AC = Acc<DX>;
-    const int NACC = 2 * AC::kSet + Dy;
-    const int d = threadIdx.x;
-    if (d < DX) {
-        // (sums read where they are used: an array indexed by the thread's d would live in scratch)
-        auto S = [&](int i) {
-            float v = 0.f;
-            for (int b = 0; b < B; ++b) v += sacc[(size_t)b * NACC + i];
-            return v;
-        };
-        float ds2 = 0.f;
-        for (int set = 0; set < 2; ++set) {  // set 0: t = 0 (sig0), set 1: t >= 1 (sig_q1)
-            const int P = set * AC::kSet;
-            const float s1 = set ? sig_q1[d] : sig0[d];
-            float ds1;
-            if (two_q) {
-                const float i1 = 1.f / s1, i2 = 1.f / sig_q2[d];
-                const float c = 1.f / (i1 + i2);
-                const float dc = S(P + AC::kSc + d) + S(P + AC::kSmm + d) / c;
-                const float di1 = c * S(P + AC::kSmm1 + d) - c * c * dc;
-                const float di2 = c * S(P + AC::kSmb + d) - c * c * dc;
-                ds1 = -i1 * i1 * di1;
-                ds2 += -i2 * i2 * di2;
-            } else {
-                ds1 = S(P + AC::kSc + d);
-            }
-            const float dfs = S(P + AC::kSfs + d);
-            if (set) {
-                dsig_q1[d] = ds1 + (bootstrap ? dfs : 0.f);
-                dsig_f[d] = bootstrap ? 0.f : dfs;
-            } else {
-                dsig0[d] = same0 ? ds1 + dfs : ds1;      // (fsig0 aliasing sig0: the sum, as for m0 / fm0)
-                dfsig0[d] = same0 ? 0.f : dfs;
-            }
-        }
-        dsig_q2[d] = ds2;
-    }
-    if (d < Dy) {
-        float s = 0.f;
-        for (int b = 0; b < B; ++b) s += sacc[(size_t)b * NACC + AC::kSg + d];
-        dsig_g[d] = s;
-    }
-}
-
-// out[r] = sum_l in[r * L + l]: one wave per row, lanes stride over the row and fold with the DPP scan
-__global__ void __launch_bounds__(256) wobs_row_sum_kernel(const float* __restrict__ in, long long rows, int L,
-                                                           float* __restrict__ out) {
-    const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= rows) return;
-    const int lane = threadIdx.x & 63;
-    float s = 0.f;
-    for (int l = lane; l < L; l += 64) s += in[r * L + l];
-    s = wave_sum(s);
-    if (lane == 0) out[r] = s;
-}
-
 struct BwdOut {
     float *dsig_q1, *dsig_q2, *dsig_f, *dsig_g, *dsig0, *dfsig0;
 };
@@ -761,13 +656,11 @@ static int launch_bwd(const BwdArgs& a, const BwdOut& o, hipStream_t stream) {
         else hipLaunchKernelGGL((filter_bwd_wobs_kernel<DX, H, false, false>), dim3(a.B), dim3(NT), lds, stream, a);
     }
     if (a.two_q) {
-        const long long rows = (long long)a.T * a.B * DX;
-        hipLaunchKernelGGL(wobs_row_sum_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, a.dm2_rows, rows,
-                           a.N, a.dmu2);
+        launch_row_sum(a.dm2_rows, (long long)a.T * a.B * DX, a.N, a.dmu2, stream);
     }
-    hipLaunchKernelGGL((filter_bwd_wobs_finalize<DX>), dim3(1), dim3(64), 0, stream, a.sacc, a.B, a.Dy, a.two_q, a.bootstrap,
-                       a.sig_q1, a.sig_q2, a.sig0, (int)(a.fsig0 == a.sig0), o.dsig_q1, o.dsig_q2, o.dsig_f, o.dsig_g,
-                       o.dsig0, o.dfsig0);
+    // (DX is a template value inside the envelope: the status can only be PSVO_OK)
+    (void)launch_filter_bwd_finalize(DX, {a.sacc, a.B, a.Dy, a.two_q, a.bootstrap, a.sig_q1, a.sig_q2, a.sig0, (int)(a.fsig0 == a.sig0),
+                                    o.dsig_q1, o.dsig_q2, o.dsig_f, o.dsig_g, o.dsig0, o.dfsig0}, stream);
     return launch_status();
 }
 
@@ -790,7 +683,7 @@ static int dispatch_dx_h(int Dx, int H, F&& f) {
 //             beyond the last row: such rows and columns contribute nothing), x -> xs, db2 in registers;
 //   1 (MFMA)  wave w: dh of rows 16 w .. 16 w + 15 = Ds W2s (K = DP); in the accumulator layout: mask, db1, dW1 (registers);
 //   2 (MFMA)  dW2 tiles (16 units x 16 outputs, K = the 64 rows), dealt round-robin to the waves, accumulators persistent.
-// One partial per workgroup, folded in block order by wobs_reduce_partials_kernel.
+// One partial per workgroup, folded in block order by reduce_rows_kernel (api.hip).
 // MFMA operand layout (lane = 16 lg + li): A[i = li][k = lg], B[k = lg][j = li], D[i = 4 lg + r][j = li].
 // ---------------------------------------------------------------------------------------------
 struct WgradArgs {
@@ -978,23 +871,13 @@ __global__ void __launch_bounds__(256) mlp_wgrad_wobs_kernel(const WgradArgs a) 
     }
 }
 
-// out[p] (+)= sum_blk partial[blk][p]: one wave per output element, lanes stride over the blocks (fixed order)
-__global__ void wobs_reduce_partials_kernel(const float* __restrict__ partial, int nblk, int NP, float* __restrict__ out,
-                                            int accumulate) {
-    const int p = blockIdx.x;
-    float s = 0.f;
-    for (int b = threadIdx.x; b < nblk; b += 64) s += partial[(size_t)b * NP + p];
-    s = wave_sum(s);
-    if (threadIdx.x == 0) out[p] = accumulate ? out[p] + s : s;
-}
-
 template <int DIN, int H, int NOT>
 static int launch_wgrad(const WgradArgs& a, int nblk, float* out, int accumulate, hipStream_t s) {
     const int NP = DIN * H + H + H * a.Dout + a.Dout;
     const size_t lds = sizeof(float) * WgradLds<DIN, H, NOT>::kSize;
     clear_hip_error();
     hipLaunchKernelGGL((mlp_wgrad_wobs_kernel<DIN, H, NOT>), dim3(nblk), dim3(256), lds, s, a);
-    hipLaunchKernelGGL(wobs_reduce_partials_kernel, dim3(NP), dim3(64), 0, s, a.partial, nblk, NP, out, accumulate);
+    launch_reduce_rows(a.partial, nblk, NP, NP, out, accumulate, s);      // (workgroups in order)
     return launch_status();
 }
 

@@ -311,17 +311,6 @@ static bool wgrad_old_kernel() {
 }
 
 
-// out[p] (+)= sum_blk partial[blk][p]: one wave per output element, lanes stride over the blocks
-// (fixed order, deterministic)
-__global__ void reduce_partials_kernel(const float* __restrict__ partial, int nblk, int NP, float* __restrict__ out,
-                                       int accumulate) {
-    const int p = blockIdx.x;
-    float s = 0.f;
-    for (int b = threadIdx.x; b < nblk; b += 64) s += partial[(size_t)b * NP + p];
-    s = wave_sum(s);
-    if (threadIdx.x == 0) out[p] = accumulate ? out[p] + s : s;
-}
-
 template <int DIN, int DOUT>
 static int launch_wgrad(const WgradArgs& a, int H, int nblk, float* out, int accumulate, hipStream_t s) {
     const int NP = DIN * H + H + H * DOUT + DOUT;
@@ -333,7 +322,7 @@ static int launch_wgrad(const WgradArgs& a, int H, int nblk, float* out, int acc
         const int sh = ncol % 4 == 0 ? 2 : ncol % 2 == 0 ? 1 : 0;
         hipLaunchKernelGGL((mlp_wgrad_cols_kernel<DIN, DOUT>), dim3(nblk, ncol >> sh), dim3(256), 0, s, a, H, sh);
     }
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(NP), dim3(64), 0, s, a.partial, nblk, NP, out, accumulate);
+    launch_reduce_rows(a.partial, nblk, NP, NP, out, accumulate, s);      // (workgroups in order)
     return launch_status();
 }
 
@@ -358,7 +347,7 @@ static int wgrad_dispatch_out(const WgradArgs& a, int H, int Dout, int nblk, flo
 //             in the accumulator layout: h2, d pre2 = [pre2 > 0] (dOut W2^T) -> LDS, dW2 += h2^T dOut, dbh += d pre2
 //   2 (MFMA)  d h1 = (d pre2) Wh^T ; * [h1 > 0] ; dW1 += x^T d h1, db1 += d h1   (accumulator layout, registers)
 //   3 (MFMA)  dWh += h1^T (d pre2)  (K = the 64 rows of the chunk), accumulators persistent over the chunks
-// and writes one partial per workgroup, folded by reduce_partials_kernel (fixed order, no atomics).
+// and writes one partial per workgroup, folded by reduce_rows_kernel (api.hip: fixed order, no atomics).
 // Output layout (keras order hidden_0, hidden_1, mu_layer): [dW1 (DIN,H) | db1 (H) | dWh (H,H) | dbh (H) | dW2 (H,DOUT) | db2].
 // ---------------------------------------------------------------------------------------------
 typedef float wg_f4 __attribute__((ext_vector_type(4)));
@@ -893,7 +882,7 @@ static int launch_wgrad2(const WgradArgs& a, int H, int nblk, float* out, int ac
         else launch_wgrad2_bf16<DIN, DOUT, 64, 3>(a, nblk, s);
     } else if (H == 32) hipLaunchKernelGGL((mlp2_wgrad_kernel<DIN, DOUT, 32>), dim3(nblk), dim3(256), lds, s, a);
     else hipLaunchKernelGGL((mlp2_wgrad_kernel<DIN, DOUT, 64>), dim3(nblk), dim3(256), lds, s, a);
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(NP2), dim3(64), 0, s, a.partial, nblk, NP2, out, accumulate);
+    launch_reduce_rows(a.partial, nblk, NP2, NP2, out, accumulate, s);
     return launch_status();
 }
 

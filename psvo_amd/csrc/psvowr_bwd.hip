@@ -59,12 +59,6 @@ static inline int wb_depth(int T) { return T < kWbDepth ? T : kWbDepth; }
 static inline long long wb_ring_floats(int B, int T, int N) { return 2ll * ((long long)wb_depth(T) * B * N * kWbWords); }
 static inline long long wb_ws_floats(int B, int T, int N) { return wb_ring_floats(B, T, N) + (long long)B * kWbProg + 2; }
 
-template <int DX, int DY>
-struct WAcc {   // same slots as BAcc in bsim_bwd_impl.h (shares bsim_bwd_finalize's algebra)
-    static constexpr int kSc = 0, kSmm1 = DX, kSmb = 2 * DX, kSmm = 3 * DX, kSf = 4 * DX, kSinit = 5 * DX,
-                         kSiota = 6 * DX, kSg = 7 * DX, kN = 7 * DX + DY;
-};
-
 template <int DX>
 struct WbSlot {
     static constexpr int kFloats = (DX <= 3) ? 4 : 8;
@@ -110,7 +104,8 @@ template <int DX, int DY, int H, int M, int MAXT>
 __global__ void __launch_bounds__(MAXT) psvowr_bwd_kernel(const WrBwdArgs a) {
     using MQ = MlpLds<DX, H, DX, PSVO_L>;
     using MG = MlpLds<DX, H, DY, PSVO_L>;
-    using AC = WAcc<DX, DY>;
+    using AC = BAcc<DX>;
+    constexpr int kN = AC::kSg + DY;
     constexpr int PS = WbSlot<DX>::kFloats;
     constexpr bool kRolled = (MAXT > 256) || (H > 32) || (DX > 2);   // small MLPs: unrolled, their LDS reads overlap
     constexpr int NA = DX + 1;
@@ -250,9 +245,9 @@ __global__ void __launch_bounds__(MAXT) psvowr_bwd_kernel(const WrBwdArgs a) {
         }
     };
 
-    float acc[AC::kN];
+    float acc[kN];
 #pragma unroll
-    for (int i = 0; i < AC::kN; ++i) acc[i] = 0.f;
+    for (int i = 0; i < kN; ++i) acc[i] = 0.f;
     const int nq = NP >> 2;
     constexpr int b0 = 2, b1 = 3, b2 = 4, b3 = 5;   // quad-index bits of the lane id
     const int ebase = ((lane >> b0) & 1) * (CH / 2) + ((lane >> b1) & 1) * (CH / 4) + ((lane >> b2) & 1) * (CH / 8) +
@@ -644,45 +639,41 @@ __global__ void __launch_bounds__(MAXT) psvowr_bwd_kernel(const WrBwdArgs a) {
         SEC(7);   // per-workgroup partials of d Fm / d logW / d lse, barrier
     }
 
-    for (int i = 0; i < AC::kN; ++i) {
+    for (int i = 0; i < kN; ++i) {
         float v = 0.f;
 #pragma unroll
-        for (int k = 0; k < AC::kN; ++k) v = (k == i) ? acc[k] : v;
+        for (int k = 0; k < kN; ++k) v = (k == i) ? acc[k] : v;
         v = wave_sum(v);
         if (lane == 0) red[wave] = v;
         __syncthreads();
         if (tid == 0) {
             float s = 0.f;
             for (int w = 0; w < nw; ++w) s += red[w];
-            a.sacc[((size_t)b * K + kb) * AC::kN + i] = s;
+            a.sacc[((size_t)b * K + kb) * kN + i] = s;
         }
         __syncthreads();
     }
 }
 
-// same algebra as bsim_bwd_finalize (one row of sums per sequence)
+// the scale gradients from the (sequence, cluster member) rows of sums, lanes striding over the rows
 template <int DX, int DY>
 __global__ void psvowr_bwd_finalize(const float* __restrict__ sacc, int rows, const float* sig_q1inv, const float* sig_bq2,
                                     float* dsig_f, float* dsig_g, float* dsig_q1inv, float* dsig_bq2, float* dsig_init,
                                     float* disig) {
-    using AC = WAcc<DX, DY>;
-    __shared__ float tot[AC::kN];
+    using AC = BAcc<DX>;
+    constexpr int kN = AC::kSg + DY;
+    __shared__ float tot[kN];
     const int d = threadIdx.x;
-    for (int k = 0; k < AC::kN; ++k) {
+    for (int k = 0; k < kN; ++k) {
         float v = 0.f;
-        for (int r = d; r < rows; r += 64) v += sacc[(size_t)r * AC::kN + k];
+        for (int r = d; r < rows; r += 64) v += sacc[(size_t)r * kN + k];
         v = wave_sum(v);
         if (d == 0) tot[k] = v;
     }
     __syncthreads();
     if (d < DX) {
-        const float i1 = 1.f / sig_q1inv[d], i2 = 1.f / sig_bq2[d];
-        const float c = 1.f / (i1 + i2);
-        const float dc = tot[AC::kSc + d] + tot[AC::kSmm + d] / c;
-        const float di1 = c * tot[AC::kSmm1 + d] - c * c * dc;
-        const float di2 = c * tot[AC::kSmb + d] - c * c * dc;
-        dsig_q1inv[d] = -i1 * i1 * di1;
-        dsig_bq2[d] = -i2 * i2 * di2;
+        pog_scale_grad(sig_q1inv[d], sig_bq2[d], tot[AC::kSc + d], tot[AC::kSmm1 + d], tot[AC::kSmb + d], tot[AC::kSmm + d],
+                       dsig_q1inv[d], dsig_bq2[d]);
         dsig_f[d] = tot[AC::kSf + d];
         dsig_init[d] = tot[AC::kSinit + d];
         disig[d] = tot[AC::kSiota + d];

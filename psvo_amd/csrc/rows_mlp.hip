@@ -147,16 +147,6 @@ __global__ void __launch_bounds__(256) rows_mlp_bwd_kernel(const RowsArgs a) {
     }
 }
 
-// out[p] (+)= sum_blk partial[blk][p]: one wave per output element (fixed order, deterministic)
-__global__ void rows_reduce_partials_kernel(const float* __restrict__ partial, int nblk, int NP, float* __restrict__ out,
-                                            int accumulate) {
-    const int p = blockIdx.x;
-    float s = 0.f;
-    for (int b = threadIdx.x; b < nblk; b += 64) s += partial[(size_t)b * NP + p];
-    s = wave_sum(s);
-    if (threadIdx.x == 0) out[p] = accumulate ? out[p] + s : s;
-}
-
 template <int H>
 static int launch_rows_fwd(const RowsArgs& a, hipStream_t s) {
     const size_t lds = sizeof(float) * ((size_t)a.Din * H + H + (size_t)H * a.Dout + a.Dout + 4);
@@ -175,7 +165,7 @@ static int launch_rows_bwd(const RowsArgs& a, float* grad, int accumulate, hipSt
     clear_hip_error();
     if (rb == 16) hipLaunchKernelGGL((rows_mlp_bwd_kernel<H, 16>), dim3(nblk), dim3(256), lds, s, a);
     else hipLaunchKernelGGL((rows_mlp_bwd_kernel<H, 64>), dim3(nblk), dim3(256), lds, s, a);
-    hipLaunchKernelGGL(rows_reduce_partials_kernel, dim3(NP), dim3(64), 0, s, a.partial, nblk, NP, grad, accumulate);
+    launch_reduce_rows(a.partial, nblk, NP, NP, grad, accumulate, s);      // (workgroups in order)
     return launch_status();
 }
 

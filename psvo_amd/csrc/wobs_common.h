@@ -1,4 +1,4 @@
-// What the wide-observation ("wobs") units share: the run-time width bound, the fixed-order workgroup sum and the LDS image
+// What the wide-observation ("wobs") units share: the run-time width bound, the terms of the count emission and the LDS image
 // of MLP_g with its output layer transposed (filter_wobs.hip, bsim_wobs.hip).
 #pragma once
 #include "common.h"
@@ -7,18 +7,6 @@ namespace psvo {
 namespace wobs {
 
 constexpr int kMaxDy = 32;
-
-// sum of `v` over the workgroup in a fixed order (lanes by the DPP scan, waves in wave order); `red` has 16 floats
-__device__ __forceinline__ float block_sum(float v, float* red, int wave, int lane, int nw) {
-    v = wave_sum(v);
-    if (nw == 1) return v;
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    float s = 0.f;
-    for (int i = 0; i < nw; ++i) s += red[i];
-    __syncthreads();
-    return s;
-}
 
 // Count emission (psvo_desc.emission = 2): log Gamma(y + 1) of an observed count.  Called by the lanes that stage the next
 // step's observation row, once per (step, sequence, output), never per particle.  Evaluated in fp64 and rounded once, so the
