@@ -17,9 +17,10 @@
 //     one swap + one add per pair of values, no selects); per-(chain, m) sums  U = sum_j p u,  V = sum_j p u^2  are
 //     all-reduced over the 16 lanes of the row with four DPP row rotations.
 // Addressing: every array is read / written (global address space: gptr below) as base (SGPR pair) + one 32-bit byte offset
-// per array SHAPE kept in a VGPR and advanced by a constant per step, and the float loop constants live in VGPRs (common.h
-// keep_in_vgpr): no index arithmetic in the loop, no scalar-register spills.  Arrays are therefore limited to 4 GiB each (the
-// dispatcher falls back to v1).
+// per array SHAPE kept in a VGPR -- the offset inside step 0, which never changes: the step's byte offset (a 32-bit product)
+// is added to the base on the scalar unit where the pointer is loaded -- and the float loop constants live in VGPRs (common.h
+// keep_in_vgpr): no index arithmetic on the VALU in the loop, no scalar-register spills in it.  Arrays are therefore limited
+// to 4 GiB each (the dispatcher falls back to v1).  What the step's instruction stream was cleared of: profiles/bsim_bwd2_valu_diet.md.
 //
 // MFMA variant of the per-j sums (template flag JM, measured beside the VALU form):
 //   d[F'|W^]_j = sum_k c_kj [x'_k | 1]  is  C^T [X' | 1]  with k = (item, m) -- v_mfma_f32_16x16x4_f32 takes the lane's
@@ -86,13 +87,50 @@ __device__ __forceinline__ float rs_bit2(float lo, float hi) {   // banks 0,2: l
                  : "=&v"(r) : "v"(lo), "v"(hi));
     return r;
 }
+// v + v(lane ^ MASK) in every lane, bit for bit what  v + xor_lane<MASK>(v)  gives (the two terms may swap places).  With
+// BOTH operands of a stage above the lane's own value no select is left over: lane bit 2 is the two bank-masked DPP adds
+// (xor_lane<4>: copy, two DPP moves, add), lane bits 4 and 5 one copy, the swap and the add (xor_lane<16>: two copies, the
+// swap, a select on the lane's row, the add).
+template <int MASK>
+__device__ __forceinline__ float add_xor(float v) {
+    if constexpr (MASK == 4) {
+        float r;
+        asm("s_nop 1\n\t"
+            "v_add_f32_dpp %0, %1, %1 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"
+            "v_add_f32_dpp %0, %1, %1 row_shr:4 row_mask:0xf bank_mask:0xa"
+            : "=&v"(r) : "v"(v));
+        return r;
+    } else if constexpr (MASK == 16) {
+        float w = v;
+        asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(v), "+v"(w));
+        return v + w;
+    } else if constexpr (MASK == 32) {
+        float w = v;
+        asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(v), "+v"(w));
+        return v + w;
+    } else {
+        return v + xor_lane<MASK>(v);
+    }
+}
+// common.h: group_sum, on add_xor
+template <int G>
+__device__ __forceinline__ float group_sum2(float v) {
+    if constexpr (G > 1) v = add_xor<1>(v);
+    if constexpr (G > 2) v = add_xor<2>(v);
+    if constexpr (G > 4) v = add_xor<4>(v);
+    if constexpr (G > 8) v = add_xor<8>(v);
+    if constexpr (G > 16) v = add_xor<16>(v);
+    if constexpr (G > 32) v = add_xor<32>(v);
+    return v;
+}
+
 template <int K>
 __device__ __forceinline__ void row_reduce_scatter(const float (&v)[4 * K], float (&out)[K]) {
     float h[2 * K];
 #pragma unroll
     for (int i = 0; i < 2 * K; ++i) h[i] = rs_bit3(v[i], v[2 * K + i]);
 #pragma unroll
-    for (int i = 0; i < K; ++i) out[i] = group_sum<4>(rs_bit2(h[i], h[K + i]));
+    for (int i = 0; i < K; ++i) out[i] = group_sum2<4>(rs_bit2(h[i], h[K + i]));
 }
 
 typedef float f4v __attribute__((ext_vector_type(4)));
@@ -242,7 +280,9 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
     const float ninf = -__builtin_huge_valf();
     const float aw = valid ? as_global(a.dscore)[(size_t)b * N + n] : 0.f;  // d loss / d score of this chain
 
-    // ---- byte offsets of step 0, one per array shape, and their per-step strides -----------------------------------
+    // ---- byte offsets inside step 0, one per array shape (they never change), and the per-step strides.  The step is added
+    // to the BASE (row below: one scalar multiply and a 64-bit scalar add per array, off the VALU); the lane's offset stays
+    // what it is, and the access keeps the saddr form.
     const unsigned NM = (unsigned)N * M;
     unsigned o_nm = 4u * ((unsigned)b * NM + n * M + m);                      // (T,B,N,M)     om, lam2
     unsigned o_dnm[DX], o_knm[DY], o_dn[DX];
@@ -257,6 +297,15 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
     unsigned o_d = 4u * ((unsigned)b * DX), o_k = 4u * ((unsigned)b * DY);    // (T,B,DX) bmu2, (T,B,DY) obs   (uniform)
     const unsigned s_nm = 4u * B * NM, s_dnm = s_nm * DX, s_knm = s_nm * DY, s_dn = 4u * B * DX * N, s_n = 4u * B * N,
                    s_d = 4u * B * DX, s_k = 4u * B * DY;
+    // base of step tt's part of an array (below 4 GiB: the product fits 32 bits)
+    auto row = [](unsigned long long p, int tt, unsigned stride) { return p + (unsigned long long)((unsigned)tt * stride); };
+    // a base that stays one: left to itself hipcc adds a uniform displacement of the base (d * N below) behind the lane's
+    // offset, as a 64-bit VALU add per access
+    auto row_base = [](gptr<float> p) {
+        unsigned long long q = (unsigned long long)p;
+        asm volatile("" : "+s"(q));
+        return as_global<float>(q);
+    };
 
     // ---- forward-tile staging (image identical to v1 / the forward kernel) ---------------------------------------------
     float st[DX + 1], st_l = 0.f;
@@ -389,36 +438,29 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
                   offsetof(BsimBwdArgs, lam2_all) - offsetof(BsimBwdArgs, obs) == 32 &&
                   offsetof(BsimBwdArgs, om_all) - offsetof(BsimBwdArgs, obs) == 40 &&
                   offsetof(BsimBwdArgs, mu1_all) - offsetof(BsimBwdArgs, obs) == 48, "BsimBwdArgs: input pointer block");
-    auto load_step = [&](bool lst, bool fst, StepIn& s) {    // (the offsets already point at the step to load)
+    auto load_step = [&](int tt, bool lst, bool fst, StepIn& s) {    // tt: the step to load
         unsigned long long pb[8];
         arg_block<8>((unsigned)offsetof(BsimBwdArgs, obs), pb);
-        const gptr<const float> p_obs = as_global<const float>(pb[0]);
-        const gptr<const float> p_eps = as_global<const float>(pb[1]);
-        const gptr<const float> p_bwX = as_global<const float>(pb[2]);
-        const gptr<const int32_t> p_sel = as_global<const int32_t>(pb[3]);
-        const gptr<const float> p_lam2 = as_global<const float>(pb[4]);
-        const gptr<const float> p_om = as_global<const float>(pb[5]);
-        const gptr<const float> p_mu1 = as_global<const float>(pb[6]);
-        const gptr<const float> p_bm = PSVO_GARG(BsimBwdArgs, bmu2);
+        const gptr<const float> p_obs = as_global<const float>(row(pb[0], tt, s_k));
+        const gptr<const float> p_eps = as_global<const float>(row(pb[1], tt, s_dnm));
+        const gptr<const float> p_bwX = as_global<const float>(row(pb[2], tt + 1, s_dn));
+        const gptr<const int32_t> p_sel = as_global<const int32_t>(row(pb[3], tt, s_n));
+        const gptr<const float> p_lam2 = as_global<const float>(row(pb[4], tt, s_nm));
+        const gptr<const float> p_om = as_global<const float>(row(pb[5], tt, s_nm));
+        const gptr<const float> p_mu1 = as_global<const float>(row(pb[6], tt, s_dn));
+        const gptr<const float> p_bm = as_global<const float>(row((unsigned long long)PSVO_ARG(BsimBwdArgs, bmu2), tt, s_d));
         s.sel = ldi(p_sel, o_n);
 #pragma unroll
         for (int d = 0; d < DX; ++d) {
             s.eps[d] = ldf(p_eps, o_dnm[d]);
             s.bm[d] = ldf(p_bm, o_d + 4u * d);
-            s.xp[d] = lst ? 0.f : ldf(p_bwX, o_dn[d] + s_dn);
+            s.xp[d] = lst ? 0.f : ldf(p_bwX, o_dn[d]);
             s.mu1[d] = lst ? 0.f : ldf(p_mu1, o_dn[d]);
         }
 #pragma unroll
         for (int k = 0; k < DY; ++k) s.y[k] = ldf(p_obs, o_k + 4u * k);
         s.om = ldf(p_om, o_nm);
         s.lam2 = fst ? 0.f : ldf(p_lam2, o_nm);
-    };
-    auto advance = [&]() {
-        o_nm += s_nm; o_n += s_n; o_d += s_d; o_k += s_k;
-#pragma unroll
-        for (int d = 0; d < DX; ++d) { o_dnm[d] += s_dnm; o_dn[d] += s_dn; }
-#pragma unroll
-        for (int k = 0; k < DY; ++k) o_knm[k] += s_knm;
     };
     // The wave waits for a step's inputs in ONE place: `settle`, where the words become this step's (in front of the loop for
     // step 0, in the rotation that ends step t for step t + 1).  The empty asm reads every word, so the s_waitcnt that
@@ -434,7 +476,7 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
         asm volatile("" : "+v"(s.sel));
     };
     StepIn cur_in;
-    load_step(T == 1, true, cur_in);
+    load_step(0, T == 1, true, cur_in);
     settle(cur_in);
 
     phase_skew(a.skew);
@@ -448,15 +490,21 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
         //  they land in would be live across it; the MLP phase and the chain reductions still cover the latency)
         constexpr bool kLateTile = (DX == 4);
         if (!kLateTile && t + 1 < T && t >= 1) stage_load(t);
-        // the offsets are advanced to step t+1 for the prefetch; this step's stores subtract the stride again
-        advance();
+        // the lane offsets are redefined (by nothing) once per step: as loop constants hipcc hoists their zero-extension out
+        // of the loop as register pairs and adds each base to them on the VALU (v_lshl_add_u64 per access) instead of
+        // folding the offset into the saddr form
+        asm volatile("" : "+v"(o_nm), "+v"(o_n));
+#pragma unroll
+        for (int d = 0; d < DX; ++d) asm volatile("" : "+v"(o_dnm[d]), "+v"(o_dn[d]));
+#pragma unroll
+        for (int k = 0; k < DY; ++k) asm volatile("" : "+v"(o_knm[k]));
         // Dx <= 2: the next step's inputs are requested here, a whole step ahead.  Dx >= 3: only after the pair phase (the
         // 3 Dx + 4 registers they land in would be live across it, and the kernel is at its 256-VGPR budget there); the MLP
         // phase, the chain reductions and the two barriers that follow still cover most of their latency.
         constexpr bool kLatePrefetch = (DX >= 3);
         StepIn nxt_in;
         auto prefetch = [&]() {
-            if (t + 1 < T) load_step(t + 2 == T, false, nxt_in);
+            if (t + 1 < T) load_step(t + 1, t + 2 == T, false, nxt_in);
             else nxt_in = StepIn{};
         };
         if (!kLatePrefetch) prefetch();
@@ -563,7 +611,7 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
 #pragma unroll
                         for (int e = 0; e < NA; ++e) {
                             float v = swap_add32(A2[0][e], A2[1][e]);
-                            v += xor_lane<16>(v);
+                            v = add_xor<16>(v);
                             if ((g & 1) == 0) {
                                 float* dst = ja + e * NP + (c * JC + (g >> 1)) * 16 + j16;
                                 *dst = (r == 0) ? v : *dst + v;
@@ -591,21 +639,33 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
                     }
                 }
             } else {
+            // (The U / V sums run over all chunks of the step and start from zero.  Taking the first tile's products instead
+            //  needs a second copy of a tile's or a chunk's code for the first chunk; every form of it -- straight-line, a
+            //  loop of its own, a scalar branch around the first tile -- made hipcc spill 33 to 162 registers at Dx = 2.)
             f2 Ua[2][DX], Ub[2][DX], Va[2][DX], Vb[2][DX];
 #pragma unroll
             for (int r = 0; r < 2; ++r)
 #pragma unroll
-                for (int d = 0; d < DX; ++d) Ua[r][d] = Ub[r][d] = Va[r][d] = Vb[r][d] = f2{0.f, 0.f};
+                for (int d = 0; d < DX; ++d) {
+                    // (one 64-bit move per pair: hipcc writes the 16 Dx zeros as 32-bit moves)
+                    asm("v_mov_b64 %0, 0" : "=v"(Ua[r][d]));
+                    asm("v_mov_b64 %0, 0" : "=v"(Ub[r][d]));
+                    asm("v_mov_b64 %0, 0" : "=v"(Va[r][d]));
+                    asm("v_mov_b64 %0, 0" : "=v"(Vb[r][d]));
+                }
 
             for (int c = 0; c < nch; ++c) {
                 float A2[JC][NA];       // JM = 0: per-j sums over the lane's items
                 f4v D4[JC];             // JM = 1: MFMA accumulators (rows = [d F'_0.., d W^], columns = the 16 j of a tile)
+                if constexpr (JM == 1) {
 #pragma unroll
-                for (int jt = 0; jt < JC; ++jt) {
-#pragma unroll
-                    for (int e = 0; e < NA; ++e) A2[jt][e] = 0.f;
-                    D4[jt] = f4v{0.f, 0.f, 0.f, 0.f};
+                    for (int jt = 0; jt < JC; ++jt) D4[jt] = f4v{0.f, 0.f, 0.f, 0.f};
                 }
+                // the per-j sums take round 0's term and add round 1's (no zero to write, and no 0 + x, which is an instruction
+                // under IEEE zeros; the one value that can differ is the sign of a zero sum)
+                // (Dx = 3 keeps the zero: without it <3,2,32,8,0> was allocated 15 registers more and spilled one)
+                constexpr bool kSeedJ = (DX <= 2);
+                auto a2_add = [&](int r, float& acc, float v) { acc = (r == 0) ? (kSeedJ ? v : 0.f + v) : acc + v; };
                 const float* cbase = cur + (c * 16 * JC + j16) * PS;
 #pragma unroll
                 for (int r = 0; r < 2; ++r) {
@@ -678,11 +738,11 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
                             Va[r][DX > 1 ? 1 : 0] = pk_fma(pa, f2{Fq.y, Fq.y}, Va[r][DX > 1 ? 1 : 0]);
                             Vb[r][DX > 1 ? 1 : 0] = pk_fma(pb, f2{Fq.y, Fq.y}, Vb[r][DX > 1 ? 1 : 0]);
                             const f2 cs = ca + cb;
-                            A2[jt][DX] += cs.x + cs.y;
+                            a2_add(r, A2[jt][DX], cs.x + cs.y);
 #pragma unroll
                             for (int d = 0; d < DX; ++d) {
                                 const f2 ad = pk_fma(cb, xb[d], ca * xa[d]);     // sum c x' (the F' sum c term: at the flush)
-                                A2[jt][d] += ad.x + ad.y;
+                                a2_add(r, A2[jt][d], ad.x + ad.y);
                             }
                         }
                     } else
@@ -714,11 +774,11 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
                         }
                         if constexpr (JM != 1) {
                             const f2 cs = ca + cb;
-                            A2[jt][DX] += cs.x + cs.y;
+                            a2_add(r, A2[jt][DX], cs.x + cs.y);
 #pragma unroll
                             for (int d = 0; d < DX; ++d) {
                                 const f2 ad = pk_fma(cb, ub[d], ca * ua[d]);
-                                A2[jt][d] += ad.x + ad.y;
+                                a2_add(r, A2[jt][d], ad.x + ad.y);
                             }
                         } else {
                             // d F'_j wants sum c (x' - F'_j) = (sum c x') - F'_j (sum c): the MFMA forms sum c [x' | 1];
@@ -862,7 +922,7 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
                 float fmx[DX];
                 MQ::template eval_part<PART>(wf, part, x, fmx);
 #pragma unroll
-                for (int d = 0; d < DX; ++d) fmx[d] += xor_lane<M>(fmx[d]);
+                for (int d = 0; d < DX; ++d) fmx[d] = add_xor<M>(fmx[d]);
 #pragma unroll
                 for (int d = 0; d < DX; ++d) {
                     const float z = (xp[d] - fmx[d]) * isf[d];
@@ -883,14 +943,14 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
             if (srow) {
 #pragma unroll
                 for (int d = 0; d < DX; ++d) {
-                    stf(as_global<float>(pr[1]), o_dnm[d] - s_dnm, dFo[d]);
-                    stf(as_global<float>(pr[0]), o_dnm[d] - s_dnm, x[d]);
+                    stf(as_global<float>(row(pr[1], t, s_dnm)), o_dnm[d], dFo[d]);
+                    stf(as_global<float>(row(pr[0], t, s_dnm)), o_dnm[d], x[d]);
                 }
             }
             float gm[DY], dGo[DY];
             MG::template eval_part<PART>(wg, part, x, gm);
 #pragma unroll
-            for (int k = 0; k < DY; ++k) gm[k] += xor_lane<M>(gm[k]);
+            for (int k = 0; k < DY; ++k) gm[k] = add_xor<M>(gm[k]);
 #pragma unroll
             for (int k = 0; k < DY; ++k) {
                 float dmean = 1.f;
@@ -898,7 +958,7 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
                 const float z = (y[k] - gm[k]) * isg[k];
                 dGo[k] = dphi * z * isg[k] * dmean;
                 if (h0) acc_add(AC::kSg + k, dphi * (z * z - 1.f) * isg[k]);
-                if (srow) stf(as_global<float>(pr[2]), o_knm[k] - s_knm, dGo[k]);
+                if (srow) stf(as_global<float>(row(pr[2], t, s_knm)), o_knm[k], dGo[k]);
             }
             MG::template bwd_input_part<PART>(wg, part, x, dGo, dxt);
         }
@@ -909,10 +969,10 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
 #pragma unroll
         for (int d = 0; d < DX; ++d) {
             const float v3 = (first && h0) ? dphi * (x[d] - im[d]) * i_isig[d] * i_isig[d] : 0.f;
-            dmu[d] = group_sum<G>(dxt[d]);
-            sce[d] = group_sum<G>(dxt[d] * eps[d]);
-            dxp[d] = group_sum<G>(dxp_part[d]);
-            dim[d] = first ? group_sum<G>(v3) : 0.f;
+            dmu[d] = group_sum2<G>(dxt[d]);
+            sce[d] = group_sum2<G>(dxt[d] * eps[d]);
+            dxp[d] = group_sum2<G>(dxp_part[d]);
+            dim[d] = first ? group_sum2<G>(v3) : 0.f;
         }
         float outv[DX];  // per-chain value that is summed over the chains afterwards: d bmu2 / d minit
         if (!last) {
@@ -922,7 +982,7 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
                 dmu1[d] = dmu[d] * pc[d] * pi1[d];
                 outv[d] = dmu[d] * pc[d] * pi2[d];
                 if (lead) {
-                    stf(PSVO_GARG(BsimBwdArgs, dmu1), o_dn[d] - s_dn, dmu1[d]);
+                    stf(as_global<float>(row((unsigned long long)PSVO_ARG(BsimBwdArgs, dmu1), t, s_dn)), o_dn[d], dmu1[d]);
                     acc_add(AC::kSc + d, sce[d] + aw * pic[d]);   // -sum_m dq_m / c = a / c
                     acc_add(AC::kSmm1 + d, dmu[d] * mu1[d]);
                     acc_add(AC::kSmb + d, dmu[d] * bm[d]);
@@ -937,14 +997,14 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
                 for (int d = 0; d < DX; ++d) dq[d] = 0.f;
                 MQ::template bwd_input_part<kQS>(wqi, (lane % G) & (kQS - 1), xp, dmu1, dq);
 #pragma unroll
-                for (int d = 0; d < DX; ++d) dxp[d] += group_sum<kQS>(dq[d]);
+                for (int d = 0; d < DX; ++d) dxp[d] += group_sum2<kQS>(dq[d]);
             }
         } else {
 #pragma unroll
             for (int d = 0; d < DX; ++d) {
                 outv[d] = dmu[d];
                 if (lead) {
-                    stf(PSVO_GARG(BsimBwdArgs, dmu1), o_dn[d] - s_dn, 0.f);
+                    stf(as_global<float>(row((unsigned long long)PSVO_ARG(BsimBwdArgs, dmu1), t, s_dn)), o_dn[d], 0.f);
                     acc_add(AC::kSinit + d, sce[d] + aw * is_init[d]);
                 }
             }
@@ -954,9 +1014,15 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
         if (lead) {
 #pragma unroll
             for (int d = 0; d < DX; ++d) {
-                stf(PSVO_GARG(BsimBwdArgs, dbmu2_rows), o_dn[d] - s_dn, last ? 0.f : outv[d]);
-                if (last) PSVO_GARG(BsimBwdArgs, dminit_rows)[((size_t)b * DX + d) * N + n] = outv[d];
-                if (first) PSVO_GARG(BsimBwdArgs, dimean_rows)[((size_t)b * DX + d) * N + n] = dim[d];
+                stf(as_global<float>(row((unsigned long long)PSVO_ARG(BsimBwdArgs, dbmu2_rows), t, s_dn)), o_dn[d], last ? 0.f : outv[d]);
+                // (B,DX,N): the lane offset of a (T,B,DX,N) step.  (A copy made in the arm: shared with the stores of every
+                //  step, its zero-extension for these two would be formed in every step.)
+                if (first || last) {
+                    unsigned oe = o_dn[d];
+                    asm volatile("" : "+v"(oe));
+                    if (last) stf(PSVO_GARG(BsimBwdArgs, dminit_rows), oe, outv[d]);
+                    if (first) stf(PSVO_GARG(BsimBwdArgs, dimean_rows), oe, dim[d]);
+                }
             }
         }
         SEC(6);   // chain reductions, MLP_q1inv input gradient
@@ -971,14 +1037,19 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
             const size_t tbm = tb - B;
             const gptr<float> pF = PSVO_GARG(BsimBwdArgs, dFm_part) + (tbm * nblk + blk) * DX * N;
             const gptr<float> pW = PSVO_GARG(BsimBwdArgs, dlogW_part) + (tbm * nblk + blk) * N;
+            // (stores as scalar base of the row + the lane's 32-bit byte offset: no 64-bit address on the VALU)
+            // (NP as this block sees it: the twelve products NP (NA w + d) are then formed here, on the scalar unit, instead of
+            //  holding twelve scalar registers through the whole step -- the kernel has none to spare)
+            int NPh = NP;
+            asm volatile("" : "+s"(NPh));
             for (int j = tid; j < N; j += NTB) {
 #pragma unroll
                 for (int d = 0; d < NA; ++d) {
-                    const float* col = jacc + d * NP + j;
-                    const float a0 = col[0], a1 = col[NA * NP], a2 = col[2 * NA * NP], a3 = col[3 * NA * NP];
+                    const float* col = jacc + d * NPh + j;
+                    const float a0 = col[0], a1 = col[NA * NPh], a2 = col[2 * NA * NPh], a3 = col[3 * NA * NPh];
                     const float s = (a0 + a1) + (a2 + a3);
-                    if (d < DX) pF[d * N + j] = s * isfk[d < DX ? d : 0];
-                    else pW[j] = s;
+                    if (d < DX) stf(row_base(pF + d * N), 4u * j, s * isfk[d < DX ? d : 0]);
+                    else stf(pW, 4u * j, s);
                 }
             }
         }
@@ -987,8 +1058,8 @@ __global__ void __launch_bounds__(256, 2) bsim_bwd2_kernel(const BsimBwdArgs a) 
             const gptr<float> pW = PSVO_GARG(BsimBwdArgs, dlogW_part) + (tb * nblk + blk) * N;
             for (int j = tid; j < N; j += NTB) {
 #pragma unroll
-                for (int d = 0; d < DX; ++d) pF[d * N + j] = 0.f;
-                pW[j] = 0.f;
+                for (int d = 0; d < DX; ++d) stf(row_base(pF + d * N), 4u * j, 0.f);
+                stf(pW, 4u * j, 0.f);
             }
         }
         SEC(7);   // barrier, workgroup sums, d Fm / d logW flush
