@@ -609,6 +609,54 @@ int psvo_filter_backward(const psvo_desc* desc,
                          float* sacc, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Adaptive resampling (not in the reference; added within ABI 6: purely additive, no existing struct or signature changed).
+ * psvo_filter_forward / psvo_filter_backward with the resampling decision made per (step, sequence) on the device, from the
+ * effective sample size of the step's weights.  With w_n = exp(logW[t,b,n] - max_n logW[t,b,:]) over the N particles,
+ *     ESS[t,b] = (sum_n w_n)^2 / sum_n w_n^2,        the sequence resamples at t  iff  !(ESS[t,b] >= ess_frac * N)
+ * (a NaN ESS resamples).  Every step makes and writes the multinomial draw exactly as psvo_filter_forward with resample = 1
+ * does -- idx_out[t] is the draw (idx_in teacher-forces it), Xanc[t] the gathered particles, an equally weighted sample at
+ * every step.  Only what step t+1 inherits depends on the decision: resampled, the MLP outputs of the drawn ancestor and the
+ * weight -log N; not resampled, the particle's own MLP outputs and the normalised weight logW[t] - lse[t], which then enters
+ * logW[t+1] (sum_t lse[t] stays the estimate of log Z in the mixed case).  X, Fm, P1, logW, lse keep meaning and layout.
+ *
+ *  forward, beyond the arguments of psvo_filter_forward:
+ *    ess_frac          the threshold as a fraction of N; > 0.  >= 1 resamples at (almost) every step; a value above 1
+ *                      resamples always, a tiny one never.
+ *    rs_in  (T,B) int32  teacher-forced decisions (non-zero = resample) or NULL: the analogue of idx_in
+ *    rs_out (T,B) int32  the decisions taken (1 = resampled), ess_out (T,B) the ESS they were taken from (also under rs_in)
+ *  reverse, beyond the arguments of psvo_filter_backward:
+ *    rs     (T,B) int32  the forward pass's rs_out: a constant of the reverse pass, like idx.  The ancestor of particle n at
+ *                      step t is rs[t-1] ? idx[t-1][n] : n, and the gradient of the carried weight is applied for exactly the
+ *                      steps with rs[t] == 0.  Always the persistent kernels (the affine scan assumes a gather at every
+ *                      step); deterministic mode (PSVO_TUNE_DETERMINISTIC) holds as for psvo_filter_backward.
+ *    sacc              workspace of psvo_filter_ws_floats(B, T, N, Dx, Dy) floats, as psvo_filter_backward
+ *  Envelope of psvo_filter_forward / psvo_filter_backward (Dx 2..4, Dy 1..2, N <= 512, emission 0 / 1, one or two hidden
+ *  layers, every wiring).  Refused before a device is touched: ess_frac not > 0 (NaN included), desc->resample == 0, NULL
+ *  rs_out / ess_out / rs -- PSVO_ERR_INVALID; nparts > 1 or non-NULL dFm_ext / dlogW_ext (a backward simulation behind an
+ *  adaptive filter) -- PSVO_ERR_UNSUPPORTED.
+ * ------------------------------------------------------------------------------------------- */
+int psvo_filter_forward_adaptive(const psvo_desc* desc,
+                        const psvo_mlp* q1, const psvo_mlp* f, const psvo_mlp* g,
+                        const float* sig_q1, const float* sig_q2, const float* sig_f, const float* sig_g,
+                        const float* mu2,
+                        const float* m0, const float* sig0, const float* fm0, const float* fsig0,
+                        const float* obs, const float* eps, const float* u, const int32_t* idx_in,
+                        float* X, float* Xanc, float* Fm, float* P1, float* logW, int32_t* idx_out,
+                        float* lse, float ess_frac, const int32_t* rs_in, int32_t* rs_out, float* ess_out, void* stream);
+int psvo_filter_backward_adaptive(const psvo_desc* desc,
+                         const psvo_mlp* q1, const psvo_mlp* f, const psvo_mlp* g,
+                         const float* sig_q1, const float* sig_q2, const float* sig_f, const float* sig_g,
+                         const float* mu2,
+                         const float* m0, const float* sig0, const float* fm0, const float* fsig0,
+                         const float* obs, const float* eps,
+                         const float* X, const float* Fm, const float* P1, const float* logW, const float* lse,
+                         const int32_t* idx,
+                         const float* dlse, int nparts, const float* dFm_ext, const float* dlogW_ext,
+                         float* dP, float* dF, float* dG, float* dmu2, float* dm0, float* dfm0,
+                         float* dsig_q1, float* dsig_q2, float* dsig_f, float* dsig_g, float* dsig0, float* dfsig0,
+                         float* sacc, const int32_t* rs, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Wide observations ("wobs"): the forward filter, its reverse pass and MLP_g's weight gradient for 3 <= Dy <= 32
  * (psvo_amd/csrc/filter_wobs.hip; added within ABI 6 -- the entry points above keep Dy in {1, 2}).  For the filter objectives
  * (SVO, AESMC, IWAE); PSVO's backward simulation has its own wide entry points further down, PSVOwR's stays at Dy <= 2.

@@ -9,7 +9,32 @@ permutes the result to the reference's (batch, time, particles, Dx).
 import torch
 
 from .. import ops
-from ..autograd import FilterCovFunction, FilterFunction, FilterWobsFunction
+from ..autograd import FilterAdaptiveFunction, FilterCovFunction, FilterFunction, FilterWobsFunction
+
+
+def check_resample_ess(raw, never_resamples=False, backward_simulation=False, output_cov=False, Dy=1, plain_dy=2):
+    """--resample_ess as a float: 0.0 = off, else the ESS threshold tau as a fraction of N, 0 < tau <= 1.  ValueError, naming
+    the limit, for a threshold outside that range and for everything the adaptive kernels do not cover (runner.main calls this
+    on the flags before it touches a device, SVO.__init__ on the model it is given)."""
+    tau = float(0.0 if raw is None else raw)
+    if tau == 0.0:
+        return 0.0
+    if not (0.0 < tau <= 1.0):
+        raise ValueError("--resample_ess = %r: the ESS threshold is a fraction of the particle count, 0 < tau <= 1 "
+                         "(0 = off: resample at every step)" % (raw,))
+    if never_resamples:
+        raise ValueError("--resample_ess with --IWAE: IWAE never resamples, so there is no resampling decision to make; "
+                         "use --AESMC or --SVO")
+    if backward_simulation:
+        raise ValueError("--resample_ess with --PSVO / --PSVOwR: the backward-simulation kernels assume a filter that "
+                         "resamples at every step; adaptive resampling covers the filter objectives (SVO, AESMC) only")
+    if output_cov:
+        raise ValueError("--resample_ess with output_cov: the state-dependent-scale kernels (psvo_filter_forward_cov) have "
+                         "no adaptive form; adaptive resampling takes state-independent scales only")
+    if Dy > plain_dy:
+        raise ValueError("--resample_ess with Dy = %d: the adaptive kernels are the plain filter kernels, which take "
+                         "Dy <= %d; the wide-observation kernels have no adaptive form" % (Dy, plain_dy))
+    return tau
 
 
 class SVO:
@@ -17,6 +42,8 @@ class SVO:
     uses_backward_simulation = False
     # ... and has a wide-observation form of it (PSVO: csrc/bsim_wobs.hip), taken when FLAGS.BSim_wide_obs asks for it
     has_wide_backward_simulation = False
+    # the objective never resamples (IWAE): there is no decision for FLAGS.resample_ess to make
+    never_resamples = False
     # observation widths of the plain filter kernels / of the wide-observation ("wobs") kernels (csrc/filter_wobs.hip)
     _PLAIN_DY, _WOBS_MAX_DY = 2, 32
 
@@ -44,6 +71,9 @@ class SVO:
         self.FFBS = bool(getattr(FLAGS, "FFBS", False))
         # backward-sampled trajectories behind the filter at evaluation time (FLAGS.FFBSi; psvo_ffbs_sample)
         self.FFBSi = bool(getattr(FLAGS, "FFBSi", False))
+
+        # adaptive resampling (FLAGS.resample_ess, not in the reference): 0 = off, else the ESS threshold as a fraction of N
+        self.resample_ess = self._route_resample_ess(model, FLAGS)
 
         self.name = name
         self.generator = None        # torch.Generator on the compute device; None = global RNG
@@ -89,13 +119,25 @@ class SVO:
                              "layers run for Dy <= %d only" % (Dy, deep, limit, cls._PLAIN_DY))
         return True
 
+    @classmethod
+    def _route_resample_ess(cls, model, FLAGS):
+        """FLAGS.resample_ess as a float: 0.0 (off: resampling at every step, or never for IWAE) or the threshold tau of
+        psvo_filter_forward_adaptive, 0 < tau <= 1.  What the adaptive kernels do not cover is refused here, up front."""
+        return check_resample_ess(getattr(FLAGS, "resample_ess", 0.0), never_resamples=cls.never_resamples,
+                                  backward_simulation=cls.uses_backward_simulation,
+                                  output_cov=bool(getattr(model, "output_cov", False)), Dy=getattr(model, "Dy", cls._PLAIN_DY))
+
     # ------------------------------------------------------------------------------------------
     def get_log_ZSMC(self, obs, hidden, noise=None):
         """obs (batch, time, Dy), hidden (batch, time, Dx) -> (log_ZSMC scalar, {"Xs": (B,T,N,Dx)}).
 
         `noise` optionally injects the random draws in the HBM layout of include/psvo_hip.h:
         eps_f (T,B,Dx,N), u_f (T,B,N) or idx_f (T,B,N) int32; with FLAGS.FFBS also u_s (T,B,N) or idx_s (T,B,N) int32, the
-        draws of the smoothed particles.
+        draws of the smoothed particles.  With FLAGS.resample_ess also rs_f (T,B) int32, teacher-forced resampling decisions.
+
+        With FLAGS.resample_ess (adaptive resampling) log["ess"] (B,T) is the effective sample size of every step's weights,
+        log["resampled"] (B,T) bool whether the sequence resampled there and log["filter"]["rs"] (T,B) int32 the same in the
+        kernel's layout; log["Xs"] is the multinomial draw of every step whatever the decision (an equally weighted sample).
 
         With FLAGS.FFBS and autograd not recording (evaluation, trajectory saving, prediction) the marginal smoother runs
         behind the filter: log["Xs"] then holds particles resampled by the SMOOTHED weights (the filtered ones move to
@@ -121,6 +163,9 @@ class SVO:
         # (T, B, Dx, N) -> (batch_size, time, n_particles, Dx)
         log["Xs"] = filt["Xanc"].permute(1, 0, 3, 2)
         log["filter"] = filt
+        if filt.get("rs") is not None:
+            log["ess"] = filt["ess"].transpose(0, 1)
+            log["resampled"] = filt["rs"].transpose(0, 1) != 0
         if self.FFBS and not torch.is_grad_enabled():
             self._smooth(filt, log, noise or {})
         if self.FFBSi and not torch.is_grad_enabled():
@@ -341,6 +386,14 @@ class SVO:
         node = FilterFunction
         if self.wide_obs:
             node, desc._gbufs = FilterWobsFunction, None
+        if self.resample_ess:
+            # psvo_filter_forward_adaptive / psvo_filter_backward_adaptive: the decision per (step, sequence) is the kernel's
+            desc._gbufs = None
+            lse, Fm, logW, X, Xanc, idx, rs, ess = FilterAdaptiveFunction.apply(
+                desc, obs_TB, eps, u, idx_in, self.resample_ess, noise.get("rs_f"),
+                *first, self._sigma(self.q1), sig_q2, sig_f, self._sigma(self.g), mu2, m0, sig0, fm0, fsig0, *extra)
+            return {"lse": lse, "Fm": Fm, "logW": logW, "X": X, "Xanc": Xanc, "idx": idx, "eps": eps, "u": u,
+                    "rs": rs, "ess": ess}
         lse, Fm, logW, X, Xanc, idx = node.apply(
             desc, obs_TB, eps, u, idx_in,
             *first, self._sigma(self.q1), sig_q2, sig_f, self._sigma(self.g), mu2, m0, sig0, fm0, fsig0, *extra)

@@ -48,6 +48,9 @@ SIGNATURES = {
     "psvo_filter_acc_size": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "psvo_filter_ws_floats": (ctypes.c_longlong, [ctypes.c_int] * 5),
     "psvo_filter_backward": (ctypes.c_int, [_DESC, _MLP, _MLP, _MLP] + [_P] * 18 + [ctypes.c_int] + [_P] * 16),
+    "psvo_filter_forward_adaptive": (ctypes.c_int, [_DESC, _MLP, _MLP, _MLP] + [_P] * 20 + [ctypes.c_float, _P, _P, _P] + [_P]),
+    "psvo_filter_backward_adaptive": (ctypes.c_int, [_DESC, _MLP, _MLP, _MLP] + [_P] * 18 + [ctypes.c_int] + [_P] * 15
+                                      + [_P, _P]),
     "psvo_filter_forward_wobs": (ctypes.c_int, [_DESC, _MLP, _MLP, _MLP] + [_P] * 20 + [_P]),
     "psvo_filter_wobs_ws_floats": (ctypes.c_longlong, [ctypes.c_int] * 5),
     "psvo_filter_backward_wobs": (ctypes.c_int, [_DESC, _MLP, _MLP, _MLP] + [_P] * 31 + [_P]),

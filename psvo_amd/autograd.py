@@ -361,6 +361,49 @@ class FilterWobsFunction(torch.autograd.Function):
             None if same_s else r["dfsig0"])
 
 
+class FilterAdaptiveFunction(torch.autograd.Function):
+    """psvo_filter_forward_adaptive / psvo_filter_backward_adaptive: the plain forward filter resampling a sequence at step t
+    only where its effective sample size has fallen below ess_frac N (FLAGS.resample_ess; Dy <= 2, one or two hidden layers).
+
+    apply(desc, obs_TB, eps, u, idx_in, ess_frac, rs_in, <the tensors of FilterFunction>)
+      -> lse (T,B)                                               [differentiable]
+         Fm (T,B,Dx,N), logW (T,B,N), X, Xanc (T,B,Dx,N), idx (T,B,N) int32, rs (T,B) int32, ess (T,B)     [constants]
+    rs_in (T,B) int32 teacher-forces the decisions (or None).  Nothing runs behind an adaptive filter under autograd (no
+    backward simulation), so Fm and logW leave the node as constants.  One stream, gradients returned as tensors."""
+
+    @staticmethod
+    def forward(ctx, desc, obs_TB, eps, u, idx_in, ess_frac, rs_in, *t):
+        ctx.set_materialize_grads(False)
+        t = [_cf(v) for v in t]
+        q1, f, g = _mlps(t)
+        rest = t[12:21]                 # sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, fm0, fsig0
+        if desc.bootstrap:
+            f = None
+        filt = ops.filter_forward(desc, q1, f, g, *rest, obs_TB, eps, u, idx_in, ess_frac=ess_frac, rs_in=rs_in)
+        ctx.desc, ctx.filt = desc, _aliases(filt)
+        ctx.saved = (q1, f, g, rest, obs_TB, eps)
+        const = (filt["Fm"], filt["logW"], filt["X"], filt["Xanc"], filt["idx"], filt["rs"], filt["ess"])
+        ctx.mark_non_differentiable(*const)
+        return (filt["lse"],) + const
+
+    @staticmethod
+    def backward(ctx, dlse, *_):
+        desc = ctx.desc
+        q1, f, g, rest, obs_TB, eps = ctx.saved
+        r = ops.filter_backward(desc, q1, f, g, *rest, obs_TB, eps, ctx.filt, dlse=_cg(dlse), adaptive=True)
+        Dx, Dy, H = desc.Dx, desc.Dy, desc.H
+        two_q, boot = bool(desc.two_q), bool(desc.bootstrap)
+        gfirst, gextra = _mlp_grads(r, ("gq1", None if boot else "gf", "gg"), ((Dx, Dx), (Dx, Dx), (Dx, Dy)), H,
+                                    2 if desc.layers == 2 else 1, (None, None, None))
+        m0, sig0, fm0, fsig0 = rest[5:9]
+        same_m = m0.data_ptr() == fm0.data_ptr()       # (one tensor as both: the kernel put the sum into d m0)
+        same_s = sig0.data_ptr() == fsig0.data_ptr()
+        return (None,) * 7 + gfirst + (
+            r["dsig_q1"], r["dsig_q2"] if two_q else None, None if boot else r["dsig_f"], r["dsig_g"],
+            r["dmu2"] if two_q else None, r["dm0"], r["dsig0"], None if same_m else r["dfm0"],
+            None if same_s else r["dfsig0"]) + gextra
+
+
 def _filter_node_of(Fm, ov):
     """the FilterFunction node that produced `Fm` in this evaluation (its ctx), if the overlap wiring is on: the
     backward-simulation node may launch that node's reverse kernel early.  (A downstream reference only: this node

@@ -22,6 +22,8 @@ HEADERS = ["common.h", "mlp2_valu.h", os.path.join("..", "..", "include", "psvo_
 UNIT_HEADERS = {"bsim_bwd_impl.h": ("bsim_bwd_dx", "bsim_bwd2_dx", "bsim_bwd.hip"),
                 "bsim_bwd2_impl.h": ("bsim_bwd2_dx", "bsim_bwd.hip"),
                 "ffbs_pair.h": ("ffbs.hip", "ffbsi.hip"),
+                "filter_fwd_impl.h": ("filter_fwd",),
+                "filter_bwd_impl.h": ("filter_bwd",),
                 "wobs_common.h": ("filter_wobs.hip", "bsim_wobs.hip")}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-slp-vectorize"]
 # Round 2 built the two-hidden-layer units with `-mllvm -vgpr-regalloc=basic`: their per-lane H x H layer held 2 H values per

@@ -81,6 +81,9 @@ DEFINITIONS = [
     # backward-sampled trajectories for the filter objectives (not in the reference's registry: its PSVO samples paths, its
     # filters do not): off by default, evaluation only
     ("FFBSi", bool, False, "SVO / AESMC / IWAE: return N backward-sampled trajectories per sequence (backward simulation)"),
+    # adaptive resampling for the filter objectives (not in the reference's registry, whose filters resample at every step or,
+    # IWAE, never): resample a sequence at step t only where its effective sample size has fallen below this fraction of N
+    ("resample_ess", float, 0.0, "SVO / AESMC: resample where ESS < resample_ess * n_particles (0 = off: at every step; else in (0, 1])"),
     # printing and data saving (runner_flag.py:131-153)
     ("print_freq", int, 1, "frequency to evaluate testing loss & other metrics and save results"),
     ("save_trajectory", bool, True, "whether to save hidden trajectories during training"),

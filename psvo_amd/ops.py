@@ -194,8 +194,10 @@ def _mark(name, phase):
 
 
 def filter_forward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, fm0, fsig0,
-                   obs, eps, u=None, idx_in=None, entry="psvo_filter_forward"):
-    """psvo_filter_forward (`entry`: an entry point with the same contract).  Returns dict(X, Xanc, Fm, logW, idx, lse)."""
+                   obs, eps, u=None, idx_in=None, entry="psvo_filter_forward", ess_frac=None, rs_in=None):
+    """psvo_filter_forward (`entry`: an entry point with the same contract).  Returns dict(X, Xanc, Fm, logW, idx, lse).
+    ess_frac (a float > 0): psvo_filter_forward_adaptive -- resampling where ESS < ess_frac N; rs_in (T,B) int32 teacher-forces
+    the decisions; the dict then also holds rs (T,B) int32 and ess (T,B)."""
     lib = _lib.load()
     B, T, N, Dx, Dy, H = desc.B, desc.T, desc.N, desc.Dx, desc.Dy, desc.H
     dev = eps.device
@@ -213,19 +215,30 @@ def filter_forward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, 
     _chk(u, (T, B, N), "u"); _chk(idx_in, (T, B, N), "idx_in", torch.int32)
     if desc.resample and u is None and idx_in is None:
         raise ValueError("resampling needs uniforms `u` or teacher-forced `idx_in`")
+    adaptive = ()
+    if ess_frac is not None:
+        if entry != "psvo_filter_forward":
+            raise ValueError("filter_forward: ess_frac belongs to the plain filter kernels (psvo_filter_forward_adaptive)")
+        entry = "psvo_filter_forward_adaptive"
+        _chk(rs_in, (T, B), "rs_in", torch.int32)
+    elif rs_in is not None:
+        raise ValueError("filter_forward: rs_in without ess_frac")
     out = {
         "X": _empty(T, B, Dx, N, device=dev), "Xanc": _empty(T, B, Dx, N, device=dev),
         "Fm": _empty(T, B, Dx, N, device=dev), "logW": _empty(T, B, N, device=dev),
         "idx": _empty(T, B, N, device=dev, dtype=torch.int32), "lse": _empty(T, B, device=dev),
         "P1": None if desc.bootstrap else _empty(T, B, Dx, N, device=dev),
     }
+    if ess_frac is not None:
+        out["rs"], out["ess"] = _empty(T, B, device=dev, dtype=torch.int32), _empty(T, B, device=dev)
+        adaptive = (ctypes.c_float(float(ess_frac)), _ptr(rs_in), _ptr(out["rs"]), _ptr(out["ess"]))
     _mark(entry, 0)
     st = getattr(lib, entry)(
         ctypes.byref(desc), ctypes.byref(q1s), ctypes.byref(fs) if fs is not None else None, ctypes.byref(gs),
         _ptr(sig_q1), _ptr(sig_q2), _ptr(sig_f), _ptr(sig_g), _ptr(mu2), _ptr(m0), _ptr(sig0), _ptr(fm0),
         _ptr(fsig0), _ptr(obs), _ptr(eps), _ptr(u), _ptr(idx_in),
         _ptr(out["X"]), _ptr(out["Xanc"]), _ptr(out["Fm"]), _ptr(out["P1"]), _ptr(out["logW"]), _ptr(out["idx"]),
-        _ptr(out["lse"]), _stream())
+        _ptr(out["lse"]), *adaptive, _stream())
     _mark(entry, 1)
     _lib.check(st, entry)
     return out
@@ -504,8 +517,9 @@ def split_mlp_grad(g, Din, H, Dout, layers=1):
 
 def filter_backward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, fm0, fsig0, obs, eps, filt,
                     dlse=None, dFm=None, dlogW=None, gbufs=None, before_wgrad=None, defer_wgrad=False, wobs=False,
-                    nparts=None, ext=False):
-    """psvo_filter_backward + psvo_mlp_wgrad.  `filt` = forward outputs.  dFm (T,B,Dx,N) / dlogW (T,B,N)
+                    nparts=None, ext=False, adaptive=False):
+    """psvo_filter_backward + psvo_mlp_wgrad (adaptive: psvo_filter_backward_adaptive, following the decisions filt["rs"]).
+    `filt` = forward outputs.  dFm (T,B,Dx,N) / dlogW (T,B,N)
     are upstream gradients (or None); with nparts > 1 they come in parts, (T,B,nparts,Dx,N) / (T,B,nparts,N), which the
     kernel adds in part order.  Returns a dict of gradients.
     wobs: psvo_filter_backward_wobs + psvo_mlp_wgrad_wobs for MLP_g (wide observations); with dFm / dlogW -- a backward
@@ -527,6 +541,14 @@ def filter_backward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0,
     nparts = (parts[0] if parts else 1) if (dFm is not None or dlogW is not None) else 0
     ext = bool(ext or nparts)
     name = ("psvo_filter_backward_wobs_ext" if ext else "psvo_filter_backward_wobs") if wobs else "psvo_filter_backward"
+    decisions = ()
+    if adaptive:
+        if wobs:
+            raise ValueError("filter_backward: adaptive resampling belongs to the plain filter kernels (Dy <= 2)")
+        if filt.get("rs") is None:
+            raise ValueError("filter_backward(adaptive=True) needs the forward pass's decisions filt['rs']")
+        _chk(filt["rs"], (T, B), "filt['rs']", torch.int32)
+        name, decisions = "psvo_filter_backward_adaptive", (_ptr(filt["rs"]),)
     sacc = z((lib.psvo_filter_wobs_ws_floats if wobs else lib.psvo_filter_ws_floats)(B, T, N, Dx, Dy))
     upstream = (_ptr(dlse),) if (wobs and not ext) else (_ptr(dlse), nparts, _ptr(dFm), _ptr(dlogW))
     _mark(name, 0)
@@ -538,7 +560,7 @@ def filter_backward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0,
             _ptr(filt["lse"]), _ptr(filt["idx"]), *upstream,
             _ptr(out["dP"]), _ptr(out["dF"]), _ptr(out["dG"]), _ptr(out["dmu2"]), _ptr(out["dm0"]), _ptr(out["dfm0"]),
             _ptr(out["dsig_q1"]), _ptr(out["dsig_q2"]), _ptr(out["dsig_f"]), _ptr(out["dsig_g"]), _ptr(out["dsig0"]),
-            _ptr(out["dfsig0"]), _ptr(sacc), _stream())
+            _ptr(out["dfsig0"]), _ptr(sacc), *decisions, _stream())
     _mark(name, 1)
     _lib.check(st, name)
     # weight gradients from rows; gbufs = (q1, f, g) slices of the flat gradient buffer to accumulate into

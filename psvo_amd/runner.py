@@ -27,7 +27,7 @@ from .SMC.AESMC import AESMC
 from .SMC.IWAE import IWAE
 from .SMC.PSVO import PSVO
 from .SMC.PSVOwR import PSVOwR
-from .SMC.SVO import SVO
+from .SMC.SVO import SVO, check_resample_ess
 from .trainer import trainer
 from .utils.data_generator import PoissonEmitter, count_loading, generate_dataset
 from .utils.data_loader import load_data
@@ -94,6 +94,8 @@ def main(FLAGS):
     if getattr(FLAGS, "FFBSi", False) and (FLAGS.PSVO or FLAGS.PSVOwR):
         raise ValueError("--FFBSi samples trajectories from the particle system of a filter objective (SVO, AESMC, IWAE); PSVO "
                          "and PSVOwR already return backward-simulation trajectories")
+    check_resample_ess(getattr(FLAGS, "resample_ess", 0.0), never_resamples=bool(FLAGS.IWAE),
+                       backward_simulation=bool(FLAGS.PSVO or FLAGS.PSVOwR), output_cov=bool(FLAGS.output_cov), Dy=FLAGS.Dy)
     if FLAGS.use_2_q:
         FLAGS.q_uses_true_X = False
     device = _device()

@@ -25,6 +25,10 @@ Backward-sampled trajectories (FLAGS.FFBSi, off by default; SVO / AESMC / IWAE):
 behind the filter, so "Xs", the k-step predictions and the saved trajectories are whole paths, as under PSVO; the mean and the
 minimum over each split of the number of distinct particles the N paths pass through are printed and go into metric_<iter>.p
 as ffbsi_distinct_mean_<split> / ffbsi_distinct_min_<split>.  Training steps are untouched.
+
+Adaptive resampling (FLAGS.resample_ess, off by default; SVO / AESMC): training and evaluation run the adaptive filter kernels;
+at every evaluation the share of (sequence, step) pairs that resampled and the mean / minimum of ESS / N over each split are
+printed and go into metric_<iter>.p as adaptive_rate_<split>, adaptive_ess_mean_<split>, adaptive_ess_min_<split>.
 """
 import math
 import os
@@ -263,10 +267,17 @@ class trainer:
         metric_<iter>.p with the reference's keys (trainer.py:201-241).  A non-finite training ELBO stops training."""
         ffbs = bool(getattr(self.SMC, "FFBS", False))
         ffbsi = bool(getattr(self.SMC, "FFBSi", False))
-        fetches = ["log_ZSMC", "y_hat", "y"] + (["ess_smooth"] if ffbs else []) + (["path_distinct"] if ffbsi else [])
+        adaptive = bool(getattr(self.SMC, "resample_ess", 0.0))
+        fetches = (["log_ZSMC", "y_hat", "y"] + (["ess", "resampled"] if adaptive else []) + (["ess_smooth"] if ffbs else [])
+                   + (["path_distinct"] if ffbsi else []))
         m, ess = {}, {}
         for split, obs, hid in (("train", self.obs_train, self.hidden_train), ("test", self.obs_test, self.hidden_test)):
             elbos, y_hat, y, *rest = self.evaluate(fetches, {self.obs: obs, self.hidden: hid})
+            if adaptive:
+                frac, rest = np.asarray(rest[0]) / float(self.n_particles), rest[1:]
+                ess["adaptive_rate_" + split] = float(np.mean(rest[0]))
+                ess["adaptive_ess_mean_" + split], ess["adaptive_ess_min_" + split] = float(np.mean(frac)), float(np.min(frac))
+                rest = rest[1:]
             if ffbs:
                 ess["ffbs_ess_mean_" + split], ess["ffbs_ess_min_" + split] = float(np.mean(rest[0])), float(np.min(rest[0]))
             if ffbsi:
@@ -279,6 +290,12 @@ class trainer:
             print("iter", iter_num + 1)
             print("Train log_ZSMC: {:>7.3f}, valid log_ZSMC: {:>7.3f}".format(m["log_ZSMC_train"], m["log_ZSMC_test"]))
             print("Train, Valid k-step Rsq:\n", m["R_square_train"], "\n", m["R_square_test"])
+            if adaptive:
+                print("adaptive resampling (ESS < {:g} N): resampled steps train {:.1%}, valid {:.1%}; ESS / N mean / min: train "
+                      "{:.3f} / {:.3f}, valid {:.3f} / {:.3f}"
+                      .format(self.SMC.resample_ess, ess["adaptive_rate_train"], ess["adaptive_rate_test"],
+                              ess["adaptive_ess_mean_train"], ess["adaptive_ess_min_train"],
+                              ess["adaptive_ess_mean_test"], ess["adaptive_ess_min_test"]))
             if ffbs:
                 print("FFBS effective sample size (of {} particles), mean / min: train {:.2f} / {:.2f}, valid {:.2f} / {:.2f}"
                       .format(self.n_particles, ess["ffbs_ess_mean_train"], ess["ffbs_ess_min_train"],
@@ -370,6 +387,10 @@ class trainer:
                     y_hat, y = self.SMC.n_step_prediction(self.MSE_steps, Xs, obs_d)
                     out["y_hat"] = [v.cpu().numpy() for v in y_hat]
                     out["y"] = [v.cpu().numpy() for v in y]
+            if "ess" in names:
+                out["ess"] = log["ess"].contiguous().cpu().numpy()                    # (B, T); FLAGS.resample_ess only
+            if "resampled" in names:
+                out["resampled"] = log["resampled"].contiguous().cpu().numpy()        # (B, T) bool
             if "ess_smooth" in names:
                 out["ess_smooth"] = log["ess_smooth"].contiguous().cpu().numpy()      # (B, T); FLAGS.FFBS only
             if "path_distinct" in names:
