@@ -355,6 +355,72 @@ struct MlpLds<DIN, H, DOUT, 1> {
         for (int o = 0; o < DOUT; ++o) out[o] = acc[o].x + acc[o].y;
     }
 
+    // The slice of eval_part<S> as REGISTERS: the rows of W1 and the entries of b1 and W2 of the lane's H / S hidden units, as
+    // the f2 pairs the packed math takes, plus b2 (zero outside part 0).  A persistent kernel loads it once, behind the barrier
+    // that makes the LDS image visible; its time loop then evaluates the MLP without an LDS access.  (Read through `w` inside
+    // a loop with barriers the slice is re-read every iteration: the image shares the LDS array the loop stores into, so the
+    // compiler cannot take it for unchanged.)
+    template <int S>
+    struct Slice {
+        static constexpr int HP = H / S;
+        static constexpr int kFloats = HP * (1 + DIN + DOUT) + DOUT;
+        f2 b1[HP / 2], w1[DIN][HP / 2], w2[DOUT][HP / 2];
+        f2 acc0[DOUT];                        // {b2[o] (part 0) or 0, 0}: where the output's two partial sums start
+    };
+    template <int S>
+    __device__ __forceinline__ static void load_slice(const float* __restrict__ w, int part, Slice<S>& s) {
+        constexpr int HP = H / S;
+        static_assert(HP % 4 == 0, "hidden slice must be a multiple of 4");
+        const float* wp = w + part * HP;
+#pragma unroll
+        for (int k = 0; k < HP; k += 4) {
+            const float4 b = *reinterpret_cast<const float4*>(wp + kB1 + k);
+            s.b1[k / 2] = f2{b.x, b.y};
+            s.b1[k / 2 + 1] = f2{b.z, b.w};
+#pragma unroll
+            for (int i = 0; i < DIN; ++i) {
+                const float4 wi = *reinterpret_cast<const float4*>(wp + kW1 + i * H + k);
+                s.w1[i][k / 2] = f2{wi.x, wi.y};
+                s.w1[i][k / 2 + 1] = f2{wi.z, wi.w};
+            }
+#pragma unroll
+            for (int o = 0; o < DOUT; ++o) {
+                const float4 wo = *reinterpret_cast<const float4*>(wp + kW2 + o * H + k);
+                s.w2[o][k / 2] = f2{wo.x, wo.y};
+                s.w2[o][k / 2 + 1] = f2{wo.z, wo.w};
+            }
+        }
+#pragma unroll
+        for (int o = 0; o < DOUT; ++o) s.acc0[o] = f2{part == 0 ? w[kB2 + o] : 0.f, 0.f};
+    }
+    // eval_part<S> on a register slice: the operations of group4, in its order
+    template <int S>
+    __device__ __forceinline__ static void eval_part(const Slice<S>& s, const float (&x)[DIN], float (&out)[DOUT]) {
+        f2 acc[DOUT];
+#pragma unroll
+        for (int o = 0; o < DOUT; ++o) acc[o] = s.acc0[o];
+        const f2 zero = f2{0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < H / S / 2; k += 2) {
+            f2 ha = s.b1[k], hb = s.b1[k + 1];
+#pragma unroll
+            for (int i = 0; i < DIN; ++i) {
+                const f2 xi = f2{x[i], x[i]};
+                ha = pk_fma(xi, s.w1[i][k], ha);
+                hb = pk_fma(xi, s.w1[i][k + 1], hb);
+            }
+            ha = pk_max(ha, zero);
+            hb = pk_max(hb, zero);
+#pragma unroll
+            for (int o = 0; o < DOUT; ++o) {
+                acc[o] = pk_fma(ha, s.w2[o][k], acc[o]);
+                acc[o] = pk_fma(hb, s.w2[o][k + 1], acc[o]);
+            }
+        }
+#pragma unroll
+        for (int o = 0; o < DOUT; ++o) out[o] = acc[o].x + acc[o].y;
+    }
+
     // input gradient of four hidden units (recomputes their pre-activations; relu' = [pre > 0])
     __device__ __forceinline__ static void bwd_group4(const float* __restrict__ w, int k, const float (&x)[DIN],
                                                       const float (&dout)[DOUT], f2 (&dxa)[DIN]) {

@@ -283,9 +283,13 @@ __global__ void __launch_bounds__(MAXT) PSVO_FWD_KERNEL(const PSVO_FWD_ARGS a) {
 // ---------------------------------------------------------------------------------------------
 // Four lanes per particle (N <= 256).  The filter runs ONE workgroup per sequence, so a step is a pure
 // latency chain; with lane = particle the two dependent MLP evaluations were > 40 % of it.  Here particle
-// n owns the quad of lanes 4n..4n+3: lane p evaluates hidden units [p*H/4, (p+1)*H/4) of every MLP (its
-// slice of the weights is loop-invariant and stays in registers) and the outputs are summed over the quad
-// with two DPP adds.  Everything else is computed redundantly in the four lanes; the multinomial search is a
+// n owns the quad of lanes 4n..4n+3: lane p evaluates hidden units [p*H/4, (p+1)*H/4) of every MLP and the
+// outputs are summed over the quad with two DPP adds.  With one hidden layer the lane's slice of the weights is
+// read from LDS ONCE, behind the barrier that makes the weights visible, into registers (MlpLds::Slice): read
+// through the LDS pointer inside the time loop it was re-read every step -- the image shares the LDS array the
+// step stores into, and across a barrier hipcc cannot take it for unchanged (18 ds_read_b128 per step at C*).
+// MLP_f's slice joins the other two where the three fit (kSliceBudget); the two-layer MLP reads LDS.
+// Everything else is computed redundantly in the four lanes; the multinomial search is a
 // two-round 16-ary search in which the quad reads 16 CDF pivots / 16 CDF entries as four float4 per round.
 // The per-sequence log-sum-exp and CDF use per-wave maxima and ONE barrier.
 // ---------------------------------------------------------------------------------------------
@@ -294,7 +298,16 @@ __global__ void __launch_bounds__(MAXT) PSVO_FWD_LPP_KERNEL(const PSVO_FWD_ARGS 
     using MQ = MlpLds<DX, H, DX, PSVO_L>;
     using MG = MlpLds<DX, H, DY, PSVO_L>;
     constexpr int P = 4;
-    constexpr bool kOpaque = false;   // (every instantiated shape keeps its weight slice in VGPRs without scratch)
+    using SG = typename MlpLds<DX, H, DY, 1>::template Slice<P>;
+    using SQ = typename MlpLds<DX, H, DX, 1>::template Slice<P>;
+    // which slices are held in registers (one hidden layer only: the H x H layer of two reads its operands from LDS as the
+    // matrix instructions want them).  MLP_g and MLP_q1 wherever the build stays within 256 VGPRs, without scratch and without
+    // one more spilled register than it had: that leaves out Dx = 4 and the adaptive kernels at Dy = 2, which gain spilled
+    // SGPRs -- their slices stay in LDS and are read there each step, as before.  MLP_f, evaluated without bootstrap only,
+    // joins where all three stay inside kSliceBudget floats (above it: more than the 256 registers of two waves per SIMD).
+    constexpr int kSliceBudget = 120;
+    constexpr bool kRegGQ = PSVO_L == 1 && DX <= 3 && !(PSVO_AD && DY == 2);
+    constexpr bool kRegF = kRegGQ && SG::kFloats + 2 * SQ::kFloats <= kSliceBudget;
     extern __shared__ __attribute__((aligned(16))) float smem[];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -420,6 +433,15 @@ __global__ void __launch_bounds__(MAXT) PSVO_FWD_LPP_KERNEL(const PSVO_FWD_ARGS 
     take_inputs();
     __syncthreads();  // weights visible
 
+    // the lane's weight slices, read from LDS here and nowhere else (see the kernel's header)
+    SG rg;
+    SQ rq, rf;
+    if constexpr (kRegGQ) {
+        MlpLds<DX, H, DY, 1>::template load_slice<P>(wg, p, rg);
+        MlpLds<DX, H, DX, 1>::template load_slice<P>(wq1, p, rq);
+    }
+    if constexpr (kRegF) MlpLds<DX, H, DX, 1>::template load_slice<P>(wfm, p, rf);
+
     SEC_INIT(filter_fwd)
     // t = 0 (its own proposal constants) is peeled: the loop proper then carries one set of step constants
     // instead of selecting between two every step (scalar-register pressure: spills cost v_readlane + s_nop)
@@ -446,14 +468,18 @@ __global__ void __launch_bounds__(MAXT) PSVO_FWD_LPP_KERNEL(const PSVO_FWD_ARGS 
 
         SEC(2);   // (lpp) proposal, q / f densities
         // ---- the MLPs of the step, hidden units split over the quad ------------------------------------
-        // (the lane's weight slice is loop-invariant: the compiler keeps it in VGPRs when the budget allows;
-        //  otherwise an opaque LDS offset per step makes it re-read the slice instead of spilling it)
-        int zo = 0;
-        if (kOpaque) asm volatile("" : "+v"(zo));
         float gm[DY], p1[DX], fm[DX];
-        MG::template eval_part<P>(wg + zo, p, x, gm);
-        MQ::template eval_part<P>(wq1 + zo, p, x, p1);
-        if (!a.bootstrap) MQ::template eval_part<P>(wfm + zo, p, x, fm);
+        if constexpr (kRegGQ) {
+            MlpLds<DX, H, DY, 1>::template eval_part<P>(rg, x, gm);
+            MlpLds<DX, H, DX, 1>::template eval_part<P>(rq, x, p1);
+        } else {
+            MG::template eval_part<P>(wg, p, x, gm);
+            MQ::template eval_part<P>(wq1, p, x, p1);
+        }
+        if (!a.bootstrap) {
+            if constexpr (kRegF) MlpLds<DX, H, DX, 1>::template eval_part<P>(rf, x, fm);
+            else MQ::template eval_part<P>(wfm, p, x, fm);
+        }
 #pragma unroll
         for (int k = 0; k < DY; ++k) gm[k] = group_sum<P>(gm[k]);
         if (a.emission) {
