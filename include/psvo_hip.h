@@ -719,6 +719,45 @@ int psvo_mlp_wgrad_wobs(long long S, int L, int Din, int H, int Dout, const floa
                         const psvo_mlp* w, float* partial, float* grad, int accumulate, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Adaptive resampling on wide observations (added within ABI 6: purely additive).  psvo_filter_forward_wobs /
+ * psvo_filter_backward_wobs with the decision of "Adaptive resampling" above, word for word: ESS[t,b] = (sum_n w_n)^2 /
+ * sum_n w_n^2 with w_n = exp(logW[t,b,n] - max_n logW[t,b,:]); the sequence resamples at t iff !(ESS[t,b] >= ess_frac * N) (a
+ * NaN ESS resamples); the draw is made and written at every step (idx_out, Xanc; idx_in teacher-forces it) and only what step
+ * t+1 inherits depends on the decision -- resampled: the drawn ancestor's MLP outputs and the weight -log N; kept: the
+ * particle's own and logW[t] - lse[t].  ess_frac, rs_in, rs_out, ess_out and rs mean what they mean there.
+ *  forward:  the arguments of psvo_filter_forward_wobs, then ess_frac, rs_in (T,B) int32 or NULL, rs_out (T,B) int32,
+ *            ess_out (T,B).  With ess_frac > 1 every output equals psvo_filter_forward_wobs's with resample = 1 bit for bit;
+ *            with a tiny ess_frac X, Fm, P1, logW, lse equal its outputs with resample = 0 bit for bit.
+ *  reverse:  the arguments of psvo_filter_backward_wobs, then rs (T,B) int32, the forward pass's rs_out.  ws:
+ *            psvo_filter_wobs_ws_floats(B, T, N, Dx, Dy) floats, unchanged.  Upstream gradient dlse only: nothing runs behind
+ *            an adaptive filter under autograd.  One fixed order for every sum and no float atomics, as
+ *            psvo_filter_backward_wobs; a step with rs[t-1] == 0 has no gather to reverse and skips the walk over the children.
+ *  Envelope of the wide filter entry points (3 <= Dy <= 32, Dx in {2,3,4}, H in {16,32,64}, N <= 512, one hidden layer,
+ *  emission 0 / 1 / 2, every bootstrap / two_q wiring).  Refused before a device is touched, the adaptive contract first:
+ *  ess_frac not > 0 (NaN included), desc->resample == 0, NULL rs_out / ess_out / rs -- PSVO_ERR_INVALID; then whatever
+ *  psvo_filter_forward_wobs / psvo_filter_backward_wobs refuse, with their statuses.
+ * ------------------------------------------------------------------------------------------- */
+int psvo_filter_forward_wobs_adaptive(const psvo_desc* desc,
+                             const psvo_mlp* q1, const psvo_mlp* f, const psvo_mlp* g,
+                             const float* sig_q1, const float* sig_q2, const float* sig_f, const float* sig_g,
+                             const float* mu2,
+                             const float* m0, const float* sig0, const float* fm0, const float* fsig0,
+                             const float* obs, const float* eps, const float* u, const int32_t* idx_in,
+                             float* X, float* Xanc, float* Fm, float* P1, float* logW, int32_t* idx_out,
+                             float* lse, float ess_frac, const int32_t* rs_in, int32_t* rs_out, float* ess_out, void* stream);
+int psvo_filter_backward_wobs_adaptive(const psvo_desc* desc,
+                              const psvo_mlp* q1, const psvo_mlp* f, const psvo_mlp* g,
+                              const float* sig_q1, const float* sig_q2, const float* sig_f, const float* sig_g,
+                              const float* mu2,
+                              const float* m0, const float* sig0, const float* fm0, const float* fsig0,
+                              const float* obs, const float* eps,
+                              const float* X, const float* Fm, const float* P1, const float* logW, const float* lse,
+                              const int32_t* idx, const float* dlse,
+                              float* dP, float* dF, float* dG, float* dmu2, float* dm0, float* dfm0,
+                              float* dsig_q1, float* dsig_q2, float* dsig_f, float* dsig_g, float* dsig0, float* dfsig0,
+                              float* ws, const int32_t* rs, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * PSVO on wide observations: the backward simulation with proposal and its reverse pass for 3 <= Dy <= 32
  * (psvo_amd/csrc/bsim_wobs.hip), and the wide reverse filter with upstream gradients of Fm / logW (added within ABI 6).
  * The Dy <= 2 entry points are unchanged: psvo_bsim_forward, psvo_bsim_backward and psvo_bsim_backward_fold keep answering

@@ -9,13 +9,17 @@ permutes the result to the reference's (batch, time, particles, Dx).
 import torch
 
 from .. import ops
-from ..autograd import FilterAdaptiveFunction, FilterCovFunction, FilterFunction, FilterWobsFunction
+from ..autograd import (FilterAdaptiveFunction, FilterCovFunction, FilterFunction, FilterWobsAdaptiveFunction,
+                        FilterWobsFunction)
 
 
-def check_resample_ess(raw, never_resamples=False, backward_simulation=False, output_cov=False, Dy=1, plain_dy=2):
+def check_resample_ess(raw, never_resamples=False, backward_simulation=False, output_cov=False, Dy=1, plain_dy=2,
+                       wide_obs=False, layers=(), wobs_max_dy=32):
     """--resample_ess as a float: 0.0 = off, else the ESS threshold tau as a fraction of N, 0 < tau <= 1.  ValueError, naming
     the limit, for a threshold outside that range and for everything the adaptive kernels do not cover (runner.main calls this
-    on the flags before it touches a device, SVO.__init__ on the model it is given)."""
+    on the flags before it touches a device, SVO.__init__ on the model it is given).  `wide_obs`: --resample_ess_wide_obs, the
+    adaptive wide-observation kernels for plain_dy < Dy <= wobs_max_dy (`layers`: the hidden layers of the per-particle MLPs,
+    one each there); no effect at Dy <= plain_dy or with the threshold off."""
     tau = float(0.0 if raw is None else raw)
     if tau == 0.0:
         return 0.0
@@ -31,10 +35,27 @@ def check_resample_ess(raw, never_resamples=False, backward_simulation=False, ou
     if output_cov:
         raise ValueError("--resample_ess with output_cov: the state-dependent-scale kernels (psvo_filter_forward_cov) have "
                          "no adaptive form; adaptive resampling takes state-independent scales only")
+    if Dy > plain_dy and not wide_obs:
+        raise ValueError("--resample_ess with Dy = %d: without --resample_ess_wide_obs the adaptive kernels are the plain filter "
+                         "kernels, which take Dy <= %d; pass --resample_ess_wide_obs for the adaptive wide-observation kernels "
+                         "(3 <= Dy <= %d)" % (Dy, plain_dy, wobs_max_dy))
+    if Dy > wobs_max_dy:
+        raise ValueError("--resample_ess --resample_ess_wide_obs with Dy = %d: the adaptive wide-observation kernels take "
+                         "3 <= Dy <= %d" % (Dy, wobs_max_dy))
     if Dy > plain_dy:
-        raise ValueError("--resample_ess with Dy = %d: the adaptive kernels are the plain filter kernels, which take "
-                         "Dy <= %d; the wide-observation kernels have no adaptive form" % (Dy, plain_dy))
+        deep = [v for v in (_layer_list(s) for s in layers) if len(v) != 1]
+        if deep:
+            raise ValueError("--resample_ess --resample_ess_wide_obs with Dy = %d and per-particle MLP layers %s: the adaptive "
+                             "wide-observation kernels take one hidden layer per MLP; two hidden layers run for Dy <= %d only"
+                             % (Dy, deep, plain_dy))
     return tau
+
+
+def _layer_list(spec):
+    """a *_layers flag ("32" / "32,32") or a list of widths -> list of ints"""
+    if isinstance(spec, str):
+        return [int(v) for v in spec.split(",") if v.strip()]
+    return [int(v) for v in spec]
 
 
 class SVO:
@@ -122,10 +143,17 @@ class SVO:
     @classmethod
     def _route_resample_ess(cls, model, FLAGS):
         """FLAGS.resample_ess as a float: 0.0 (off: resampling at every step, or never for IWAE) or the threshold tau of
-        psvo_filter_forward_adaptive, 0 < tau <= 1.  What the adaptive kernels do not cover is refused here, up front."""
+        psvo_filter_forward_adaptive, 0 < tau <= 1.  What the adaptive kernels do not cover is refused here, up front.  With
+        FLAGS.resample_ess_wide_obs a model on the wide-observation route (_route_wide_obs has accepted it, or refused it, by
+        now) takes psvo_filter_forward_wobs_adaptive; without the flag Dy > 2 stays refused: making it the default is a
+        one-line change here."""
+        trans = [t for t in (getattr(model, "q1_tran", None), getattr(model, "g_tran", None),
+                             None if getattr(model, "use_bootstrap", True) else getattr(model, "f_tran", None)) if t is not None]
         return check_resample_ess(getattr(FLAGS, "resample_ess", 0.0), never_resamples=cls.never_resamples,
                                   backward_simulation=cls.uses_backward_simulation,
-                                  output_cov=bool(getattr(model, "output_cov", False)), Dy=getattr(model, "Dy", cls._PLAIN_DY))
+                                  output_cov=bool(getattr(model, "output_cov", False)), Dy=getattr(model, "Dy", cls._PLAIN_DY),
+                                  plain_dy=cls._PLAIN_DY, wide_obs=bool(getattr(FLAGS, "resample_ess_wide_obs", False)),
+                                  layers=[t.Dhs for t in dict.fromkeys(trans)], wobs_max_dy=cls._WOBS_MAX_DY)
 
     # ------------------------------------------------------------------------------------------
     def get_log_ZSMC(self, obs, hidden, noise=None):
@@ -388,8 +416,10 @@ class SVO:
             node, desc._gbufs = FilterWobsFunction, None
         if self.resample_ess:
             # psvo_filter_forward_adaptive / psvo_filter_backward_adaptive: the decision per (step, sequence) is the kernel's
+            # (wide observations, FLAGS.resample_ess_wide_obs: psvo_filter_forward_wobs_adaptive / _backward_wobs_adaptive)
             desc._gbufs = None
-            lse, Fm, logW, X, Xanc, idx, rs, ess = FilterAdaptiveFunction.apply(
+            node = FilterWobsAdaptiveFunction if self.wide_obs else FilterAdaptiveFunction
+            lse, Fm, logW, X, Xanc, idx, rs, ess = node.apply(
                 desc, obs_TB, eps, u, idx_in, self.resample_ess, noise.get("rs_f"),
                 *first, self._sigma(self.q1), sig_q2, sig_f, self._sigma(self.g), mu2, m0, sig0, fm0, fsig0, *extra)
             return {"lse": lse, "Fm": Fm, "logW": logW, "X": X, "Xanc": Xanc, "idx": idx, "eps": eps, "u": u,

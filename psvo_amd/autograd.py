@@ -404,6 +404,47 @@ class FilterAdaptiveFunction(torch.autograd.Function):
             None if same_s else r["dfsig0"]) + gextra
 
 
+class FilterWobsAdaptiveFunction(torch.autograd.Function):
+    """psvo_filter_forward_wobs_adaptive / psvo_filter_backward_wobs_adaptive: FilterAdaptiveFunction on the wide-observation
+    kernels (FLAGS.resample_ess with FLAGS.resample_ess_wide_obs; 3 <= Dy <= 32, one hidden layer, every emission form).
+
+    apply(...) takes FilterAdaptiveFunction's arguments and returns its outputs; only lse is differentiable.  The reverse uses
+    psvo_mlp_wgrad_wobs for MLP_g and psvo_mlp_wgrad for MLP_q1 / MLP_f, as FilterWobsFunction does.  One stream, gradients
+    returned as tensors."""
+
+    @staticmethod
+    def forward(ctx, desc, obs_TB, eps, u, idx_in, ess_frac, rs_in, *t):
+        ctx.set_materialize_grads(False)
+        t = [_cf(v) for v in t]
+        q1, f, g = _mlps(t)
+        rest = t[12:21]                 # sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, fm0, fsig0
+        if desc.bootstrap:
+            f = None
+        filt = ops.filter_forward_wobs_adaptive(desc, q1, f, g, *rest, obs_TB, eps, u, idx_in, ess_frac=ess_frac, rs_in=rs_in)
+        ctx.desc, ctx.filt = desc, _aliases(filt)
+        ctx.saved = (q1, f, g, rest, obs_TB, eps)
+        const = (filt["Fm"], filt["logW"], filt["X"], filt["Xanc"], filt["idx"], filt["rs"], filt["ess"])
+        ctx.mark_non_differentiable(*const)
+        return (filt["lse"],) + const
+
+    @staticmethod
+    def backward(ctx, dlse, *_):
+        desc = ctx.desc
+        q1, f, g, rest, obs_TB, eps = ctx.saved
+        r = ops.filter_backward_wobs_adaptive(desc, q1, f, g, *rest, obs_TB, eps, ctx.filt, dlse=_cg(dlse))
+        Dx, Dy, H = desc.Dx, desc.Dy, desc.H
+        two_q, boot = bool(desc.two_q), bool(desc.bootstrap)
+        gfirst, _ = _mlp_grads(r, ("gq1", None if boot else "gf", "gg"), ((Dx, Dx), (Dx, Dx), (Dx, Dy)), H, 1,
+                               (None, None, None))
+        m0, sig0, fm0, fsig0 = rest[5:9]
+        same_m = m0.data_ptr() == fm0.data_ptr()       # (one tensor as both: the kernel put the sum into d m0)
+        same_s = sig0.data_ptr() == fsig0.data_ptr()
+        return (None,) * 7 + gfirst + (
+            r["dsig_q1"], r["dsig_q2"] if two_q else None, None if boot else r["dsig_f"], r["dsig_g"],
+            r["dmu2"] if two_q else None, r["dm0"], r["dsig0"], None if same_m else r["dfm0"],
+            None if same_s else r["dfsig0"])
+
+
 def _filter_node_of(Fm, ov):
     """the FilterFunction node that produced `Fm` in this evaluation (its ctx), if the overlap wiring is on: the
     backward-simulation node may launch that node's reverse kernel early.  (A downstream reference only: this node

@@ -24,6 +24,7 @@ UNIT_HEADERS = {"bsim_bwd_impl.h": ("bsim_bwd_dx", "bsim_bwd2_dx", "bsim_bwd.hip
                 "ffbs_pair.h": ("ffbs.hip", "ffbsi.hip"),
                 "filter_fwd_impl.h": ("filter_fwd",),
                 "filter_bwd_impl.h": ("filter_bwd",),
+                "filter_wobs_impl.h": ("filter_wobs.hip",),
                 "wobs_common.h": ("filter_wobs.hip", "bsim_wobs.hip")}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-slp-vectorize"]
 # Round 2 built the two-hidden-layer units with `-mllvm -vgpr-regalloc=basic`: their per-lane H x H layer held 2 H values per

@@ -84,6 +84,9 @@ DEFINITIONS = [
     # adaptive resampling for the filter objectives (not in the reference's registry, whose filters resample at every step or,
     # IWAE, never): resample a sequence at step t only where its effective sample size has fallen below this fraction of N
     ("resample_ess", float, 0.0, "SVO / AESMC: resample where ESS < resample_ess * n_particles (0 = off: at every step; else in (0, 1])"),
+    # (not in the reference's registry) adaptive resampling on observations wider than two: the wide-observation filter kernels
+    # in their adaptive form.  Off by default: without it --resample_ess stays refused at Dy > 2
+    ("resample_ess_wide_obs", bool, False, "SVO / AESMC: run --resample_ess at 3 <= Dy <= 32 on the wide-observation adaptive kernels"),
     # printing and data saving (runner_flag.py:131-153)
     ("print_freq", int, 1, "frequency to evaluate testing loss & other metrics and save results"),
     ("save_trajectory", bool, True, "whether to save hidden trajectories during training"),

@@ -193,6 +193,12 @@ def _mark(name, phase):
         _HOOK(name, phase, _cur_stream())
 
 
+# the entry points that take ess_frac / rs_in, by the `entry` they are asked for under (filter_forward_wobs with ess_frac stays a
+# refusal: the wide adaptive route is filter_forward_wobs_adaptive)
+_ADAPTIVE_ENTRY = {"psvo_filter_forward": "psvo_filter_forward_adaptive",
+                   "psvo_filter_forward_wobs_adaptive": "psvo_filter_forward_wobs_adaptive"}
+
+
 def filter_forward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, fm0, fsig0,
                    obs, eps, u=None, idx_in=None, entry="psvo_filter_forward", ess_frac=None, rs_in=None):
     """psvo_filter_forward (`entry`: an entry point with the same contract).  Returns dict(X, Xanc, Fm, logW, idx, lse).
@@ -217,9 +223,9 @@ def filter_forward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, 
         raise ValueError("resampling needs uniforms `u` or teacher-forced `idx_in`")
     adaptive = ()
     if ess_frac is not None:
-        if entry != "psvo_filter_forward":
+        if entry not in _ADAPTIVE_ENTRY:
             raise ValueError("filter_forward: ess_frac belongs to the plain filter kernels (psvo_filter_forward_adaptive)")
-        entry = "psvo_filter_forward_adaptive"
+        entry = _ADAPTIVE_ENTRY[entry]
         _chk(rs_in, (T, B), "rs_in", torch.int32)
     elif rs_in is not None:
         raise ValueError("filter_forward: rs_in without ess_frac")
@@ -248,6 +254,14 @@ def filter_forward_wobs(*args, **kw):
     """psvo_filter_forward_wobs: the forward filter for wide observations (3 <= Dy <= 32, one hidden layer); arguments,
     outputs and layouts of filter_forward."""
     return filter_forward(*args, entry="psvo_filter_forward_wobs", **kw)
+
+
+def filter_forward_wobs_adaptive(*args, ess_frac, rs_in=None, **kw):
+    """psvo_filter_forward_wobs_adaptive: filter_forward_wobs resampling where ESS < ess_frac N; arguments of filter_forward,
+    the result also holds rs (T,B) int32 and ess (T,B)."""
+    if ess_frac is None:
+        raise ValueError("filter_forward_wobs_adaptive needs the threshold ess_frac")
+    return filter_forward(*args, entry="psvo_filter_forward_wobs_adaptive", ess_frac=ess_frac, rs_in=rs_in, **kw)
 
 
 # The plain backward simulations (PSVO: bsim_*, PSVOwR: bsimwr_*) take the same inputs ahead of their own and their reverse
@@ -543,12 +557,16 @@ def filter_backward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0,
     name = ("psvo_filter_backward_wobs_ext" if ext else "psvo_filter_backward_wobs") if wobs else "psvo_filter_backward"
     decisions = ()
     if adaptive:
-        if wobs:
+        if wobs and adaptive != "wobs":     # (the wide adaptive route is filter_backward_wobs_adaptive)
             raise ValueError("filter_backward: adaptive resampling belongs to the plain filter kernels (Dy <= 2)")
+        if wobs and ext:
+            raise ValueError("filter_backward_wobs_adaptive: no upstream gradient of Fm / logW (nothing runs behind an adaptive "
+                             "filter under autograd)")
         if filt.get("rs") is None:
             raise ValueError("filter_backward(adaptive=True) needs the forward pass's decisions filt['rs']")
         _chk(filt["rs"], (T, B), "filt['rs']", torch.int32)
-        name, decisions = "psvo_filter_backward_adaptive", (_ptr(filt["rs"]),)
+        name = "psvo_filter_backward_wobs_adaptive" if wobs else "psvo_filter_backward_adaptive"
+        decisions = (_ptr(filt["rs"]),)
     sacc = z((lib.psvo_filter_wobs_ws_floats if wobs else lib.psvo_filter_ws_floats)(B, T, N, Dx, Dy))
     upstream = (_ptr(dlse),) if (wobs and not ext) else (_ptr(dlse), nparts, _ptr(dFm), _ptr(dlogW))
     _mark(name, 0)
@@ -593,6 +611,12 @@ def filter_backward_wobs(*args, **kw):
     """psvo_filter_backward_wobs + psvo_mlp_wgrad (q1, f) + psvo_mlp_wgrad_wobs (g): the reverse of filter_forward_wobs;
     arguments and result of filter_backward (dFm / dlogW given: psvo_filter_backward_wobs_ext)."""
     return filter_backward(*args, wobs=True, **kw)
+
+
+def filter_backward_wobs_adaptive(*args, **kw):
+    """psvo_filter_backward_wobs_adaptive + psvo_mlp_wgrad (q1, f) + psvo_mlp_wgrad_wobs (g): the reverse of
+    filter_forward_wobs_adaptive, following the decisions filt["rs"]; arguments and result of filter_backward (dlse only)."""
+    return filter_backward(*args, wobs=True, adaptive="wobs", **kw)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -95,7 +95,9 @@ def main(FLAGS):
         raise ValueError("--FFBSi samples trajectories from the particle system of a filter objective (SVO, AESMC, IWAE); PSVO "
                          "and PSVOwR already return backward-simulation trajectories")
     check_resample_ess(getattr(FLAGS, "resample_ess", 0.0), never_resamples=bool(FLAGS.IWAE),
-                       backward_simulation=bool(FLAGS.PSVO or FLAGS.PSVOwR), output_cov=bool(FLAGS.output_cov), Dy=FLAGS.Dy)
+                       backward_simulation=bool(FLAGS.PSVO or FLAGS.PSVOwR), output_cov=bool(FLAGS.output_cov), Dy=FLAGS.Dy,
+                       wide_obs=bool(getattr(FLAGS, "resample_ess_wide_obs", False)),
+                       layers=[FLAGS.q1_layers, FLAGS.g_layers] + ([] if FLAGS.use_bootstrap else [FLAGS.f_layers]))
     if FLAGS.use_2_q:
         FLAGS.q_uses_true_X = False
     device = _device()
