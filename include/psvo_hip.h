@@ -294,6 +294,43 @@ int psvo_ffbs_sample(const psvo_desc* desc,
                      float* Xs, int32_t* idx_out, float* logq, int32_t* distinct, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Particle forecast: the k-step predictive distribution of a weighted particle cloud, k = 0..K, from every origin t of a
+ * sequence at once.  Added within ABI 6: purely additive.  Per sequence b and origin t:
+ *     w_n         = softmax_n(logW[t,b,:])                     (1 / N without logW)
+ *     x^(0)_n     = X[t,b,:,n]
+ *     x^(k+1)_n   = MLP_f(x^(k)_n) + sig_f (*) eps[k,t,b,:,n]  (no noise term without eps)
+ *     mu_n        = MLP_g(x^(k)_n)                             (emission 0);  softplus(MLP_g(x^(k)_n)) + 1e-6  (emission 1, 2)
+ *     ymean[k,t,b,:] = sum_n w_n mu_n
+ *     yvar [k,t,b,:] = sum_n w_n mu_n^2 - ymean^2 + v,          v = sig_g^2 (emission 0), 1 (emission 1), ymean (emission 2)
+ *     xmean[k,t,b,:] = sum_n w_n x^(k)_n
+ *     lpd  [k,t,b]   = logsumexp_n(log w_n + log g(obs[t+k,b,:] | x^(k)_n))   where t + k < T, else exactly 0
+ * with log g as the filter kernels score it: the diagonal normal around mu_n with scale sig_g (emissions 0 and 1; the caller
+ * passes ones for the unit-scale normal of emission 1) or sum_e y_e log mu_n,e - mu_n,e - log Gamma(y_e + 1) (emission 2).
+ * ymean, yvar and xmean are produced for every (k, t), past the end of the data included.  The caller passes q1's MLP and
+ * scale as f under the bootstrap wiring; desc->bootstrap is not looked at.
+ *
+ * A lane per particle, a workgroup per origin (four origins where N <= 64); the horizon loop runs in the kernel with one
+ * workgroup barrier per horizon.  No atomics and every sum in a fixed order (wave scan, then the waves in wave order): two
+ * calls on the same inputs give bit-identical outputs, with or without PSVO_TUNE_DETERMINISTIC.  No gradient.
+ *
+ *  desc            B, T, N, Dx, Dy, H, emission, layers are read.  Dx in {2,3,4}, 1 <= Dy <= 32, H in {16,32,64}, N <= 512,
+ *                  emission in {0,1,2}, one hidden layer (layers = 2: PSVO_ERR_UNSUPPORTED, as everything outside this list)
+ *  K               horizons beyond the origin, >= 0 (K = 0: the cloud read through the emission, no transition)
+ *  f, g            MLP_f (Dx -> Dx) and MLP_g (Dx -> Dy), one hidden layer of width H
+ *  sig_f (Dx)      transition scale; may be NULL without eps
+ *  sig_g (Dy)      emission scale; may be NULL for emission 2 only
+ *  X (T,B,Dx,N)    the cloud at every origin (the filter's Xanc, backward-sampled paths, ...)
+ *  logW (T,B,N)    log-weights of the cloud, or NULL = equal weights; entries of -inf are particles of weight zero
+ *  obs (T,B,Dy)    observations, or NULL (then lpd must be NULL)
+ *  eps (K,T,B,Dx,N) standard normals, or NULL = noise-free propagation of every particle
+ *  outputs: ymean, yvar (K+1,T,B,Dy), xmean (K+1,T,B,Dx), lpd (K+1,T,B); each may be NULL, not all (else PSVO_ERR_INVALID).
+ * ------------------------------------------------------------------------------------------- */
+int psvo_particle_forecast(const psvo_desc* desc, int K,
+                           const psvo_mlp* f, const psvo_mlp* g, const float* sig_f, const float* sig_g,
+                           const float* X, const float* logW, const float* obs, const float* eps,
+                           float* ymean, float* yvar, float* xmean, float* lpd, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Backward simulation with proposal, STATE-DEPENDENT diagonal scales (FLAGS.output_cov and FLAGS.diag_cov; see
  * psvo_filter_forward_cov).  Same loop and outputs as psvo_bsim_forward (PSVO.backward_simulation_w_proposal, reference
  * src/SMC/PSVO.py:69-203); differences:

@@ -96,6 +96,11 @@ class SVO:
         # adaptive resampling (FLAGS.resample_ess, not in the reference): 0 = off, else the ESS threshold as a fraction of N
         self.resample_ess = self._route_resample_ess(model, FLAGS)
 
+        # k-step predictive distribution of the evaluation's cloud (FLAGS.particle_forecast, not in the reference;
+        # psvo_particle_forecast); FLAGS.forecast_noise off = every particle propagated without transition noise
+        self.forecast = self._route_forecast(model, bool(getattr(FLAGS, "particle_forecast", False)))
+        self.forecast_noise = bool(getattr(FLAGS, "forecast_noise", True))
+
         self.name = name
         self.generator = None        # torch.Generator on the compute device; None = global RNG
 
@@ -138,6 +143,25 @@ class SVO:
         if deep:
             raise ValueError("Dy = %d with per-particle MLP layers %s: %s, which take one hidden layer per MLP; two hidden "
                              "layers run for Dy <= %d only" % (Dy, deep, limit, cls._PLAIN_DY))
+        return True
+
+    @classmethod
+    def _route_forecast(cls, model, on=True):
+        """`on` when the particle forecast (psvo_particle_forecast) covers this model.  What the kernel does not cover is refused
+        here, up front: it evaluates MLP_f and MLP_g with one hidden layer each, state-independent scales, Dy <= 32."""
+        if not on:
+            return False
+        Dy = getattr(model, "Dy", cls._PLAIN_DY)
+        limit = "--particle_forecast runs on the particle-forecast kernel (psvo_particle_forecast)"
+        if Dy > cls._WOBS_MAX_DY:
+            raise ValueError("Dy = %d: %s, which takes 1 <= Dy <= %d; no fallback path exists" % (Dy, limit, cls._WOBS_MAX_DY))
+        if getattr(model, "output_cov", False):
+            raise ValueError("output_cov: %s, which takes state-independent scales; the state-dependent-scale kernels have no "
+                             "forecast form" % limit)
+        trans = [t for t in (getattr(model, "f_tran", None), getattr(model, "g_tran", None)) if t is not None]
+        deep = [t.Dhs for t in dict.fromkeys(trans) if len(t.Dhs) != 1]
+        if deep:
+            raise ValueError("per-particle MLP layers %s: %s, which takes one hidden layer per MLP (f and g)" % (deep, limit))
         return True
 
     @classmethod
@@ -536,6 +560,44 @@ class SVO:
         y_hat_N_BxTxDy.append(self.g.mean(x_BxTmkxDz))
         y_N_BxTxDy = [obs[:, k:, :] for k in range(n_steps + 1)]
         return y_hat_N_BxTxDy, y_N_BxTxDy
+
+    def particle_forecast(self, n_steps, hidden, obs, noise=None):
+        """k-step predictive distribution of the cloud `hidden` (B,T,N,Dx), as log["Xs"] is, for k = 0 .. n_steps from every
+        origin t (psvo_particle_forecast; not in the reference).  Every particle is pushed through f -- q1's network and scale
+        when f shares them -- with transition noise: noise["eps_p"] (n_steps,T,B,Dx,N) injects the standard normals, else they
+        are drawn here; with FLAGS.forecast_noise off every particle is propagated noise-free.  The particles are equally
+        weighted (log["Xs"] is a resampled cloud, or whole paths).  n_steps >= T is valid: forecasts past the end of the data
+        are outputs too.  Evaluation only: no gradient, and under autograd the kernel is not launched (ValueError).
+
+        Returns {"y_mean", "y_var": (B,T,n_steps+1,Dy), "x_mean": (B,T,n_steps+1,Dx), "lpd": (B,T,n_steps+1) the predictive
+        log-density of obs[b, t+k] (0 where t + k >= T), "valid": (T,n_steps+1) bool, t + k < T, "forecast": the kernel's
+        output dict in its own layout}.  `n_step_prediction` beside it stays the reference's metric."""
+        if torch.is_grad_enabled():
+            raise ValueError("particle_forecast has no gradient: call it under torch.no_grad() (evaluation only)")
+        self._route_forecast(self.model)
+        B, T, N, Dx = hidden.shape
+        K = int(n_steps)
+        H, _, layers = self._kernel_width()
+        if layers != 1:
+            raise ValueError("particle_forecast with two hidden layers per particle MLP: psvo_particle_forecast takes one hidden "
+                             "layer; no fallback path exists")
+        model = self.model
+        X = _c(hidden.permute(1, 0, 3, 2))                 # (T,B,Dx,N): no copy when `hidden` is a view of a kernel-layout tensor
+        obs_TB = obs.transpose(0, 1).contiguous().float()
+        noise = noise or {}
+        eps = noise.get("eps_p")
+        if eps is None and self.forecast_noise and K > 0:
+            eps = self._randn(K, T, B, Dx, N, device=X.device)
+        f_tran, f_dist = (model.q1_tran, self.q1) if model.use_bootstrap else (model.f_tran, self.f)
+        desc = ops.make_desc(B, T, N, 1, Dx, model.Dy, H, bootstrap=model.use_bootstrap,
+                             emission=(2 if getattr(model, "count_emission", False)
+                                       else int(getattr(model, "poisson_emission", False))), layers=1)
+        fc = ops.particle_forecast(desc, K, _c(self._mlp_params(f_tran)), _c(self._mlp_params(model.g_tran)),
+                                   _c(self._sigma(f_dist)), _c(self._sigma(self.g)), X, obs=obs_TB, eps=eps)
+        t = torch.arange(T, device=X.device)
+        return {"y_mean": fc["ymean"].permute(2, 1, 0, 3), "y_var": fc["yvar"].permute(2, 1, 0, 3),
+                "x_mean": fc["xmean"].permute(2, 1, 0, 3), "lpd": fc["lpd"].permute(2, 1, 0),
+                "valid": (t[:, None] + torch.arange(K + 1, device=X.device)[None, :]) < T, "forecast": fc}
 
     def get_nextX(self, X):
         """SVO.py:406-409 (quiver plots)."""

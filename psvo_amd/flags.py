@@ -87,6 +87,10 @@ DEFINITIONS = [
     # (not in the reference's registry) adaptive resampling on observations wider than two: the wide-observation filter kernels
     # in their adaptive form.  Off by default: without it --resample_ess stays refused at Dy > 2
     ("resample_ess_wide_obs", bool, False, "SVO / AESMC: run --resample_ess at 3 <= Dy <= 32 on the wide-observation adaptive kernels"),
+    # k-step predictive distribution of the evaluation's particle cloud (not in the reference's registry, whose only forecast
+    # pushes the cloud's mean through f): off by default, evaluation only; every objective
+    ("particle_forecast", bool, False, "evaluate the k-step predictive mean, variance and log-density of the whole particle cloud"),
+    ("forecast_noise", bool, True, "--particle_forecast: apply transition noise to every particle (off: noise-free propagation)"),
     # printing and data saving (runner_flag.py:131-153)
     ("print_freq", int, 1, "frequency to evaluate testing loss & other metrics and save results"),
     ("save_trajectory", bool, True, "whether to save hidden trajectories during training"),

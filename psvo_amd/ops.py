@@ -741,6 +741,39 @@ def ffbs_sample(desc, filt, sig_f=None, u=None, idx_in=None):
     return out
 
 
+def particle_forecast(desc, K, f, g, sig_f, sig_g, X, logW=None, obs=None, eps=None):
+    """psvo_particle_forecast: the k-step predictive distribution, k = 0..K, of the weighted cloud `X` (T,B,Dx,N) at every origin.
+    `f`, `g` are the MLP tuples of the transition and the emission at the kernels' width (one hidden layer), `sig_f` (Dx) and
+    `sig_g` (Dy) their scales (sig_g may be None for the count emission).  `logW` (T,B,N) log-weights or None = equal weights,
+    `obs` (T,B,Dy) or None = no predictive log-density, `eps` (K,T,B,Dx,N) standard normals or None = noise-free propagation.
+    Returns dict(ymean, yvar (K+1,T,B,Dy), xmean (K+1,T,B,Dx), lpd (K+1,T,B) or None without obs; lpd is 0 where t + k >= T).
+    Asynchronous on the launch stream."""
+    lib = _lib.load()
+    B, T, N, Dx, Dy, H = desc.B, desc.T, desc.N, desc.Dx, desc.Dy, desc.H
+    K = int(K)
+    if K < 0:
+        raise ValueError("particle_forecast: K = %d horizons; K >= 0" % K)
+    if X is None:
+        raise ValueError("particle_forecast needs the cloud X (T,B,Dx,N)")
+    _chk(X, (T, B, Dx, N), "X"); _chk(logW, (T, B, N), "logW"); _chk(obs, (T, B, Dy), "obs")
+    _chk(eps, (K, T, B, Dx, N), "eps"); _chk(sig_f, (Dx,), "sig_f"); _chk(sig_g, (Dy,), "sig_g")
+    if eps is not None and sig_f is None:
+        raise ValueError("particle_forecast: transition noise `eps` needs the transition scale `sig_f`")
+    if sig_g is None and desc.emission != 2:
+        raise ValueError("particle_forecast: the emission scale `sig_g` may be None for the count emission only")
+    fs, gs = _mlp_struct(f, Dx, H, Dx, "f"), _mlp_struct(g, Dx, H, Dy, "g")
+    dev = X.device
+    out = {"ymean": _empty(K + 1, T, B, Dy, device=dev), "yvar": _empty(K + 1, T, B, Dy, device=dev),
+           "xmean": _empty(K + 1, T, B, Dx, device=dev), "lpd": _empty(K + 1, T, B, device=dev) if obs is not None else None}
+    _mark("psvo_particle_forecast", 0)
+    st = lib.psvo_particle_forecast(ctypes.byref(desc), K, ctypes.byref(fs), ctypes.byref(gs), _ptr(sig_f), _ptr(sig_g), _ptr(X),
+                                    _ptr(logW), _ptr(obs), _ptr(eps), _ptr(out["ymean"]), _ptr(out["yvar"]), _ptr(out["xmean"]),
+                                    _ptr(out["lpd"]), _stream())
+    _mark("psvo_particle_forecast", 1)
+    _lib.check(st, "psvo_particle_forecast")
+    return out
+
+
 def filter_backward_cov(desc, q1, f, g, sigc_q1, sigc_f, sigc_g, mu2, sig2, m0, sig0, fm0, fsig0, obs, eps, filt,
                         dlse=None, dFm=None, dFs=None, dlogW=None):
     """psvo_filter_backward_cov + two psvo_mlp_wgrad launches per MLP (one per head; both contribute to dW1 / db1).

@@ -29,6 +29,13 @@ as ffbsi_distinct_mean_<split> / ffbsi_distinct_min_<split>.  Training steps are
 Adaptive resampling (FLAGS.resample_ess, off by default; SVO / AESMC): training and evaluation run the adaptive filter kernels;
 at every evaluation the share of (sequence, step) pairs that resampled and the mean / minimum of ESS / N over each split are
 printed and go into metric_<iter>.p as adaptive_rate_<split>, adaptive_ess_mean_<split>, adaptive_ess_min_<split>.
+
+Particle forecast (FLAGS.particle_forecast, off by default; every objective): every evaluation then also runs
+psvo_particle_forecast on the evaluation's own cloud (SVO.particle_forecast) for k = 0 .. MSE_steps; per horizon the mean predictive
+log-density over the (sequence, origin) pairs whose target lies inside the data, the R-square of the predictive mean and the
+calibration mean((y - y_mean)^2 / y_var) (about 1 when calibrated) are printed and go into metric_<iter>.p as forecast_lpd_<split>,
+forecast_R_square_<split>, forecast_calibration_<split>; y_hat_<epoch>.p gains y_mean and y_var of the saved sequences.
+Training steps are untouched.
 """
 import math
 import os
@@ -59,6 +66,20 @@ def _r_square(y_hat, y):
     resid = y_hat - y
     centred = y - y.mean(axis=0, keepdims=True)
     return 1.0 - float(np.square(resid).sum()) / float(np.square(centred).sum())
+
+
+def _forecast_metrics(y_mean, y_var, lpd, obs):
+    """(lpd, R-square, calibration) per horizon k = 0 .. K of a particle forecast over one split: y_mean, y_var (n,T,K+1,Dy),
+    lpd (n,T,K+1), obs (n,T,Dy).  Horizon k pairs origin t with obs[:, t + k], t + k < T; a horizon with no such pair (K >= T)
+    is NaN.  R-square as _r_square defines it."""
+    n, T, K1, _ = y_mean.shape
+    out = np.full((3, K1), np.nan)
+    for k in range(min(K1, T)):
+        y, m, v = obs[:, k:], y_mean[:, :T - k, k], y_var[:, :T - k, k]
+        out[0, k] = float(np.mean(lpd[:, :T - k, k]))
+        out[1, k] = _r_square(m, y)
+        out[2, k] = float(np.mean(np.square(y - m) / v))
+    return out[0], out[1], out[2]
 
 
 def _collate(per_batch, keepdims):
@@ -223,15 +244,21 @@ class trainer:
         which its notebook reads back (notebooks/PSVO.ipynb: `lattice_dict["X_trajs"], ["X"], ["nextX"]`)."""
         self.saving_feed_dict = {self.obs: obs_test[:self.saving_num], self.hidden: hidden_test[:self.saving_num]}
         Xs_val = None
+        forecast = bool(getattr(self.SMC, "forecast", False))
         for flag, fetch, stem in ((self.save_trajectory, "Xs", "trajectory"), (self.save_y_hat, "y_hat", "y_hat")):
             if not flag:
                 continue
-            val = self.evaluate(fetch, self.saving_feed_dict, average=False)      # (collective: every rank takes part)
+            extra = {}
+            if forecast and fetch == "y_hat":      # (FLAGS.particle_forecast: the predictive moments beside the point forecast)
+                val, extra["y_mean"], extra["y_var"] = self.evaluate([fetch, "forecast_y_mean", "forecast_y_var"],
+                                                                     self.saving_feed_dict, average=False)
+            else:
+                val = self.evaluate(fetch, self.saving_feed_dict, average=False)      # (collective: every rank takes part)
             if fetch == "Xs":
                 Xs_val = val
             if write:
                 with open(self.epoch_data_DIR + "{}_{}.p".format(stem, epoch), "wb") as f:
-                    pickle.dump({fetch: val}, f)
+                    pickle.dump(dict({fetch: val}, **extra), f)
         if self.Dx == 2 and Xs_val is not None:      # (the reference draws from the trajectories it has just saved)
             lattice = self.quiver_lattice(Xs_val)
             if write:
@@ -268,11 +295,19 @@ class trainer:
         ffbs = bool(getattr(self.SMC, "FFBS", False))
         ffbsi = bool(getattr(self.SMC, "FFBSi", False))
         adaptive = bool(getattr(self.SMC, "resample_ess", 0.0))
+        forecast = bool(getattr(self.SMC, "forecast", False))
         fetches = (["log_ZSMC", "y_hat", "y"] + (["ess", "resampled"] if adaptive else []) + (["ess_smooth"] if ffbs else [])
                    + (["path_distinct"] if ffbsi else []))
+        if forecast:       # (last, so that the fetches ahead of them keep their places)
+            fetches += ["forecast_y_mean", "forecast_y_var", "forecast_lpd"]
         m, ess = {}, {}
         for split, obs, hid in (("train", self.obs_train, self.hidden_train), ("test", self.obs_test, self.hidden_test)):
             elbos, y_hat, y, *rest = self.evaluate(fetches, {self.obs: obs, self.hidden: hid})
+            if forecast:
+                fc, rest = rest[-3:], rest[:-3]
+                lpd, rsq, cal = _forecast_metrics(*fc, np.asarray(obs, dtype=np.float32))
+                ess["forecast_lpd_" + split], ess["forecast_R_square_" + split] = lpd, rsq
+                ess["forecast_calibration_" + split] = cal
             if adaptive:
                 frac, rest = np.asarray(rest[0]) / float(self.n_particles), rest[1:]
                 ess["adaptive_rate_" + split] = float(np.mean(rest[0]))
@@ -304,6 +339,13 @@ class trainer:
                 print("FFBSi distinct particles per step (of {}), mean / min: train {:.2f} / {:.0f}, valid {:.2f} / {:.0f}"
                       .format(self.n_particles, ess["ffbsi_distinct_mean_train"], ess["ffbsi_distinct_min_train"],
                               ess["ffbsi_distinct_mean_test"], ess["ffbsi_distinct_min_test"]))
+
+            if forecast:
+                print("particle forecast, k = 0 .. {}: predictive log-density train, valid:\n".format(self.MSE_steps),
+                      ess["forecast_lpd_train"], "\n", ess["forecast_lpd_test"])
+                print("particle forecast Rsq train, valid:\n", ess["forecast_R_square_train"], "\n", ess["forecast_R_square_test"])
+                print("particle forecast calibration (1 = calibrated) train, valid:\n", ess["forecast_calibration_train"], "\n",
+                      ess["forecast_calibration_test"])
 
         if not math.isfinite(m["log_ZSMC_train"]):
             print("Nan in log_ZSMC, stop training")
@@ -387,6 +429,11 @@ class trainer:
                     y_hat, y = self.SMC.n_step_prediction(self.MSE_steps, Xs, obs_d)
                     out["y_hat"] = [v.cpu().numpy() for v in y_hat]
                     out["y"] = [v.cpu().numpy() for v in y]
+            if any(n.startswith("forecast_") for n in names):       # FLAGS.particle_forecast only
+                fc = self.SMC.particle_forecast(self.MSE_steps, log["Xs"], obs_d)
+                out["forecast_y_mean"] = fc["y_mean"].contiguous().cpu().numpy()      # (B, T, K+1, Dy)
+                out["forecast_y_var"] = fc["y_var"].contiguous().cpu().numpy()
+                out["forecast_lpd"] = fc["lpd"].contiguous().cpu().numpy()            # (B, T, K+1); 0 where t + k >= T
             if "ess" in names:
                 out["ess"] = log["ess"].contiguous().cpu().numpy()                    # (B, T); FLAGS.resample_ess only
             if "resampled" in names:
