@@ -69,11 +69,24 @@ class PSVO(SVO):
         self._release()
         return log_ZSMC, log
 
+    def _bsim_draws(self, noise, obs):
+        """the backward simulation's randomness -> (eps_b (T,B,Dx,N,M), u_b (T,B,N) or None, sel_in, obs_TB): injected through
+        `noise` (eps_b, u_b / sel_b) or drawn here, eps_b before u_b; obs_TB (T,B,Dy) is the copy SMC() made of this batch"""
+        T, B, N = self.time, self.batch_size, self.n_particles
+        eps_b = noise.get("eps_b")
+        if eps_b is None:
+            eps_b = self._randn(T, B, self.Dx, N, self.n_particles_for_BSim_proposal, device=obs.device)
+        u_b, sel_in = noise.get("u_b"), noise.get("sel_b")
+        if u_b is None and sel_in is None:
+            u_b = self._rand(T, B, N, device=obs.device)
+        obs_TB = getattr(self, "_obs_TB", None)
+        if obs_TB is None or obs_TB.shape[:2] != (T, B):
+            obs_TB = obs.transpose(0, 1).contiguous().float()
+        return eps_b, u_b, sel_in, obs_TB
+
     def _backward_simulation_cov(self, filt, obs, noise):
         model = self.model
-        Dx, T, N, B = self.Dx, self.time, self.n_particles, self.batch_size
-        M = self.n_particles_for_BSim_proposal
-        dev = obs.device
+        Dx, B, M = self.Dx, self.batch_size, self.n_particles_for_BSim_proposal
         _, preprocessed_obs = self.BS_preprocess_obs(obs)                        # (B, T, 2Dh)
         bmu2, bsig2 = (v.transpose(0, 1).contiguous()
                        for v in self.BSim_q2.mean_and_sigma(preprocessed_obs, self._sigma(self.BSim_q2)))    # (T, B, Dx)
@@ -83,15 +96,7 @@ class PSVO(SVO):
             imean, isig = self.f.mean_and_sigma(mu_0, self._sigma(self.f))       # PSVO.py:171
         else:
             imean, isig = self._m0, self._sig0                                   # PSVO.py:173: q0's density at mu_0
-        eps_b = noise.get("eps_b")
-        if eps_b is None:
-            eps_b = self._randn(T, B, Dx, N, M, device=dev)
-        u_b, sel_in = noise.get("u_b"), noise.get("sel_b")
-        if u_b is None and sel_in is None:
-            u_b = self._rand(T, B, N, device=dev)
-        obs_TB = getattr(self, "_obs_TB", None)
-        if obs_TB is None or obs_TB.shape[:2] != (T, B):
-            obs_TB = obs.transpose(0, 1).contiguous().float()
+        eps_b, u_b, sel_in, obs_TB = self._bsim_draws(noise, obs)
         score, bwX, flp, glp, Omega, sel = BsimCovFunction.apply(
             self._desc(M), obs_TB, eps_b, u_b, sel_in, filt["Fm"], filt["Fs"], filt["logW"], filt["lse"],
             *self._mlp_params_cov(model.f_tran), *self._mlp_params_cov(model.g_tran), *self._mlp_params_cov(model.q1_inv_tran),
@@ -105,10 +110,7 @@ class PSVO(SVO):
 
     def backward_simulation_w_proposal(self, filt, obs, noise=None):
         model = self.model
-        Dx, T, N, B = self.Dx, self.time, self.n_particles, self.batch_size
         M = self.n_particles_for_BSim_proposal
-        dev = obs.device
-        noise = noise or {}
 
         _, preprocessed_obs = self.BS_preprocess_obs(obs)                        # (B, T, 2Dh)
         bmu2 = self.BSim_q2.mean(preprocessed_obs).transpose(0, 1).contiguous()   # (T, B, Dx)
@@ -120,15 +122,7 @@ class PSVO(SVO):
             # PSVO.py:173: q0.log_prob(mu_0, .) -- the very MLP_q0(mu_0) / sigma_q0 the filter used at t = 0
             imean, isig = self._m0, self._sig0
 
-        eps_b = noise.get("eps_b")
-        if eps_b is None:
-            eps_b = self._randn(T, B, Dx, N, M, device=dev)
-        u_b, sel_in = noise.get("u_b"), noise.get("sel_b")
-        if u_b is None and sel_in is None:
-            u_b = self._rand(T, B, N, device=dev)
-        obs_TB = getattr(self, "_obs_TB", None)                                  # cached by SMC() for this batch
-        if obs_TB is None or obs_TB.shape[:2] != (T, B):
-            obs_TB = obs.transpose(0, 1).contiguous().float()
+        eps_b, u_b, sel_in, obs_TB = self._bsim_draws(noise or {}, obs)
 
         # one opaque autograd node: psvo_bsim_forward / psvo_bsim_backward, or their wide-observation forms (Dy > 2)
         desc = self._desc(M)

@@ -56,7 +56,6 @@ class PSVOwR(PSVO):
         filt = self.SMC(None, obs, noise=noise)
         Dx, T, N, B = self.Dx, self.time, self.n_particles, self.batch_size
         M = self.n_particles_for_BSim_proposal
-        dev = obs.device
         _, preprocessed_obs = self.BS_preprocess_obs(obs)
         bmu2, bsig2 = (v.transpose(0, 1).contiguous()
                        for v in self.BSim_q2.mean_and_sigma(preprocessed_obs, self._sigma(self.BSim_q2)))
@@ -66,18 +65,7 @@ class PSVOwR(PSVO):
             imean, isig = self.f.mean_and_sigma(mu_0, self._sigma(self.f))       # PSVOwR.py:167
         else:
             imean, isig = self._m0, self._sig0                                   # PSVOwR.py:169
-        eps_b = noise.get("eps_b")
-        if eps_b is None:
-            eps_b = self._randn(T, B, Dx, N, M, device=dev)
-        u_b, sel_in = noise.get("u_b"), noise.get("sel_b")
-        if u_b is None and sel_in is None:
-            u_b = self._rand(T, B, N, device=dev)
-        u_r, anc_in = noise.get("u_r"), noise.get("anc_r")
-        if u_r is None and anc_in is None:
-            u_r = self._rand(T, B, N, device=dev)
-        obs_TB = getattr(self, "_obs_TB", None)
-        if obs_TB is None or obs_TB.shape[:2] != (T, B):
-            obs_TB = obs.transpose(0, 1).contiguous().float()
+        eps_b, u_b, u_r, sel_in, anc_in, obs_TB = self._bsimwr_draws(noise, obs)
         lseW, bwXanc, bwX, bwW, sel, anc = BsimWRCovFunction.apply(
             self._desc(M), obs_TB, eps_b, u_b, u_r, sel_in, anc_in, filt["Fm"], filt["Fs"], filt["logW"], filt["lse"],
             *self._mlp_params_cov(model.f_tran), *self._mlp_params_cov(model.g_tran), *self._mlp_params_cov(model.q1_inv_tran),
@@ -90,12 +78,19 @@ class PSVOwR(PSVO):
         self._release()
         return log_ZSMC, log
 
+    def _bsimwr_draws(self, noise, obs):
+        """PSVO._bsim_draws and, behind them, the cross-chain draw (u_r / anc_r)
+        -> (eps_b, u_b, u_r (T,B,N) or None, sel_in, anc_in, obs_TB)"""
+        eps_b, u_b, sel_in, obs_TB = self._bsim_draws(noise, obs)
+        u_r, anc_in = noise.get("u_r"), noise.get("anc_r")
+        if u_r is None and anc_in is None:
+            u_r = self._rand(self.time, self.batch_size, self.n_particles, device=obs.device)
+        return eps_b, u_b, u_r, sel_in, anc_in, obs_TB
+
     def backward_simulation_w_resampling(self, filt, obs, noise=None):
         model = self.model
-        Dx, T, N, B = self.Dx, self.time, self.n_particles, self.batch_size
         M = self.n_particles_for_BSim_proposal
         dev = obs.device
-        noise = noise or {}
 
         _, preprocessed_obs = self.BS_preprocess_obs(obs)
         bmu2 = self.BSim_q2.mean(preprocessed_obs).transpose(0, 1).contiguous()
@@ -106,18 +101,7 @@ class PSVOwR(PSVO):
         else:
             imean, isig = self._m0, self._sig0                                   # PSVOwR.py:169
 
-        eps_b = noise.get("eps_b")
-        if eps_b is None:
-            eps_b = self._randn(T, B, Dx, N, M, device=dev)
-        u_b, sel_in = noise.get("u_b"), noise.get("sel_b")
-        if u_b is None and sel_in is None:
-            u_b = self._rand(T, B, N, device=dev)
-        u_r, anc_in = noise.get("u_r"), noise.get("anc_r")
-        if u_r is None and anc_in is None:
-            u_r = self._rand(T, B, N, device=dev)
-        obs_TB = getattr(self, "_obs_TB", None)                                  # cached by SMC() for this batch
-        if obs_TB is None or obs_TB.shape[:2] != (T, B):
-            obs_TB = obs.transpose(0, 1).contiguous().float()
+        eps_b, u_b, u_r, sel_in, anc_in, obs_TB = self._bsimwr_draws(noise or {}, obs)
 
         desc = self._desc(M)
         gb = (self._gbuf(model.f_tran), self._gbuf(model.g_tran), self._gbuf(model.q1_inv_tran))

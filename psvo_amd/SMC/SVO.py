@@ -367,16 +367,29 @@ class SVO:
     def _make_desc(self, M, H):
         return ops.make_desc(self.batch_size, self.time, self.n_particles, M, self.model.Dx, self.model.Dy, H,
                              resample=self.resample_particles, two_q=self.model.use_2_q,
-                             bootstrap=self.model.use_bootstrap,
-                             emission=(2 if getattr(self.model, "count_emission", False)
-                                       else int(getattr(self.model, "poisson_emission", False))),
+                             bootstrap=self.model.use_bootstrap, emission=self._emission_code(),
                              layers=self._kernel_width()[2])
+
+    def _emission_code(self):
+        """psvo_desc.emission: 2 = count (Poisson) emission, 1 = tf_poisson (unit-scale normal around the rate), 0 = normal"""
+        return 2 if getattr(self.model, "count_emission", False) else int(getattr(self.model, "poisson_emission", False))
 
     def _randn(self, *shape, device):
         return torch.randn(*shape, device=device, dtype=torch.float32, generator=self.generator)
 
     def _rand(self, *shape, device):
         return torch.rand(*shape, device=device, dtype=torch.float32, generator=self.generator)
+
+    def _filter_draws(self, noise, dev):
+        """the filter's randomness (eps (T,B,Dx,N), u (T,B,N) or None, idx_in): noise["eps_f"], ["u_f"] / ["idx_f"], or drawn, eps first"""
+        T, B, N = self.time, self.batch_size, self.n_particles
+        eps = noise.get("eps_f")
+        if eps is None:
+            eps = self._randn(T, B, self.Dx, N, device=dev)
+        u, idx_in = noise.get("u_f"), noise.get("idx_f")
+        if self.resample_particles and u is None and idx_in is None:
+            u = self._rand(T, B, N, device=dev)
+        return eps, u, idx_in
 
     def SMC(self, hidden, obs, q_cov=1.0, noise=None):
         """SVO.py:60-180.  Returns the kernel's output dict: X (pre-resampling, Xs_ta),
@@ -388,7 +401,6 @@ class SVO:
         model = self.model
         if model.output_cov:
             return self._SMC_cov(obs, noise)
-        Dx, T, N, B = self.Dx, self.time, self.n_particles, self.batch_size
         dev = obs.device
         noise = noise or {}
 
@@ -419,12 +431,7 @@ class SVO:
                 mu2 = self.q2.mean(preprocessed_obs).transpose(0, 1).contiguous()
             sig_q2 = self._sigma(self.q2)
 
-        eps = noise.get("eps_f")
-        if eps is None:
-            eps = self._randn(T, B, Dx, N, device=dev)
-        u, idx_in = noise.get("u_f"), noise.get("idx_f")
-        if self.resample_particles and u is None and idx_in is None:
-            u = self._rand(T, B, N, device=dev)
+        eps, u, idx_in = self._filter_draws(noise, dev)
 
         first, extra = self._mlp_args(self._mlp_params(model.q1_tran),
                                       None if model.use_bootstrap else self._mlp_params(model.f_tran),
@@ -469,7 +476,7 @@ class SVO:
         (q0, q2 and, outside the default wiring, f on the X0 feature) hand over mean AND scale per row; the per-particle
         MLPs carry their second head into the kernel."""
         model = self.model
-        Dx, T, N, B = self.Dx, self.time, self.n_particles, self.batch_size
+        Dx, B = self.Dx, self.batch_size
         dev = obs.device
         noise = noise or {}
         if self._kernel_width()[2] != 1:
@@ -495,12 +502,7 @@ class SVO:
                 mu2, sig2 = (v.transpose(0, 1).contiguous()
                              for v in self.q2.mean_and_sigma(preprocessed_obs, self._sigma(self.q2)))
 
-        eps = noise.get("eps_f")
-        if eps is None:
-            eps = self._randn(T, B, Dx, N, device=dev)
-        u, idx_in = noise.get("u_f"), noise.get("idx_f")
-        if self.resample_particles and u is None and idx_in is None:
-            u = self._rand(T, B, N, device=dev)
+        eps, u, idx_in = self._filter_draws(noise, dev)
 
         q1p = self._mlp_params_cov(model.q1_tran)
         fp = (None,) * 6 if model.use_bootstrap else self._mlp_params_cov(model.f_tran)
@@ -589,9 +591,7 @@ class SVO:
         if eps is None and self.forecast_noise and K > 0:
             eps = self._randn(K, T, B, Dx, N, device=X.device)
         f_tran, f_dist = (model.q1_tran, self.q1) if model.use_bootstrap else (model.f_tran, self.f)
-        desc = ops.make_desc(B, T, N, 1, Dx, model.Dy, H, bootstrap=model.use_bootstrap,
-                             emission=(2 if getattr(model, "count_emission", False)
-                                       else int(getattr(model, "poisson_emission", False))), layers=1)
+        desc = ops.make_desc(B, T, N, 1, Dx, model.Dy, H, bootstrap=model.use_bootstrap, emission=self._emission_code(), layers=1)
         fc = ops.particle_forecast(desc, K, _c(self._mlp_params(f_tran)), _c(self._mlp_params(model.g_tran)),
                                    _c(self._sigma(f_dist)), _c(self._sigma(self.g)), X, obs=obs_TB, eps=eps)
         t = torch.arange(T, device=X.device)

@@ -127,6 +127,16 @@ SIGNATURES = {
     "psvo_elbo_bsim_mean_backward": (ctypes.c_int, [_DESC, _P, _P, _P, _P]),
 }
 
+# environment variable -> the psvo_set_tuning key load() sets from it
+ENV_TUNING = (
+    ("PSVO_BSIM_BWD_VARIANT", PSVO_TUNE_BSIM_BWD),      # A/B measurements (tools/, bench.py --bsim-bwd-variant)
+    ("PSVO_SKEW", PSVO_TUNE_SKEW),                      # A/B: phase offset of co-resident workgroups, per cent (0 = off)
+    ("PSVO_FILTER_BWD_SCAN", PSVO_TUNE_FILTER_BWD),     # A/B: 0 = the persistent reverse filter kernel instead of the affine scan
+    ("PSVO_WGRAD2", PSVO_TUNE_WGRAD2),                  # A/B: two-layer weight gradients on the bf16 matrix instructions (2 / 3 pieces)
+    ("PSVO_L2_SPLIT", PSVO_TUNE_L2_SPLIT),              # A/B: two-layer backward-simulation kernels with the half-split chains
+    ("PSVO_DETERMINISTIC", PSVO_TUNE_DETERMINISTIC),    # 1: fixed-order sums on the reverse paths (bit-reproducible gradients)
+)
+
 _lib = None
 
 
@@ -146,24 +156,10 @@ def load():
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
-        v = os.environ.get("PSVO_BSIM_BWD_VARIANT")      # A/B measurements (tools/, bench.py --bsim-bwd-variant)
-        if v is not None and lib.psvo_set_tuning(PSVO_TUNE_BSIM_BWD, int(v)) != PSVO_OK:
-            raise PsvoHipError("PSVO_BSIM_BWD_VARIANT=%s is not a valid psvo_set_tuning value" % v)
-        v = os.environ.get("PSVO_SKEW")                  # A/B: phase offset of co-resident workgroups, per cent (0 = off)
-        if v is not None and lib.psvo_set_tuning(PSVO_TUNE_SKEW, int(v)) != PSVO_OK:
-            raise PsvoHipError("PSVO_SKEW=%s is not a valid psvo_set_tuning value" % v)
-        v = os.environ.get("PSVO_FILTER_BWD_SCAN")       # A/B: 0 = the persistent reverse filter kernel instead of the affine scan
-        if v is not None and lib.psvo_set_tuning(PSVO_TUNE_FILTER_BWD, int(v)) != PSVO_OK:
-            raise PsvoHipError("PSVO_FILTER_BWD_SCAN=%s is not a valid psvo_set_tuning value" % v)
-        v = os.environ.get("PSVO_WGRAD2")                # A/B: two-layer weight gradients on the bf16 matrix instructions (2 / 3 pieces)
-        if v is not None and lib.psvo_set_tuning(PSVO_TUNE_WGRAD2, int(v)) != PSVO_OK:
-            raise PsvoHipError("PSVO_WGRAD2=%s is not a valid psvo_set_tuning value" % v)
-        v = os.environ.get("PSVO_L2_SPLIT")              # A/B: two-layer backward-simulation kernels with the half-split chains
-        if v is not None and lib.psvo_set_tuning(PSVO_TUNE_L2_SPLIT, int(v)) != PSVO_OK:
-            raise PsvoHipError("PSVO_L2_SPLIT=%s is not a valid psvo_set_tuning value" % v)
-        v = os.environ.get("PSVO_DETERMINISTIC")         # 1: fixed-order sums on the reverse paths (bit-reproducible gradients)
-        if v is not None and lib.psvo_set_tuning(PSVO_TUNE_DETERMINISTIC, int(v)) != PSVO_OK:
-            raise PsvoHipError("PSVO_DETERMINISTIC=%s is not a valid psvo_set_tuning value" % v)
+        for var, key in ENV_TUNING:
+            v = os.environ.get(var)
+            if v is not None and lib.psvo_set_tuning(key, int(v)) != PSVO_OK:
+                raise PsvoHipError("%s=%s is not a valid psvo_set_tuning value" % (var, v))
         _lib = lib
     return _lib
 

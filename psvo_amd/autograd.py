@@ -145,6 +145,66 @@ def _used_on(stream, tensors):
             t.record_stream(stream)
 
 
+def _filter_forward(ctx, op, desc, obs_TB, eps, u, idx_in, t, ov=None, **route):
+    """a filter node's forward (state-independent scales): op (ops.filter_forward / _wobs / _wobs_adaptive; `route`: ess_frac
+    and rs_in of the adaptive entry points) on the node's positional tensors `t`; keeps on ctx what the reverse pass needs and
+    returns op's dict.  ov: the overlap wiring (FilterFunction under PSVO / PSVOwR) -- the launch goes to the side stream and
+    the consumer (BsimFunction) waits on ov.filter_done."""
+    # missing upstream gradients stay None: a zero tensor materialised by the engine would be filled on the
+    # main stream AFTER the event the side-stream reverse pass waits for
+    ctx.set_materialize_grads(False)
+    t = [_cf(v) for v in t]
+    q1, f, g = _mlps(t)
+    rest = t[12:21]                 # sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, fm0, fsig0
+    if desc.bootstrap:
+        f = None
+    if ov is not None:
+        ov.side.wait_stream(torch.cuda.current_stream())
+        with ops.launch_on(ov.side):
+            filt = op(desc, q1, f, g, *rest, obs_TB, eps, u, idx_in, **route)
+        ov.filter_done = torch.cuda.Event()
+        ov.filter_done.record(ov.side)
+        _used_on(torch.cuda.current_stream(), filt.values())
+    else:
+        filt = op(desc, q1, f, g, *rest, obs_TB, eps, u, idx_in, **route)
+    ctx.desc, ctx.filt = desc, _aliases(filt)
+    ctx.saved = (q1, f, g, rest, obs_TB, eps)
+    return filt
+
+
+def _filter_grads(r, desc, m0, sig0, fm0, fsig0, gbufs):
+    """a filter node's gradients behind its leading non-tensor inputs, from the reverse wrapper's dict `r`: the twelve MLP
+    tensors, sig_q1 .. fsig0 and -- two hidden layers -- the (Wh, bh) extras.  gbufs: the (q1, f, g) slices of the flat
+    gradient buffer the kernels accumulated into (no tensor is returned for those MLPs), or None."""
+    Dx, Dy, H = desc.Dx, desc.Dy, desc.H
+    two_q, boot = bool(desc.two_q), bool(desc.bootstrap)
+    gfirst, gextra = _mlp_grads(r, ("gq1", None if boot else "gf", "gg"), ((Dx, Dx), (Dx, Dx), (Dx, Dy)), H,
+                                2 if desc.layers == 2 else 1, gbufs or (None, None, None))
+    # (one tensor passed as both m0 and fm0 -- the default wiring -- gets the summed gradient in d m0 from the kernel:
+    #  returning the zero d fm0 as well would only make the engine launch an add; likewise sig0 / fsig0)
+    same_m = m0.data_ptr() == fm0.data_ptr()
+    same_s = sig0.data_ptr() == fsig0.data_ptr()
+    return gfirst + (
+        r["dsig_q1"], r["dsig_q2"] if two_q else None, None if boot else r["dsig_f"], r["dsig_g"],
+        r["dmu2"] if two_q else None, r["dm0"], r["dsig0"], None if same_m else r["dfm0"],
+        None if same_s else r["dfsig0"]) + gextra
+
+
+def _filter_backward(ctx, op, lead, dlse, dFm=None, dlogW=None, **route):
+    """its reverse on one stream (op: ops.filter_backward / _wobs / _wobs_adaptive; `route`: gbufs, adaptive): None for the
+    `lead` non-tensor inputs, then _filter_grads"""
+    q1, f, g, rest, obs_TB, eps = ctx.saved
+    r = op(ctx.desc, q1, f, g, *rest, obs_TB, eps, ctx.filt, dlse=_cg(dlse), dFm=_cg(dFm), dlogW=_cg(dlogW), **route)
+    return (None,) * lead + _filter_grads(r, ctx.desc, *rest[5:9], route.get("gbufs"))
+
+
+def _adaptive_outputs(ctx, filt):
+    """the outputs of an adaptive filter node: nothing runs behind it under autograd, so everything but lse is a constant"""
+    const = (filt["Fm"], filt["logW"], filt["X"], filt["Xanc"], filt["idx"], filt["rs"], filt["ess"])
+    ctx.mark_non_differentiable(*const)
+    return (filt["lse"],) + const
+
+
 class FilterFunction(torch.autograd.Function):
     """psvo_filter_forward / psvo_filter_backward.
 
@@ -158,29 +218,9 @@ class FilterFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, desc, obs_TB, eps, u, idx_in, *t):
-        # missing upstream gradients stay None: a zero tensor materialised by the engine would be filled on the
-        # main stream AFTER the event the side-stream reverse pass waits for
-        ctx.set_materialize_grads(False)
-        t = [_cf(v) for v in t]
-        q1, f, g = _mlps(t)
-        sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, fm0, fsig0 = t[12:21]
         ctx.gbufs = getattr(desc, "_gbufs", None)     # (q1, f, g) flat-gradient slices or None
-        if desc.bootstrap:
-            f = None
-        ov = getattr(desc, "_ov", None)             # shared with the BsimFunction of the same evaluation
-        if ov is not None:                          # PSVO: the consumer (BsimFunction) waits on ov.filter_done
-            ov.side.wait_stream(torch.cuda.current_stream())
-            with ops.launch_on(ov.side):
-                filt = ops.filter_forward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, fm0, fsig0,
-                                          obs_TB, eps, u, idx_in)
-            ov.filter_done = torch.cuda.Event()
-            ov.filter_done.record(ov.side)
-            _used_on(torch.cuda.current_stream(), filt.values())
-        else:
-            filt = ops.filter_forward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, fm0, fsig0,
-                                      obs_TB, eps, u, idx_in)
-        ctx.desc, ctx.filt = desc, _aliases(filt)
-        ctx.saved = (q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, fm0, fsig0, obs_TB, eps)
+        # (desc._ov: shared with the BsimFunction of the same evaluation)
+        filt = _filter_forward(ctx, ops.filter_forward, desc, obs_TB, eps, u, idx_in, t, ov=getattr(desc, "_ov", None))
         ctx.mark_non_differentiable(filt["X"], filt["Xanc"], filt["idx"])
         return filt["lse"], filt["Fm"], filt["logW"], filt["X"], filt["Xanc"], filt["idx"]
 
@@ -192,13 +232,12 @@ class FilterFunction(torch.autograd.Function):
         runs the encoder's reverse pass before this node (it was created earlier in the forward pass), and in a replayed
         hipGraph the reverse filter kernel then started ~75 us after its inputs existed, behind those launches."""
         desc = ctx.desc
-        q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, fm0, fsig0, obs_TB, eps = ctx.saved
+        q1, f, g, rest, obs_TB, eps = ctx.saved
         ov = desc._ov
         ov.side.wait_event(ov.bsim_grads_ready)
         with ops.launch_on(ov.side):
-            r = ops.filter_backward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, fm0, fsig0,
-                                    obs_TB, eps, ctx.filt, dlse=_cg(dlse), dFm=_cg(dFm), dlogW=_cg(dlogW),
-                                    gbufs=ctx.gbufs, defer_wgrad=True)
+            r = ops.filter_backward(desc, q1, f, g, *rest, obs_TB, eps, ctx.filt, dlse=_cg(dlse), dFm=_cg(dFm),
+                                    dlogW=_cg(dlogW), gbufs=ctx.gbufs, defer_wgrad=True)
         kernel_done = torch.cuda.Event()
         kernel_done.record(ov.side)              # the reverse kernel's own outputs (d mu2, d m0, scale sums) exist
         return {"r": r, "kernel_done": kernel_done, "grads": (dlse, dFm, dlogW)}
@@ -206,7 +245,6 @@ class FilterFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dlse, dFm, dlogW, *_):
         desc = ctx.desc
-        q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, fm0, fsig0, obs_TB, eps = ctx.saved
         ov = getattr(desc, "_ov", None)
         side = None if ov is None else ov.side
         ready = None if ov is None else ov.bsim_grads_ready
@@ -263,21 +301,9 @@ class FilterFunction(torch.autograd.Function):
                     main.wait_event(ov.bsim_wgrad_done)
             _used_on(main, r.values())
         else:
-            r = ops.filter_backward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, fm0, fsig0,
-                                    obs_TB, eps, ctx.filt, dlse=_cg(dlse), dFm=_cg(dFm), dlogW=_cg(dlogW),
-                                    gbufs=ctx.gbufs)
-        Dx, Dy, H = desc.Dx, desc.Dy, desc.H
-        gfirst, gextra = _mlp_grads(r, ("gq1", None if desc.bootstrap else "gf", "gg"), ((Dx, Dx), (Dx, Dx), (Dx, Dy)), H,
-                                    2 if desc.layers == 2 else 1, ctx.gbufs or (None, None, None))
-        two_q, boot = bool(desc.two_q), bool(desc.bootstrap)
-        # (one tensor passed as both m0 and fm0 -- the default wiring -- gets the summed gradient in d m0 from the kernel:
-        #  returning the zero d fm0 as well would only make the engine launch an add; likewise sig0 / fsig0)
-        same_m = m0.data_ptr() == fm0.data_ptr()
-        same_s = sig0.data_ptr() == fsig0.data_ptr()
-        return (None, None, None, None, None) + gfirst + (
-            r["dsig_q1"], r["dsig_q2"] if two_q else None, None if boot else r["dsig_f"], r["dsig_g"],
-            r["dmu2"] if two_q else None, r["dm0"], r["dsig0"], None if same_m else r["dfm0"],
-            None if same_s else r["dfsig0"]) + gextra
+            return _filter_backward(ctx, ops.filter_backward, 5, dlse, dFm, dlogW, gbufs=ctx.gbufs)
+        rest = ctx.saved[3]                         # (.. m0, sig0, fm0, fsig0)
+        return (None,) * 5 + _filter_grads(r, desc, *rest[5:9], ctx.gbufs)
 
 
 class FilterCovFunction(torch.autograd.Function):
@@ -330,35 +356,13 @@ class FilterWobsFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, desc, obs_TB, eps, u, idx_in, *t):
-        ctx.set_materialize_grads(False)
-        t = [_cf(v) for v in t]
-        q1, f, g = _mlps(t)
-        rest = t[12:21]                 # sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, fm0, fsig0
-        if desc.bootstrap:
-            f = None
-        filt = ops.filter_forward_wobs(desc, q1, f, g, *rest, obs_TB, eps, u, idx_in)
-        ctx.desc, ctx.filt = desc, _aliases(filt)
-        ctx.saved = (q1, f, g, rest, obs_TB, eps)
+        filt = _filter_forward(ctx, ops.filter_forward_wobs, desc, obs_TB, eps, u, idx_in, t)
         ctx.mark_non_differentiable(filt["X"], filt["Xanc"], filt["idx"])
         return filt["lse"], filt["Fm"], filt["logW"], filt["X"], filt["Xanc"], filt["idx"]
 
     @staticmethod
     def backward(ctx, dlse, dFm, dlogW, *_):
-        desc = ctx.desc
-        q1, f, g, rest, obs_TB, eps = ctx.saved
-        r = ops.filter_backward_wobs(desc, q1, f, g, *rest, obs_TB, eps, ctx.filt, dlse=_cg(dlse), dFm=_cg(dFm),
-                                     dlogW=_cg(dlogW))
-        Dx, Dy, H = desc.Dx, desc.Dy, desc.H
-        two_q, boot = bool(desc.two_q), bool(desc.bootstrap)
-        gfirst, _ = _mlp_grads(r, ("gq1", None if boot else "gf", "gg"), ((Dx, Dx), (Dx, Dx), (Dx, Dy)), H, 1,
-                               (None, None, None))
-        m0, sig0, fm0, fsig0 = rest[5:9]
-        same_m = m0.data_ptr() == fm0.data_ptr()       # (one tensor as both: the kernel put the sum into d m0)
-        same_s = sig0.data_ptr() == fsig0.data_ptr()
-        return (None, None, None, None, None) + gfirst + (
-            r["dsig_q1"], r["dsig_q2"] if two_q else None, None if boot else r["dsig_f"], r["dsig_g"],
-            r["dmu2"] if two_q else None, r["dm0"], r["dsig0"], None if same_m else r["dfm0"],
-            None if same_s else r["dfsig0"])
+        return _filter_backward(ctx, ops.filter_backward_wobs, 5, dlse, dFm, dlogW)
 
 
 class FilterAdaptiveFunction(torch.autograd.Function):
@@ -373,35 +377,12 @@ class FilterAdaptiveFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, desc, obs_TB, eps, u, idx_in, ess_frac, rs_in, *t):
-        ctx.set_materialize_grads(False)
-        t = [_cf(v) for v in t]
-        q1, f, g = _mlps(t)
-        rest = t[12:21]                 # sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, fm0, fsig0
-        if desc.bootstrap:
-            f = None
-        filt = ops.filter_forward(desc, q1, f, g, *rest, obs_TB, eps, u, idx_in, ess_frac=ess_frac, rs_in=rs_in)
-        ctx.desc, ctx.filt = desc, _aliases(filt)
-        ctx.saved = (q1, f, g, rest, obs_TB, eps)
-        const = (filt["Fm"], filt["logW"], filt["X"], filt["Xanc"], filt["idx"], filt["rs"], filt["ess"])
-        ctx.mark_non_differentiable(*const)
-        return (filt["lse"],) + const
+        filt = _filter_forward(ctx, ops.filter_forward, desc, obs_TB, eps, u, idx_in, t, ess_frac=ess_frac, rs_in=rs_in)
+        return _adaptive_outputs(ctx, filt)
 
     @staticmethod
     def backward(ctx, dlse, *_):
-        desc = ctx.desc
-        q1, f, g, rest, obs_TB, eps = ctx.saved
-        r = ops.filter_backward(desc, q1, f, g, *rest, obs_TB, eps, ctx.filt, dlse=_cg(dlse), adaptive=True)
-        Dx, Dy, H = desc.Dx, desc.Dy, desc.H
-        two_q, boot = bool(desc.two_q), bool(desc.bootstrap)
-        gfirst, gextra = _mlp_grads(r, ("gq1", None if boot else "gf", "gg"), ((Dx, Dx), (Dx, Dx), (Dx, Dy)), H,
-                                    2 if desc.layers == 2 else 1, (None, None, None))
-        m0, sig0, fm0, fsig0 = rest[5:9]
-        same_m = m0.data_ptr() == fm0.data_ptr()       # (one tensor as both: the kernel put the sum into d m0)
-        same_s = sig0.data_ptr() == fsig0.data_ptr()
-        return (None,) * 7 + gfirst + (
-            r["dsig_q1"], r["dsig_q2"] if two_q else None, None if boot else r["dsig_f"], r["dsig_g"],
-            r["dmu2"] if two_q else None, r["dm0"], r["dsig0"], None if same_m else r["dfm0"],
-            None if same_s else r["dfsig0"]) + gextra
+        return _filter_backward(ctx, ops.filter_backward, 7, dlse, adaptive=True)
 
 
 class FilterWobsAdaptiveFunction(torch.autograd.Function):
@@ -414,35 +395,13 @@ class FilterWobsAdaptiveFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, desc, obs_TB, eps, u, idx_in, ess_frac, rs_in, *t):
-        ctx.set_materialize_grads(False)
-        t = [_cf(v) for v in t]
-        q1, f, g = _mlps(t)
-        rest = t[12:21]                 # sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, fm0, fsig0
-        if desc.bootstrap:
-            f = None
-        filt = ops.filter_forward_wobs_adaptive(desc, q1, f, g, *rest, obs_TB, eps, u, idx_in, ess_frac=ess_frac, rs_in=rs_in)
-        ctx.desc, ctx.filt = desc, _aliases(filt)
-        ctx.saved = (q1, f, g, rest, obs_TB, eps)
-        const = (filt["Fm"], filt["logW"], filt["X"], filt["Xanc"], filt["idx"], filt["rs"], filt["ess"])
-        ctx.mark_non_differentiable(*const)
-        return (filt["lse"],) + const
+        filt = _filter_forward(ctx, ops.filter_forward_wobs_adaptive, desc, obs_TB, eps, u, idx_in, t, ess_frac=ess_frac,
+                               rs_in=rs_in)
+        return _adaptive_outputs(ctx, filt)
 
     @staticmethod
     def backward(ctx, dlse, *_):
-        desc = ctx.desc
-        q1, f, g, rest, obs_TB, eps = ctx.saved
-        r = ops.filter_backward_wobs_adaptive(desc, q1, f, g, *rest, obs_TB, eps, ctx.filt, dlse=_cg(dlse))
-        Dx, Dy, H = desc.Dx, desc.Dy, desc.H
-        two_q, boot = bool(desc.two_q), bool(desc.bootstrap)
-        gfirst, _ = _mlp_grads(r, ("gq1", None if boot else "gf", "gg"), ((Dx, Dx), (Dx, Dx), (Dx, Dy)), H, 1,
-                               (None, None, None))
-        m0, sig0, fm0, fsig0 = rest[5:9]
-        same_m = m0.data_ptr() == fm0.data_ptr()       # (one tensor as both: the kernel put the sum into d m0)
-        same_s = sig0.data_ptr() == fsig0.data_ptr()
-        return (None,) * 7 + gfirst + (
-            r["dsig_q1"], r["dsig_q2"] if two_q else None, None if boot else r["dsig_f"], r["dsig_g"],
-            r["dmu2"] if two_q else None, r["dm0"], r["dsig0"], None if same_m else r["dfm0"],
-            None if same_s else r["dfsig0"])
+        return _filter_backward(ctx, ops.filter_backward_wobs_adaptive, 7, dlse)
 
 
 def _filter_node_of(Fm, ov):
@@ -453,6 +412,58 @@ def _filter_node_of(Fm, ov):
     if ov is None or node is None or getattr(node, "desc", None) is None or getattr(node.desc, "_ov", None) is not ov:
         return None
     return node if hasattr(node, "filt") and hasattr(node, "saved") else None
+
+
+def _bsim_forward(ctx, op, desc, obs_TB, eps_b, Fm, logW, lse, t, **draws):
+    """a backward-simulation node's forward (state-independent scales): op (ops.bsim_forward / bsim_forward_wobs /
+    bsimwr_forward) on the filter's outputs and the node's positional tensors `t`, after the filter where that ran on the side
+    stream; keeps on ctx what the reverse pass needs and returns op's dict"""
+    t = [_cf(v) for v in t]
+    f, g, q = _mlps(t)
+    rest = t[12:21]                 # sig_f, sig_g, sig_q1inv, sig_bq2, bmu2, minit, sig_init, imean, isig
+    filt = {"Fm": _cf(Fm), "logW": _cf(logW), "lse": _cf(lse)}
+    ov = getattr(desc, "_ov", None)
+    if ov is not None and ov.filter_done is not None:     # the filter ran on the side stream
+        torch.cuda.current_stream().wait_event(ov.filter_done)
+    ctx.filter_node = _filter_node_of(Fm, ov)
+    ctx.gbufs = getattr(desc, "_gbufs", None)             # (f, g, q1_inv) flat-gradient slices or None
+    bs = op(desc, {**filt, "X": filt["Fm"]}, f, g, q, *rest, obs_TB, eps_b, save=any(ctx.needs_input_grad), **draws)
+    ctx.desc, ctx.filt, ctx.bs = desc, filt, _aliases(bs)
+    ctx.saved = (f, g, q, rest, obs_TB, eps_b)
+    ctx.set_materialize_grads(False)      # (else the engine zero-fills a gradient for each of the node's constants)
+    return bs
+
+
+def _or_zeros(ctx, dout, *shape):
+    """the upstream gradient of a node's one differentiable output; zeros when the loss does not use it (None)"""
+    return torch.zeros(*shape, device=ctx.filt["Fm"].device) if dout is None else dout
+
+
+def _prelaunch_filter(ctx, ov, iFm):
+    """the after_kernel callback of the overlap backward-simulation nodes: d Fm / d logW exist, the filter's reverse pass (side
+    stream) may start.  iFm: the position of Fm among the node's inputs (logW follows it)."""
+    def after_kernel(out):
+        if ov is not None:
+            ov.bsim_grads_ready = torch.cuda.Event()
+            ov.bsim_grads_ready.record()
+            if PRELAUNCH and ctx.filter_node is not None and (ctx.needs_input_grad[iFm] or ctx.needs_input_grad[iFm + 1]):
+                # (d lse = -sum_n d logW: zero analytically, rounding-sized numerically, passed on as autodiff of the
+                #  reference's graph would -- ops.bsim_backward / bsim_bwd_fold_finalize)
+                ov.pre = FilterFunction.launch_reverse_kernel(ctx.filter_node, out["dlse"], out["dFm"], out["dlogW"])
+    return after_kernel
+
+
+def _bsim_node_grads(ctx, r, lead):
+    """a backward-simulation node's gradients from the reverse wrapper's dict `r`: None for the `lead` non-tensor inputs, then
+    Fm, logW, lse, the twelve MLP tensors, sig_f .. isig and -- two hidden layers -- the (Wh, bh) extras"""
+    desc = ctx.desc
+    Dx, Dy, H = desc.Dx, desc.Dy, desc.H
+    gfirst, gextra = _mlp_grads(r, ("gf", "gg", "gq1inv"), ((Dx, Dx), (Dx, Dy), (Dx, Dx)), H,
+                                2 if desc.layers == 2 else 1, ctx.gbufs or (None, None, None))
+    ops.sum_chain_rows(r, desc.T, desc.B, Dx)       # (one reduction for d bmu2 / d minit / d imean)
+    return (None,) * lead + (r["dFm"], r["dlogW"], r["dlse"] if ctx.needs_input_grad[lead + 2] else None) + gfirst + (
+        r["dsig_f"], r["dsig_g"], r["dsig_q1inv"], r["dsig_bq2"], r["dbmu2"],
+        r["dminit"], r["dsig_init"], r["dimean"], r["disig"]) + gextra
 
 
 class BsimFunction(torch.autograd.Function):
@@ -466,46 +477,21 @@ class BsimFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, desc, obs_TB, eps_b, u_b, sel_in, Fm, logW, lse, *t):
-        t = [_cf(v) for v in t]
-        f, g, q = _mlps(t)
-        sig_f, sig_g, sig_q1inv, sig_bq2, bmu2, minit, sig_init, imean, isig = t[12:21]
-        filt = {"X": None, "Fm": _cf(Fm), "logW": _cf(logW), "lse": _cf(lse)}
-        ov = getattr(desc, "_ov", None)
-        if ov is not None and ov.filter_done is not None:     # the filter ran on the side stream
-            torch.cuda.current_stream().wait_event(ov.filter_done)
-        ctx.filter_node = _filter_node_of(Fm, ov)
-        ctx.gbufs = getattr(desc, "_gbufs", None)             # (f, g, q1_inv) flat-gradient slices or None
-        need = any(ctx.needs_input_grad)
-        bs = ops.bsim_forward(desc, {**filt, "X": filt["Fm"]}, f, g, q, sig_f, sig_g, sig_q1inv, sig_bq2, bmu2, minit,
-                              sig_init, imean, isig, obs_TB, eps_b, u_b, sel_in, save=need)
-        ctx.desc, ctx.filt, ctx.bs = desc, filt, _aliases(bs)
-        ctx.saved = (f, g, q, sig_f, sig_g, sig_q1inv, sig_bq2, bmu2, minit, sig_init, imean, isig, obs_TB, eps_b)
+        bs = _bsim_forward(ctx, ops.bsim_forward, desc, obs_TB, eps_b, Fm, logW, lse, t, u_b=u_b, sel_in=sel_in)
         ctx.mark_non_differentiable(bs["bwX"], bs["flp"], bs["glp"], bs["Omega"], bs["sel"])
-        ctx.set_materialize_grads(False)      # (else the engine zero-fills a gradient for each of the five constants)
         return bs["score"], bs["bwX"], bs["flp"], bs["glp"], bs["Omega"], bs["sel"]
 
     @staticmethod
     def backward(ctx, dscore, *_):
         desc = ctx.desc
-        if dscore is None:                    # (score unused by the loss)
-            dscore = torch.zeros(desc.B, desc.N, device=ctx.filt["Fm"].device)
-        f, g, q, sig_f, sig_g, sig_q1inv, sig_bq2, bmu2, minit, sig_init, imean, isig, obs_TB, eps_b = ctx.saved
+        dscore = _or_zeros(ctx, dscore, desc.B, desc.N)
+        f, g, q, rest, obs_TB, eps_b = ctx.saved
         ov = getattr(desc, "_ov", None)
-
-        def after_kernel(out):   # d Fm / d logW exist: the filter's reverse pass (side stream) may start
-            if ov is not None:
-                ov.bsim_grads_ready = torch.cuda.Event()
-                ov.bsim_grads_ready.record()
-                if PRELAUNCH and ctx.filter_node is not None and (ctx.needs_input_grad[5] or ctx.needs_input_grad[6]):
-                    # (d lse = -sum_n d logW: zero analytically, rounding-sized numerically, passed on as autodiff of the
-                    #  reference's graph would -- ops.bsim_backward / bsim_bwd_fold_finalize)
-                    ov.pre = FilterFunction.launch_reverse_kernel(ctx.filter_node, out["dlse"], out["dFm"], out["dlogW"])
         ws = None if (ov is None or ctx.gbufs is None) else ov.side2
         defer = (DEFER_BSIM_WGRAD and DEFER_JOIN and PRELAUNCH and ws is not None and ctx.filter_node is not None
                  and (ctx.needs_input_grad[5] or ctx.needs_input_grad[6]))
-        r = ops.bsim_backward(desc, ctx.filt, f, g, q, sig_f, sig_g, sig_q1inv, sig_bq2, bmu2, minit, sig_init,
-                              imean, isig, obs_TB, eps_b, ctx.bs, _cg(dscore), gbufs=ctx.gbufs,
-                              after_kernel=after_kernel, wgrad_stream=ws, defer_wgrad=defer)
+        r = ops.bsim_backward(desc, ctx.filt, f, g, q, *rest, obs_TB, eps_b, ctx.bs, _cg(dscore), gbufs=ctx.gbufs,
+                              after_kernel=_prelaunch_filter(ctx, ov, 5), wgrad_stream=ws, defer_wgrad=defer)
         if defer:
             ready, issue_wgrad = ov.bsim_grads_ready, r.pop("_wgrad")
 
@@ -520,14 +506,7 @@ class BsimFunction(torch.autograd.Function):
         elif ov is not None:
             ov.bsim_wgrad_done = torch.cuda.Event()
             ov.bsim_wgrad_done.record(ws if ws is not None else torch.cuda.current_stream())
-        Dx, Dy, H = desc.Dx, desc.Dy, desc.H
-        gfirst, gextra = _mlp_grads(r, ("gf", "gg", "gq1inv"), ((Dx, Dx), (Dx, Dy), (Dx, Dx)), H,
-                                    2 if desc.layers == 2 else 1, ctx.gbufs or (None, None, None))
-        dFm, dlogW = r["dFm"], r["dlogW"]
-        ops.sum_chain_rows(r, desc.T, desc.B, Dx)       # (one reduction for d bmu2 / d minit / d imean)
-        return (None, None, None, None, None, dFm, dlogW, r["dlse"] if ctx.needs_input_grad[7] else None) + gfirst + (
-            r["dsig_f"], r["dsig_g"], r["dsig_q1inv"], r["dsig_bq2"], r["dbmu2"],
-            r["dminit"], r["dsig_init"], r["dimean"], r["disig"]) + gextra
+        return _bsim_node_grads(ctx, r, 5)
 
 
 class BsimWobsFunction(torch.autograd.Function):
@@ -539,31 +518,18 @@ class BsimWobsFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, desc, obs_TB, eps_b, u_b, sel_in, Fm, logW, lse, *t):
-        t = [_cf(v) for v in t]
-        f, g, q = _mlps(t)
-        rest = t[12:21]                 # sig_f, sig_g, sig_q1inv, sig_bq2, bmu2, minit, sig_init, imean, isig
-        filt = {"X": None, "Fm": _cf(Fm), "logW": _cf(logW), "lse": _cf(lse)}
-        bs = ops.bsim_forward_wobs(desc, {**filt, "X": filt["Fm"]}, f, g, q, *rest, obs_TB, eps_b, u_b, sel_in,
-                                   save=any(ctx.needs_input_grad))
-        ctx.desc, ctx.filt, ctx.bs = desc, filt, _aliases(bs)
-        ctx.saved = (f, g, q, rest, obs_TB, eps_b)
+        bs = _bsim_forward(ctx, ops.bsim_forward_wobs, desc, obs_TB, eps_b, Fm, logW, lse, t, u_b=u_b, sel_in=sel_in)
+        ctx.gbufs = None                      # (this route returns every gradient as a tensor)
         ctx.mark_non_differentiable(bs["bwX"], bs["flp"], bs["glp"], bs["Omega"], bs["sel"])
-        ctx.set_materialize_grads(False)
         return bs["score"], bs["bwX"], bs["flp"], bs["glp"], bs["Omega"], bs["sel"]
 
     @staticmethod
     def backward(ctx, dscore, *_):
         desc = ctx.desc
-        if dscore is None:                    # (score unused by the loss)
-            dscore = torch.zeros(desc.B, desc.N, device=ctx.filt["Fm"].device)
         f, g, q, rest, obs_TB, eps_b = ctx.saved
-        r = ops.bsim_backward_wobs(desc, ctx.filt, f, g, q, *rest, obs_TB, eps_b, ctx.bs, _cg(dscore).float())
-        Dx, Dy, H = desc.Dx, desc.Dy, desc.H
-        gfirst, _ = _mlp_grads(r, ("gf", "gg", "gq1inv"), ((Dx, Dx), (Dx, Dy), (Dx, Dx)), H, 1, (None, None, None))
-        ops.sum_chain_rows(r, desc.T, desc.B, Dx)
-        return (None, None, None, None, None, r["dFm"], r["dlogW"], r["dlse"] if ctx.needs_input_grad[7] else None) + gfirst + (
-            r["dsig_f"], r["dsig_g"], r["dsig_q1inv"], r["dsig_bq2"], r["dbmu2"],
-            r["dminit"], r["dsig_init"], r["dimean"], r["disig"])
+        dscore = _cg(_or_zeros(ctx, dscore, desc.B, desc.N)).float()
+        r = ops.bsim_backward_wobs(desc, ctx.filt, f, g, q, *rest, obs_TB, eps_b, ctx.bs, dscore)
+        return _bsim_node_grads(ctx, r, 5)
 
 
 def _bsim_cov_forward(ctx, op, desc, obs_TB, eps_b, Fm, Fs, logW, lse, t, **draws):
@@ -648,54 +614,27 @@ class BsimWRFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, desc, obs_TB, eps_b, u_b, u_r, sel_in, anc_in, Fm, logW, lse, *t):
-        t = [_cf(v) for v in t]
-        f, g, q = _mlps(t)
-        sig_f, sig_g, sig_q1inv, sig_bq2, bmu2, minit, sig_init, imean, isig = t[12:21]
-        filt = {"Fm": _cf(Fm), "logW": _cf(logW), "lse": _cf(lse)}
-        ov = getattr(desc, "_ov", None)
-        if ov is not None and ov.filter_done is not None:
-            torch.cuda.current_stream().wait_event(ov.filter_done)
-        ctx.filter_node = _filter_node_of(Fm, ov)
-        ctx.gbufs = getattr(desc, "_gbufs", None)
-        need = any(ctx.needs_input_grad)
-        bs = ops.bsimwr_forward(desc, filt, f, g, q, sig_f, sig_g, sig_q1inv, sig_bq2, bmu2, minit, sig_init, imean,
-                                isig, obs_TB, eps_b, u_b=u_b, u_r=u_r, sel_in=sel_in, anc_in=anc_in, save=need)
-        ctx.desc, ctx.filt, ctx.bs = desc, filt, _aliases(bs)
+        bs = _bsim_forward(ctx, ops.bsimwr_forward, desc, obs_TB, eps_b, Fm, logW, lse, t, u_b=u_b, u_r=u_r, sel_in=sel_in,
+                           anc_in=anc_in)
         _note_exchange(desc, bs["ws"], 1)
-        ctx.saved = (f, g, q, sig_f, sig_g, sig_q1inv, sig_bq2, bmu2, minit, sig_init, imean, isig, obs_TB, eps_b)
         ctx.mark_non_differentiable(bs["bwXanc"], bs["bwX"], bs["bwW"], bs["sel"], bs["anc"], bs["ws"])
-        ctx.set_materialize_grads(False)      # (else the engine zero-fills a gradient for each of the six constants)
         return bs["lseW"], bs["bwXanc"], bs["bwX"], bs["bwW"], bs["sel"], bs["anc"], bs["ws"]
 
     @staticmethod
     def backward(ctx, dlseW, *_):
         desc = ctx.desc
-        if dlseW is None:                     # (lseW unused by the loss)
-            dlseW = torch.zeros(desc.T, desc.B, device=ctx.filt["Fm"].device)
-        f, g, q, sig_f, sig_g, sig_q1inv, sig_bq2, bmu2, minit, sig_init, imean, isig, obs_TB, eps_b = ctx.saved
+        dlseW = _or_zeros(ctx, dlseW, desc.T, desc.B)
+        f, g, q, rest, obs_TB, eps_b = ctx.saved
         ov = getattr(desc, "_ov", None)
-
-        def after_kernel(out):
-            if ov is not None:
-                ov.bsim_grads_ready = torch.cuda.Event()
-                ov.bsim_grads_ready.record()
-                if PRELAUNCH and ctx.filter_node is not None and (ctx.needs_input_grad[7] or ctx.needs_input_grad[8]):
-                    ov.pre = FilterFunction.launch_reverse_kernel(ctx.filter_node, out["dlse"], out["dFm"], out["dlogW"])
         ws = None if (ov is None or ctx.gbufs is None) else ov.side2
-        r = ops.bsimwr_backward(desc, ctx.filt, f, g, q, sig_f, sig_g, sig_q1inv, sig_bq2, bmu2, minit, sig_init,
-                                imean, isig, obs_TB, eps_b, ctx.bs, _cg(dlseW), gbufs=ctx.gbufs,
-                                after_kernel=after_kernel, wgrad_stream=ws)
+        r = ops.bsimwr_backward(desc, ctx.filt, f, g, q, *rest, obs_TB, eps_b, ctx.bs, _cg(dlseW), gbufs=ctx.gbufs,
+                                after_kernel=_prelaunch_filter(ctx, ov, 7), wgrad_stream=ws)
         if ov is not None:
             ov.bsim_wgrad_done = torch.cuda.Event()
             ov.bsim_wgrad_done.record(ws if ws is not None else torch.cuda.current_stream())
-        Dx, Dy, H = desc.Dx, desc.Dy, desc.H
-        gfirst, gextra = _mlp_grads(r, ("gf", "gg", "gq1inv"), ((Dx, Dx), (Dx, Dy), (Dx, Dx)), H,
-                                    2 if desc.layers == 2 else 1, ctx.gbufs or (None, None, None))
-        ops.sum_chain_rows(r, desc.T, desc.B, Dx)
+        grads = _bsim_node_grads(ctx, r, 7)
         _note_exchange(desc, r["ws"], 2)          # (after the weight-gradient launches: see ops.sum_chain_rows)
-        return (None,) * 7 + (r["dFm"], r["dlogW"], r["dlse"]) + gfirst + (
-            r["dsig_f"], r["dsig_g"], r["dsig_q1inv"], r["dsig_bq2"], r["dbmu2"],
-            r["dminit"], r["dsig_init"], r["dimean"], r["disig"]) + gextra
+        return grads
 
 
 class RowsMLPFunction(torch.autograd.Function):

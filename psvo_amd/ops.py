@@ -193,6 +193,14 @@ def _mark(name, phase):
         _HOOK(name, phase, _cur_stream())
 
 
+def _launch(name, fn, *args):
+    """one native launch: the hook's marks around it, its status checked under `name`"""
+    _mark(name, 0)
+    st = fn(*args)
+    _mark(name, 1)
+    _lib.check(st, name)
+
+
 # the entry points that take ess_frac / rs_in, by the `entry` they are asked for under (filter_forward_wobs with ess_frac stays a
 # refusal: the wide adaptive route is filter_forward_wobs_adaptive)
 _ADAPTIVE_ENTRY = {"psvo_filter_forward": "psvo_filter_forward_adaptive",
@@ -238,15 +246,13 @@ def filter_forward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, 
     if ess_frac is not None:
         out["rs"], out["ess"] = _empty(T, B, device=dev, dtype=torch.int32), _empty(T, B, device=dev)
         adaptive = (ctypes.c_float(float(ess_frac)), _ptr(rs_in), _ptr(out["rs"]), _ptr(out["ess"]))
-    _mark(entry, 0)
-    st = getattr(lib, entry)(
+    _launch(
+        entry, getattr(lib, entry),
         ctypes.byref(desc), ctypes.byref(q1s), ctypes.byref(fs) if fs is not None else None, ctypes.byref(gs),
         _ptr(sig_q1), _ptr(sig_q2), _ptr(sig_f), _ptr(sig_g), _ptr(mu2), _ptr(m0), _ptr(sig0), _ptr(fm0),
         _ptr(fsig0), _ptr(obs), _ptr(eps), _ptr(u), _ptr(idx_in),
         _ptr(out["X"]), _ptr(out["Xanc"]), _ptr(out["Fm"]), _ptr(out["P1"]), _ptr(out["logW"]), _ptr(out["idx"]),
         _ptr(out["lse"]), *adaptive, _stream())
-    _mark(entry, 1)
-    _lib.check(st, entry)
     return out
 
 
@@ -296,12 +302,13 @@ def _bsim_chk_saves(desc, bs, fn, own):
 
 
 def _bsim_grads(desc, dev, nparts, own):
-    """the outputs of both reverse launches, in allocation order: the rows for psvo_mlp_wgrad, the per-workgroup partials (nparts
-    per sequence), the caller's `own` ((key, shape), ...), the scale gradients"""
+    """the outputs of the reverse launches, in allocation order: the rows for psvo_mlp_wgrad, the per-workgroup partials (nparts
+    per sequence; 0: none, the entry point folds them itself), the caller's `own` ((key, shape), ...), the scale gradients"""
     B, T, N, M, Dx, Dy = desc.B, desc.T, desc.N, desc.M, desc.Dx, desc.Dy
     z = lambda *s: _empty(*s, device=dev)
-    out = {"xt": z(T, B, Dx, N, M), "dFt": z(T, B, Dx, N, M), "dGt": z(T, B, Dy, N, M), "dmu1": z(T, B, Dx, N),
-           "dFm_part": z(T, B, nparts, Dx, N), "dlogW_part": z(T, B, nparts, N)}
+    out = {"xt": z(T, B, Dx, N, M), "dFt": z(T, B, Dx, N, M), "dGt": z(T, B, Dy, N, M), "dmu1": z(T, B, Dx, N)}
+    if nparts:
+        out.update({"dFm_part": z(T, B, nparts, Dx, N), "dlogW_part": z(T, B, nparts, N)})
     out.update((k, z(*shp)) for k, shp in own)
     out.update({"dsig_f": z(Dx), "dsig_g": z(Dy), "dsig_q1inv": z(Dx), "dsig_bq2": z(Dx), "dsig_init": z(Dx), "disig": z(Dx)})
     return out
@@ -330,16 +337,14 @@ def bsim_forward(desc, filt, f, g, q1_inv, sig_f, sig_g, sig_q1inv, sig_bq2, bmu
     z = lambda *s: _empty(*s, device=dev)
     out = {"bwX": z(T, B, Dx, N), "flp": z(T, B, N), "glp": z(T, B, N), "Omega": z(T, B, N),
            "sel": _empty(T, B, N, device=dev, dtype=torch.int32), "score": z(B, N), **_bsim_saves(desc, dev, save)}
-    _mark(entry, 0)
-    st = getattr(lib, entry)(
+    _launch(
+        entry, getattr(lib, entry),
         ctypes.byref(desc), _ptr(filt["X"]), _ptr(filt["Fm"]), _ptr(filt["logW"]), _ptr(filt["lse"]),
         ctypes.byref(fs), ctypes.byref(gs), ctypes.byref(qs),
         _ptr(sig_f), _ptr(sig_g), _ptr(sig_q1inv), _ptr(sig_bq2), _ptr(bmu2), _ptr(minit), _ptr(sig_init),
         _ptr(imean), _ptr(isig), _ptr(obs), _ptr(eps_b), _ptr(u_b), _ptr(sel_in),
         _ptr(out["bwX"]), _ptr(out["flp"]), _ptr(out["glp"]), _ptr(out["Omega"]), _ptr(out["sel"]),
         _ptr(out["score"]), _ptr(out["lam2"]), _ptr(out["om"]), _ptr(out["mu1"]), _stream())
-    _mark(entry, 1)
-    _lib.check(st, entry)
     return out
 
 
@@ -396,11 +401,8 @@ def bilstm_forward(x, W_fw, b_fw, W_bw, b_bw, save=False):
     out = _empty(B, T, 2 * Dh, device=x.device)
     cs = _empty(2, B, T, Dh, device=x.device) if save else None
     gates = _empty(2, B, T, 4 * Dh, device=x.device) if save else None
-    _mark("psvo_bilstm_forward", 0)
-    st = lib.psvo_bilstm_forward(B, T, Din, Dh, _ptr(x), _ptr(W_fw), _ptr(b_fw), _ptr(W_bw), _ptr(b_bw),
-                                 _ptr(out), _ptr(cs), _ptr(gates), _stream())
-    _mark("psvo_bilstm_forward", 1)
-    _lib.check(st, "psvo_bilstm_forward")
+    _launch("psvo_bilstm_forward", lib.psvo_bilstm_forward, B, T, Din, Dh, _ptr(x), _ptr(W_fw), _ptr(b_fw), _ptr(W_bw),
+            _ptr(b_bw), _ptr(out), _ptr(cs), _ptr(gates), _stream())
     return (out, cs, gates) if save else out
 
 
@@ -436,11 +438,8 @@ def mlp_wgrad(X, dOut, w, Din, H, Dout, grad=None, axis=2, wobs=False):
         grad = _empty(NP, device=dev)
     elif grad.numel() != NP:
         raise ValueError("mlp_wgrad: gradient slice of %d floats for an MLP of %d parameters" % (grad.numel(), NP))
-    _mark(name, 0)
-    st = getattr(lib, name)(S, L, Din, H, Dout, _ptr(X), _ptr(dOut), ctypes.byref(ws), _ptr(partial), _ptr(grad),
-                            int(acc), _stream())
-    _mark(name, 1)
-    _lib.check(st, name)
+    _launch(name, getattr(lib, name), S, L, Din, H, Dout, _ptr(X), _ptr(dOut), ctypes.byref(ws), _ptr(partial), _ptr(grad),
+            int(acc), _stream())
     return grad
 
 
@@ -457,10 +456,7 @@ def rows_mlp_forward(X, w):
     _chk(X, (R, Din), "X")
     ws = _mlp_struct(w, Din, H, Dout, "w")
     out = _empty(R, Dout, device=X.device)
-    _mark("psvo_rows_mlp_forward", 0)
-    st = lib.psvo_rows_mlp_forward(R, Din, H, Dout, _ptr(X), ctypes.byref(ws), _ptr(out), _stream())
-    _mark("psvo_rows_mlp_forward", 1)
-    _lib.check(st, "psvo_rows_mlp_forward")
+    _launch("psvo_rows_mlp_forward", lib.psvo_rows_mlp_forward, R, Din, H, Dout, _ptr(X), ctypes.byref(ws), _ptr(out), _stream())
     return out
 
 
@@ -477,11 +473,8 @@ def rows_mlp_backward(X, dOut, w, need_dX=True, grad=None):
     acc = grad is not None
     if grad is None:
         grad = _empty(NP, device=X.device)
-    _mark("psvo_rows_mlp_backward", 0)
-    st = lib.psvo_rows_mlp_backward(R, Din, H, Dout, _ptr(X), _ptr(dOut), ctypes.byref(ws), _ptr(dX), _ptr(partial),
-                                    _ptr(grad), int(acc), _stream())
-    _mark("psvo_rows_mlp_backward", 1)
-    _lib.check(st, "psvo_rows_mlp_backward")
+    _launch("psvo_rows_mlp_backward", lib.psvo_rows_mlp_backward, R, Din, H, Dout, _ptr(X), _ptr(dOut), ctypes.byref(ws),
+            _ptr(dX), _ptr(partial), _ptr(grad), int(acc), _stream())
     return dX, grad
 
 
@@ -492,10 +485,7 @@ def dense_forward(X, W, b, relu):
     Dout = W.shape[1]
     _chk(X, (R, Din), "X"); _chk(W, (Din, Dout), "W"); _chk(b, (Dout,), "b")
     Y = _empty(R, Dout, device=X.device)
-    _mark("psvo_dense_forward", 0)
-    st = lib.psvo_dense_forward(R, Din, Dout, _ptr(X), _ptr(W), _ptr(b), int(relu), _ptr(Y), _stream())
-    _mark("psvo_dense_forward", 1)
-    _lib.check(st, "psvo_dense_forward")
+    _launch("psvo_dense_forward", lib.psvo_dense_forward, R, Din, Dout, _ptr(X), _ptr(W), _ptr(b), int(relu), _ptr(Y), _stream())
     return Y
 
 
@@ -510,11 +500,8 @@ def dense_backward(X, Y, dY, W, relu, need_dX=True):
     dX = _empty(R, Din, device=X.device) if need_dX else None
     partial = _empty(lib.psvo_dense_wgrad_slices(R), (Din + 1) * Dout, device=X.device)
     grad = _empty((Din + 1) * Dout, device=X.device)
-    _mark("psvo_dense_backward", 0)
-    st = lib.psvo_dense_backward(R, Din, Dout, _ptr(X), _ptr(Y) if relu else None, _ptr(dY), _ptr(W), int(relu), _ptr(dX),
-                                 _ptr(partial), _ptr(grad), 0, _stream())
-    _mark("psvo_dense_backward", 1)
-    _lib.check(st, "psvo_dense_backward")
+    _launch("psvo_dense_backward", lib.psvo_dense_backward, R, Din, Dout, _ptr(X), _ptr(Y) if relu else None, _ptr(dY), _ptr(W),
+            int(relu), _ptr(dX), _ptr(partial), _ptr(grad), 0, _stream())
     return dX, grad[:Din * Dout].view(Din, Dout), grad[Din * Dout:]
 
 
@@ -569,9 +556,9 @@ def filter_backward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0,
         decisions = (_ptr(filt["rs"]),)
     sacc = z((lib.psvo_filter_wobs_ws_floats if wobs else lib.psvo_filter_ws_floats)(B, T, N, Dx, Dy))
     upstream = (_ptr(dlse),) if (wobs and not ext) else (_ptr(dlse), nparts, _ptr(dFm), _ptr(dlogW))
-    _mark(name, 0)
     with _fixed_order():
-        st = getattr(lib, name)(
+        _launch(
+            name, getattr(lib, name),
             ctypes.byref(desc), ctypes.byref(q1s), ctypes.byref(fs) if fs is not None else None, ctypes.byref(gs),
             _ptr(sig_q1), _ptr(sig_q2), _ptr(sig_f), _ptr(sig_g), _ptr(mu2), _ptr(m0), _ptr(sig0), _ptr(fm0), _ptr(fsig0),
             _ptr(obs), _ptr(eps), _ptr(filt["X"]), _ptr(filt["Fm"]), _ptr(filt["P1"]), _ptr(filt["logW"]),
@@ -579,8 +566,6 @@ def filter_backward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0,
             _ptr(out["dP"]), _ptr(out["dF"]), _ptr(out["dG"]), _ptr(out["dmu2"]), _ptr(out["dm0"]), _ptr(out["dfm0"]),
             _ptr(out["dsig_q1"]), _ptr(out["dsig_q2"]), _ptr(out["dsig_f"]), _ptr(out["dsig_g"]), _ptr(out["dsig0"]),
             _ptr(out["dfsig0"]), _ptr(sacc), *decisions, _stream())
-    _mark(name, 1)
-    _lib.check(st, name)
     # weight gradients from rows; gbufs = (q1, f, g) slices of the flat gradient buffer to accumulate into
     # directly (then no gradient tensor is returned for that MLP), or None
     gb = gbufs or (None, None, None)
@@ -666,17 +651,29 @@ def filter_forward_cov(desc, q1, f, g, sigc_q1, sigc_f, sigc_g, mu2, sig2, m0, s
     out = {"X": z(T, B, Dx, N), "Xanc": z(T, B, Dx, N), "Fm": z(T, B, Dx, N), "Fs": z(T, B, Dx, N), "logW": z(T, B, N),
            "idx": _empty(T, B, N, device=dev, dtype=torch.int32), "lse": z(T, B),
            "P1": None if desc.bootstrap else z(T, B, Dx, N), "P1s": None if desc.bootstrap else z(T, B, Dx, N)}
-    _mark("psvo_filter_forward_cov", 0)
-    st = lib.psvo_filter_forward_cov(
+    _launch(
+        "psvo_filter_forward_cov", lib.psvo_filter_forward_cov,
         ctypes.byref(desc), ctypes.byref(q1s), ctypes.byref(fs) if fs is not None else None, ctypes.byref(gs),
         _ptr(sigc_q1), _ptr(sigc_f), _ptr(sigc_g), _ptr(mu2), _ptr(sig2), _ptr(m0), _ptr(sig0), _ptr(fm0), _ptr(fsig0),
         _ptr(obs), _ptr(eps), _ptr(u), _ptr(idx_in),
         _ptr(out["X"]), _ptr(out["Xanc"]), _ptr(out["Fm"]), _ptr(out["Fs"]), _ptr(out["P1"]), _ptr(out["P1s"]),
         _ptr(out["logW"]), _ptr(out["idx"]), _ptr(out["lse"]), _stream())
-    _mark("psvo_filter_forward_cov", 1)
-    _lib.check(st, "psvo_filter_forward_cov")
     del k1, k2, k3
     return out
+
+
+def _ffbs_inputs(fn, desc, filt, sig_f, u, idx_in):
+    """what ffbs_smooth and ffbs_sample (`fn`: the caller's name) check alike -> the filter's (X, Fm, Fs, logW)"""
+    B, T, N, Dx = desc.B, desc.T, desc.N, desc.Dx
+    X, Fm, Fs, logW = filt["X"], filt["Fm"], filt.get("Fs"), filt["logW"]
+    if X is None or Fm is None or logW is None:
+        raise ValueError("%s needs the filter's X, Fm and logW" % fn)
+    _chk(X, (T, B, Dx, N), "X"); _chk(Fm, (T, B, Dx, N), "Fm"); _chk(Fs, (T, B, Dx, N), "Fs"); _chk(logW, (T, B, N), "logW")
+    _chk(sig_f, (Dx,), "sig_f")
+    if (Fs is None) == (sig_f is None):
+        raise ValueError("%s takes exactly one transition scale: the filter's per-particle `Fs` or a constant `sig_f`" % fn)
+    _chk(u, (T, B, N), "u"); _chk(idx_in, (T, B, N), "idx_in", torch.int32)
+    return X, Fm, Fs, logW
 
 
 def ffbs_smooth(desc, filt, sig_f=None, u=None, idx_in=None, want_draws=True):
@@ -687,14 +684,7 @@ def ffbs_smooth(desc, filt, sig_f=None, u=None, idx_in=None, want_draws=True):
     without draws.  Asynchronous on the launch stream."""
     lib = _lib.load()
     B, T, N, Dx = desc.B, desc.T, desc.N, desc.Dx
-    X, Fm, Fs, logW = filt["X"], filt["Fm"], filt.get("Fs"), filt["logW"]
-    if X is None or Fm is None or logW is None:
-        raise ValueError("ffbs_smooth needs the filter's X, Fm and logW")
-    _chk(X, (T, B, Dx, N), "X"); _chk(Fm, (T, B, Dx, N), "Fm"); _chk(Fs, (T, B, Dx, N), "Fs"); _chk(logW, (T, B, N), "logW")
-    _chk(sig_f, (Dx,), "sig_f")
-    if (Fs is None) == (sig_f is None):
-        raise ValueError("ffbs_smooth takes exactly one transition scale: the filter's per-particle `Fs` or a constant `sig_f`")
-    _chk(u, (T, B, N), "u"); _chk(idx_in, (T, B, N), "idx_in", torch.int32)
+    X, Fm, Fs, logW = _ffbs_inputs("ffbs_smooth", desc, filt, sig_f, u, idx_in)
     if want_draws and u is None and idx_in is None:
         raise ValueError("smoothed draws need uniforms `u` or teacher-forced `idx_in`")
     dev = X.device
@@ -703,12 +693,9 @@ def ffbs_smooth(desc, filt, sig_f=None, u=None, idx_in=None, want_draws=True):
            "idx": _empty(T, B, N, device=dev, dtype=torch.int32) if want_draws else None}
     if not want_draws:
         u = idx_in = None
-    _mark("psvo_ffbs_smooth", 0)
-    st = lib.psvo_ffbs_smooth(ctypes.byref(desc), _ptr(X), _ptr(Fm), _ptr(Fs), _ptr(sig_f), _ptr(logW), _ptr(u), _ptr(idx_in),
-                              _ptr(out["logWs"]), _ptr(out["Xmean"]), _ptr(out["ess"]), _ptr(out["Xs"]), _ptr(out["idx"]),
-                              _stream())
-    _mark("psvo_ffbs_smooth", 1)
-    _lib.check(st, "psvo_ffbs_smooth")
+    _launch("psvo_ffbs_smooth", lib.psvo_ffbs_smooth, ctypes.byref(desc), _ptr(X), _ptr(Fm), _ptr(Fs), _ptr(sig_f), _ptr(logW),
+            _ptr(u), _ptr(idx_in), _ptr(out["logWs"]), _ptr(out["Xmean"]), _ptr(out["ess"]), _ptr(out["Xs"]), _ptr(out["idx"]),
+            _stream())
     return out
 
 
@@ -720,24 +707,14 @@ def ffbs_sample(desc, filt, sig_f=None, u=None, idx_in=None):
     number of different particles the N paths pass through).  Asynchronous on the launch stream."""
     lib = _lib.load()
     B, T, N, Dx = desc.B, desc.T, desc.N, desc.Dx
-    X, Fm, Fs, logW = filt["X"], filt["Fm"], filt.get("Fs"), filt["logW"]
-    if X is None or Fm is None or logW is None:
-        raise ValueError("ffbs_sample needs the filter's X, Fm and logW")
-    _chk(X, (T, B, Dx, N), "X"); _chk(Fm, (T, B, Dx, N), "Fm"); _chk(Fs, (T, B, Dx, N), "Fs"); _chk(logW, (T, B, N), "logW")
-    _chk(sig_f, (Dx,), "sig_f")
-    if (Fs is None) == (sig_f is None):
-        raise ValueError("ffbs_sample takes exactly one transition scale: the filter's per-particle `Fs` or a constant `sig_f`")
-    _chk(u, (T, B, N), "u"); _chk(idx_in, (T, B, N), "idx_in", torch.int32)
+    X, Fm, Fs, logW = _ffbs_inputs("ffbs_sample", desc, filt, sig_f, u, idx_in)
     if u is None and idx_in is None:
         raise ValueError("backward sampling needs uniforms `u` or teacher-forced `idx_in`")
     dev = X.device
     out = {"Xs": _empty(T, B, Dx, N, device=dev), "idx": _empty(T, B, N, device=dev, dtype=torch.int32),
            "logq": _empty(T, B, N, device=dev), "distinct": _empty(T, B, device=dev, dtype=torch.int32)}
-    _mark("psvo_ffbs_sample", 0)
-    st = lib.psvo_ffbs_sample(ctypes.byref(desc), _ptr(X), _ptr(Fm), _ptr(Fs), _ptr(sig_f), _ptr(logW), _ptr(u), _ptr(idx_in),
-                              _ptr(out["Xs"]), _ptr(out["idx"]), _ptr(out["logq"]), _ptr(out["distinct"]), _stream())
-    _mark("psvo_ffbs_sample", 1)
-    _lib.check(st, "psvo_ffbs_sample")
+    _launch("psvo_ffbs_sample", lib.psvo_ffbs_sample, ctypes.byref(desc), _ptr(X), _ptr(Fm), _ptr(Fs), _ptr(sig_f), _ptr(logW),
+            _ptr(u), _ptr(idx_in), _ptr(out["Xs"]), _ptr(out["idx"]), _ptr(out["logq"]), _ptr(out["distinct"]), _stream())
     return out
 
 
@@ -765,12 +742,9 @@ def particle_forecast(desc, K, f, g, sig_f, sig_g, X, logW=None, obs=None, eps=N
     dev = X.device
     out = {"ymean": _empty(K + 1, T, B, Dy, device=dev), "yvar": _empty(K + 1, T, B, Dy, device=dev),
            "xmean": _empty(K + 1, T, B, Dx, device=dev), "lpd": _empty(K + 1, T, B, device=dev) if obs is not None else None}
-    _mark("psvo_particle_forecast", 0)
-    st = lib.psvo_particle_forecast(ctypes.byref(desc), K, ctypes.byref(fs), ctypes.byref(gs), _ptr(sig_f), _ptr(sig_g), _ptr(X),
-                                    _ptr(logW), _ptr(obs), _ptr(eps), _ptr(out["ymean"]), _ptr(out["yvar"]), _ptr(out["xmean"]),
-                                    _ptr(out["lpd"]), _stream())
-    _mark("psvo_particle_forecast", 1)
-    _lib.check(st, "psvo_particle_forecast")
+    _launch("psvo_particle_forecast", lib.psvo_particle_forecast, ctypes.byref(desc), K, ctypes.byref(fs), ctypes.byref(gs),
+            _ptr(sig_f), _ptr(sig_g), _ptr(X), _ptr(logW), _ptr(obs), _ptr(eps), _ptr(out["ymean"]), _ptr(out["yvar"]),
+            _ptr(out["xmean"]), _ptr(out["lpd"]), _stream())
     return out
 
 
@@ -794,9 +768,9 @@ def filter_backward_cov(desc, q1, f, g, sigc_q1, sigc_f, sigc_g, mu2, sig2, m0, 
            "dm0": z(B, Dx), "dsig0": z(B, Dx), "dfm0": z(B, Dx), "dfsig0": z(B, Dx),
            "dsigc_q1": z(Dx), "dsigc_f": None if boot else z(Dx), "dsigc_g": z(Dy)}
     ws = z(lib.psvo_filter_cov_ws_floats(B, T, N, Dx, Dy))
-    _mark("psvo_filter_backward_cov", 0)
     with _fixed_order():
-        st = lib.psvo_filter_backward_cov(
+        _launch(
+            "psvo_filter_backward_cov", lib.psvo_filter_backward_cov,
             ctypes.byref(desc), ctypes.byref(q1s), ctypes.byref(fs) if fs is not None else None, ctypes.byref(gs),
             _ptr(sigc_q1), _ptr(sigc_f), _ptr(sigc_g), _ptr(mu2), _ptr(sig2), _ptr(m0), _ptr(sig0), _ptr(fm0), _ptr(fsig0),
             _ptr(obs), _ptr(eps), _ptr(filt["X"]), _ptr(filt["Fm"]), _ptr(filt["Fs"]), _ptr(filt["P1"]), _ptr(filt["P1s"]),
@@ -805,8 +779,6 @@ def filter_backward_cov(desc, q1, f, g, sigc_q1, sigc_f, sigc_g, mu2, sig2, m0, 
             _ptr(out["dG"][1]), _ptr(out["dmu2"]), _ptr(out["dsig2"]), _ptr(out["dm0"]), _ptr(out["dsig0"]),
             _ptr(out["dfm0"]), _ptr(out["dfsig0"]), _ptr(out["dsigc_q1"]), _ptr(out["dsigc_f"]), _ptr(out["dsigc_g"]),
             _ptr(ws), _stream())
-    _mark("psvo_filter_backward_cov", 1)
-    _lib.check(st, "psvo_filter_backward_cov")
     del k1, k2, k3
     out["gq1"] = _head_grads(q1, filt["X"], *out["dP"], Dx, H, Dx)
     out["gf"] = None if boot else _head_grads(f, filt["X"], *out["dF"], Dx, H, Dx)
@@ -884,15 +856,13 @@ def bsim_forward_cov(desc, filt, f, g, q1_inv, sigc_f, sigc_g, sigc_q1inv, bmu2,
     z = lambda *s: _empty(*s, device=dev)
     out = {"bwX": z(T, B, Dx, N), "flp": z(T, B, N), "glp": z(T, B, N), "Omega": z(T, B, N),
            "sel": _empty(T, B, N, device=dev, dtype=torch.int32), "score": z(B, N), **_bsim_cov_saves(desc, dev, save)}
-    _mark("psvo_bsim_forward_cov", 0)
-    st = lib.psvo_bsim_forward_cov(
+    _launch(
+        "psvo_bsim_forward_cov", lib.psvo_bsim_forward_cov,
         ctypes.byref(desc), _ptr(filt["Fm"]), _ptr(filt["Fs"]), _ptr(filt["logW"]), _ptr(filt["lse"]),
         ctypes.byref(fs), ctypes.byref(gs), ctypes.byref(qs), _ptr(sigc_f), _ptr(sigc_g), _ptr(sigc_q1inv),
         _ptr(bmu2), _ptr(bsig2), _ptr(minit), _ptr(sinit), _ptr(imean), _ptr(isig), _ptr(obs), _ptr(eps_b), _ptr(u_b),
         _ptr(sel_in), _ptr(out["bwX"]), _ptr(out["flp"]), _ptr(out["glp"]), _ptr(out["Omega"]), _ptr(out["sel"]),
         _ptr(out["score"]), _ptr(out["lam"]), _ptr(out["om"]), _ptr(out["mu1"]), _ptr(out["s1"]), _stream())
-    _mark("psvo_bsim_forward_cov", 1)
-    _lib.check(st, "psvo_bsim_forward_cov")
     del keep
     return out
 
@@ -906,10 +876,10 @@ def bsim_backward_cov(desc, filt, f, g, q1_inv, sigc_f, sigc_g, sigc_q1inv, bmu2
     fs, gs, qs, keep = _bsim_cov_structs(desc, f, g, q1_inv)
     _chk(dscore, (desc.B, desc.N), "dscore")
     out = _bsim_cov_grads(desc, dev)
-    _mark("psvo_bsim_backward_cov", 0)
     with _fixed_order() as det:
         det_ws = _bsim_cov_det_ws(lib, desc, dev, det)
-        st = lib.psvo_bsim_backward_cov_ws(
+        _launch(
+            "psvo_bsim_backward_cov", lib.psvo_bsim_backward_cov_ws,      # (the name the hook and the checks know it by)
             ctypes.byref(desc), _ptr(filt["Fm"]), _ptr(filt["Fs"]), _ptr(filt["logW"]), _ptr(filt["lse"]),
             ctypes.byref(fs), ctypes.byref(gs), ctypes.byref(qs), _ptr(sigc_f), _ptr(sigc_g), _ptr(sigc_q1inv),
             _ptr(bmu2), _ptr(bsig2), _ptr(minit), _ptr(sinit), _ptr(imean), _ptr(isig), _ptr(obs), _ptr(eps_b),
@@ -919,8 +889,6 @@ def bsim_backward_cov(desc, filt, f, g, q1_inv, sigc_f, sigc_g, sigc_q1inv, bmu2
             _ptr(out["dbmu2"]), _ptr(out["dbsig2"]), _ptr(out["dminit"]), _ptr(out["dsinit"]), _ptr(out["dimean"]),
             _ptr(out["disig"]), _ptr(out["dsigc_f"]), _ptr(out["dsigc_g"]), _ptr(out["dsigc_q1inv"]), _ptr(det_ws),
             _stream())
-    _mark("psvo_bsim_backward_cov", 1)
-    _lib.check(st, "psvo_bsim_backward_cov")
     del keep
     _bsim_cov_head_grads(out, desc, f, g, q1_inv, bs["bwX"])
     return out
@@ -942,16 +910,14 @@ def bsimwr_forward_cov(desc, filt, f, g, q1_inv, sigc_f, sigc_g, sigc_q1inv, bmu
     zi = lambda *s: _empty(*s, device=dev, dtype=torch.int32)
     out = {"bwX": z(T, B, Dx, N), "bwXanc": z(T, B, Dx, N), "bwW": z(T, B, N), "lseW": z(T, B), "sel": zi(T, B, N),
            "anc": zi(T, B, N), "omsel": z(T, B, N), **_bsim_cov_saves(desc, dev, save)}
-    _mark("psvo_bsimwr_forward_cov", 0)
-    st = lib.psvo_bsimwr_forward_cov(
+    _launch(
+        "psvo_bsimwr_forward_cov", lib.psvo_bsimwr_forward_cov,
         ctypes.byref(desc), _ptr(filt["Fm"]), _ptr(filt["Fs"]), _ptr(filt["logW"]), _ptr(filt["lse"]),
         ctypes.byref(fs), ctypes.byref(gs), ctypes.byref(qs), _ptr(sigc_f), _ptr(sigc_g), _ptr(sigc_q1inv),
         _ptr(bmu2), _ptr(bsig2), _ptr(minit), _ptr(sinit), _ptr(imean), _ptr(isig), _ptr(obs), _ptr(eps_b), _ptr(u_b),
         _ptr(u_r), _ptr(sel_in), _ptr(anc_in), _ptr(out["bwX"]), _ptr(out["bwXanc"]), _ptr(out["bwW"]), _ptr(out["lseW"]),
         _ptr(out["sel"]), _ptr(out["anc"]), _ptr(out["omsel"]), _ptr(out["lam"]), _ptr(out["om"]), _ptr(out["mu1"]),
         _ptr(out["s1"]), _stream())
-    _mark("psvo_bsimwr_forward_cov", 1)
-    _lib.check(st, "psvo_bsimwr_forward_cov")
     del keep
     return out
 
@@ -965,10 +931,10 @@ def bsimwr_backward_cov(desc, filt, f, g, q1_inv, sigc_f, sigc_g, sigc_q1inv, bm
     _chk(dlseW, (desc.T, desc.B), "dlseW")
     out = _bsim_cov_grads(desc, dev)
     dXs = _zeros(desc.T, desc.B, desc.Dx, desc.N, device=dev)
-    _mark("psvo_bsimwr_backward_cov", 0)
     with _fixed_order() as det:
         det_ws = _bsim_cov_det_ws(lib, desc, dev, det)
-        st = lib.psvo_bsimwr_backward_cov_ws(
+        _launch(
+            "psvo_bsimwr_backward_cov", lib.psvo_bsimwr_backward_cov_ws,      # (as above)
             ctypes.byref(desc), _ptr(filt["Fm"]), _ptr(filt["Fs"]), _ptr(filt["logW"]), _ptr(filt["lse"]),
             ctypes.byref(fs), ctypes.byref(gs), ctypes.byref(qs), _ptr(sigc_f), _ptr(sigc_g), _ptr(sigc_q1inv),
             _ptr(bmu2), _ptr(bsig2), _ptr(minit), _ptr(sinit), _ptr(imean), _ptr(isig), _ptr(obs), _ptr(eps_b),
@@ -979,8 +945,6 @@ def bsimwr_backward_cov(desc, filt, f, g, q1_inv, sigc_f, sigc_g, sigc_q1inv, bm
             _ptr(out["dbmu2"]), _ptr(out["dbsig2"]), _ptr(out["dminit"]), _ptr(out["dsinit"]), _ptr(out["dimean"]),
             _ptr(out["disig"]), _ptr(out["dsigc_f"]), _ptr(out["dsigc_g"]), _ptr(out["dsigc_q1inv"]), _ptr(dXs),
             _ptr(det_ws), _stream())
-    _mark("psvo_bsimwr_backward_cov", 1)
-    _lib.check(st, "psvo_bsimwr_backward_cov")
     del keep
     _bsim_cov_head_grads(out, desc, f, g, q1_inv, bs["bwXanc"])
     return out
@@ -1021,8 +985,8 @@ def bsim_backward(desc, filt, f, g, q1_inv, sig_f, sig_g, sig_q1inv, sig_bq2, bm
     out = _bsim_grads(desc, dev, nblk, (("dFm", (T, B, Dx, N)), ("dlogW", (T, B, N)), ("dlse", (T, B))))
     _chain_rows(out, z, T, B, Dx, N)
     sacc = z(B, nblk, lib.psvo_bsim_acc_size(Dx, Dy))
-    _mark("psvo_bsim_backward", 0)
-    st = lib.psvo_bsim_backward(
+    _launch(
+        "psvo_bsim_backward", lib.psvo_bsim_backward,
         ctypes.byref(desc), _ptr(filt["Fm"]), _ptr(filt["logW"]), _ptr(filt["lse"]),
         ctypes.byref(fs), ctypes.byref(gs), ctypes.byref(qs),
         _ptr(sig_f), _ptr(sig_g), _ptr(sig_q1inv), _ptr(sig_bq2), _ptr(bmu2), _ptr(minit), _ptr(sig_init),
@@ -1031,17 +995,13 @@ def bsim_backward(desc, filt, f, g, q1_inv, sig_f, sig_g, sig_q1inv, sig_bq2, bm
         _ptr(out["xt"]), _ptr(out["dFt"]), _ptr(out["dGt"]), _ptr(out["dmu1"]),
         _ptr(out["dFm_part"]), _ptr(out["dlogW_part"]), _ptr(out["dbmu2_rows"]), _ptr(out["dminit_rows"]),
         _ptr(out["dimean_rows"]), _ptr(sacc), _stream())
-    _mark("psvo_bsim_backward", 1)
-    _lib.check(st, "psvo_bsim_backward")
     # one more launch folds the per-workgroup partials into d Fm / d logW (which feed the filter's reverse pass) and the
     # scale gradients; then the caller publishes them
-    _mark("psvo_bsim_backward_fold", 0)
-    st = lib.psvo_bsim_backward_fold(
+    _launch(
+        "psvo_bsim_backward_fold", lib.psvo_bsim_backward_fold,
         ctypes.byref(desc), _ptr(out["dFm_part"]), _ptr(out["dlogW_part"]), _ptr(sacc), _ptr(sig_q1inv), _ptr(sig_bq2),
         _ptr(out["dFm"]), _ptr(out["dlogW"]), _ptr(out["dsig_f"]), _ptr(out["dsig_g"]), _ptr(out["dsig_q1inv"]),
         _ptr(out["dsig_bq2"]), _ptr(out["dsig_init"]), _ptr(out["disig"]), _ptr(out["dlse"]), _stream())
-    _mark("psvo_bsim_backward_fold", 1)
-    _lib.check(st, "psvo_bsim_backward_fold")
     if after_kernel is not None:
         after_kernel(out)
     # weight gradients from rows; gbufs = (f, g, q1_inv) slices of the flat gradient buffer to accumulate into, or None.  wgrad_stream
@@ -1069,13 +1029,11 @@ def bsim_backward_wobs(desc, filt, f, g, q1_inv, sig_f, sig_g, sig_q1inv, sig_bq
     _bsim_chk_saves(desc, bs, "bsim", (("bwX", (T, B, Dx, N)),))
     _chk(bs["sel"], (T, B, N), "sel", torch.int32)
     z = lambda *s: _empty(*s, device=dev)
-    out = {"xt": z(T, B, Dx, N, M), "dFt": z(T, B, Dx, N, M), "dGt": z(T, B, Dy, N, M), "dmu1": z(T, B, Dx, N),
-           "dFm": z(T, B, Dx, N), "dlogW": z(T, B, N), "dlse": z(T, B),
-           "dsig_f": z(Dx), "dsig_g": z(Dy), "dsig_q1inv": z(Dx), "dsig_bq2": z(Dx), "dsig_init": z(Dx), "disig": z(Dx)}
+    out = _bsim_grads(desc, dev, 0, (("dFm", (T, B, Dx, N)), ("dlogW", (T, B, N)), ("dlse", (T, B))))
     _chain_rows(out, z, T, B, Dx, N)
     ws = z(max(1, lib.psvo_bsim_wobs_ws_floats(B, T, N, M, Dx, Dy)))
-    _mark("psvo_bsim_backward_wobs", 0)
-    st = lib.psvo_bsim_backward_wobs(
+    _launch(
+        "psvo_bsim_backward_wobs", lib.psvo_bsim_backward_wobs,
         ctypes.byref(desc), _ptr(filt["Fm"]), _ptr(filt["logW"]), _ptr(filt["lse"]),
         ctypes.byref(fs), ctypes.byref(gs), ctypes.byref(qs),
         _ptr(sig_f), _ptr(sig_g), _ptr(sig_q1inv), _ptr(sig_bq2), _ptr(bmu2), _ptr(minit), _ptr(sig_init),
@@ -1086,8 +1044,6 @@ def bsim_backward_wobs(desc, filt, f, g, q1_inv, sig_f, sig_g, sig_q1inv, sig_bq
         _ptr(out["dFm"]), _ptr(out["dlogW"]), _ptr(out["dlse"]),
         _ptr(out["dsig_f"]), _ptr(out["dsig_g"]), _ptr(out["dsig_q1inv"]), _ptr(out["dsig_bq2"]), _ptr(out["dsig_init"]),
         _ptr(out["disig"]), _ptr(ws), _stream())
-    _mark("psvo_bsim_backward_wobs", 1)
-    _lib.check(st, "psvo_bsim_backward_wobs")
     # weight gradients from rows: MLP_g's through the wide-output kernel with L = N M rows per (t, b) segment
     out["gf"] = mlp_wgrad(out["xt"][:T - 1], out["dFt"][:T - 1], f, Dx, H, Dx)
     out["gg"] = mlp_wgrad(out["xt"], out["dGt"], g, Dx, H, Dy, wobs=True)
@@ -1111,16 +1067,14 @@ def bsimwr_forward(desc, filt, f, g, q1_inv, sig_f, sig_g, sig_q1inv, sig_bq2, b
     out = {"bwX": z(T, B, Dx, N), "bwXanc": z(T, B, Dx, N), "bwW": z(T, B, N), "lseW": z(T, B),
            "sel": zi(T, B, N), "anc": zi(T, B, N), **_bsim_saves(desc, dev, save),
            "ws": z(lib.psvo_bsimwr_ws_floats(B, T, N))}   # (its last word, as int32, is nonzero iff a cluster barrier timed out)
-    _mark("psvo_bsimwr_forward", 0)
-    st = lib.psvo_bsimwr_forward(
+    _launch(
+        "psvo_bsimwr_forward", lib.psvo_bsimwr_forward,
         ctypes.byref(desc), _ptr(filt["Fm"]), _ptr(filt["logW"]), _ptr(filt["lse"]),
         ctypes.byref(fs), ctypes.byref(gs), ctypes.byref(qs),
         _ptr(sig_f), _ptr(sig_g), _ptr(sig_q1inv), _ptr(sig_bq2), _ptr(bmu2), _ptr(minit), _ptr(sig_init),
         _ptr(imean), _ptr(isig), _ptr(obs), _ptr(eps_b), _ptr(u_b), _ptr(u_r), _ptr(sel_in), _ptr(anc_in),
         _ptr(out["bwX"]), _ptr(out["bwXanc"]), _ptr(out["bwW"]), _ptr(out["lseW"]), _ptr(out["sel"]),
         _ptr(out["anc"]), _ptr(out["lam2"]), _ptr(out["om"]), _ptr(out["mu1"]), _ptr(out["ws"]), _stream())
-    _mark("psvo_bsimwr_forward", 1)
-    _lib.check(st, "psvo_bsimwr_forward")
     return out
 
 
@@ -1139,8 +1093,8 @@ def bsimwr_backward(desc, filt, f, g, q1_inv, sig_f, sig_g, sig_q1inv, sig_bq2, 
     out["ws"] = z(lib.psvo_bsimwr_bwd_ws_floats(B, T, N, Dx))
     _chain_rows(out, z, T, B, Dx, N)
     sacc = z(B, K, lib.psvo_bsim_acc_size(Dx, Dy))
-    _mark("psvo_bsimwr_backward", 0)
-    st = lib.psvo_bsimwr_backward(
+    _launch(
+        "psvo_bsimwr_backward", lib.psvo_bsimwr_backward,
         ctypes.byref(desc), _ptr(filt["Fm"]), _ptr(filt["logW"]), _ptr(filt["lse"]),
         ctypes.byref(fs), ctypes.byref(gs), ctypes.byref(qs),
         _ptr(sig_f), _ptr(sig_g), _ptr(sig_q1inv), _ptr(sig_bq2), _ptr(bmu2), _ptr(minit), _ptr(sig_init),
@@ -1151,8 +1105,6 @@ def bsimwr_backward(desc, filt, f, g, q1_inv, sig_f, sig_g, sig_q1inv, sig_bq2, 
         _ptr(out["dminit_rows"]), _ptr(out["dimean_rows"]), _ptr(out["dsig_f"]), _ptr(out["dsig_g"]),
         _ptr(out["dsig_q1inv"]), _ptr(out["dsig_bq2"]), _ptr(out["dsig_init"]), _ptr(out["disig"]), _ptr(sacc),
         _ptr(out["ws"]), _stream())
-    _mark("psvo_bsimwr_backward", 1)
-    _lib.check(st, "psvo_bsimwr_backward")
     # fold the per-workgroup partials that feed the filter's reverse pass, then let the caller publish them
     out["dFm"] = out["dFm_part"].sum(2)
     out["dlogW"] = out["dlogW_part"].sum(2)
@@ -1197,11 +1149,8 @@ def bilstm_backward(x, W_fw, W_bw, out, cs, gates, dout, gbufs=None, need_dx=Tru
     dx_part = _empty(2, B, T, Din, device=dev)
     dW_part = _empty(B, 2, Din + Dh, 4 * Dh, device=dev)
     db_part = _empty(B, 2, 4 * Dh, device=dev)
-    _mark("psvo_bilstm_backward", 0)
-    st = lib.psvo_bilstm_backward(B, T, Din, Dh, _ptr(x), _ptr(W_fw), _ptr(W_bw), _ptr(out), _ptr(cs), _ptr(gates),
-                                  _ptr(dout), _ptr(dx_part), _ptr(dW_part), _ptr(db_part), _stream())
-    _mark("psvo_bilstm_backward", 1)
-    _lib.check(st, "psvo_bilstm_backward")
+    _launch("psvo_bilstm_backward", lib.psvo_bilstm_backward, B, T, Din, Dh, _ptr(x), _ptr(W_fw), _ptr(W_bw), _ptr(out), _ptr(cs),
+            _ptr(gates), _ptr(dout), _ptr(dx_part), _ptr(dW_part), _ptr(db_part), _stream())
     dx = dx_part.sum(0) if need_dx else None     # (the first layer's input is the observations: no gradient wanted)
     K, G4 = Din + Dh, 4 * Dh
     if gbufs is not None and gbufs[0] is not None and gbufs[1] is not None:

@@ -396,3 +396,91 @@ def test_oracle_encoder_gradients_match_torch_lstm_in_fp64(mode, Dhs, Din):
     for n, r in g_ref.items():
         assert float(r.abs().max()) > 0, n
         assert float((got[n] - r).abs().max()) <= 1e-12 * float(r.abs().max()), n
+
+
+# ---- the filter nodes' gradient tail (psvo_amd.autograd._filter_grads) on a hand-made result dict ---------------------------
+def _filter_tail_case(layers=1, two_q=True, boot=True, same=True):
+    """(desc, result dict as ops.filter_backward returns it, (m0, sig0, fm0, fsig0)): every entry a distinct CPU tensor"""
+    from psvo_amd import ops
+    B, T, Dx, Dy, H = 2, 3, 2, 1, 4
+    desc = ops.make_desc(B, T, 4, 1, Dx, Dy, H, two_q=two_q, bootstrap=boot, layers=layers)
+    flat = lambda Dout: torch.randn(ops.mlp_grad_size(Dx, H, Dout, layers))
+    r = {"gq1": flat(Dx), "gf": None if boot else flat(Dx), "gg": flat(Dy), "dmu2": torch.randn(T, B, Dx),
+         "dm0": torch.randn(B, Dx), "dfm0": torch.randn(B, Dx), "dsig_g": torch.randn(Dy)}
+    r.update({k: torch.randn(Dx) for k in ("dsig_q1", "dsig_q2", "dsig_f", "dsig0", "dfsig0")})
+    m0, sig0 = torch.zeros(B, Dx), torch.ones(Dx)
+    fm0, fsig0 = (m0, sig0) if same else (torch.zeros(B, Dx), torch.ones(Dx))
+    return desc, r, (m0, sig0, fm0, fsig0)
+
+
+@pytest.mark.parametrize("layers", [1, 2])
+def test_filter_grads_tail_layout(layers):
+    """12 MLP tensors, sig_q1 sig_q2 sig_f sig_g mu2 m0 sig0 fm0 fsig0, then (Wh, bh) per MLP with two hidden layers"""
+    from psvo_amd import ops
+    from psvo_amd.autograd import _filter_grads
+    Dx, Dy, H = 2, 1, 4
+    desc, r, init = _filter_tail_case(layers, two_q=True, boot=False, same=False)
+    out = _filter_grads(r, desc, *init, None)
+    assert len(out) == 21 + (6 if layers == 2 else 0) and all(v is not None for v in out)
+    for i, (key, Dout) in enumerate((("gq1", Dx), ("gf", Dx), ("gg", Dy))):
+        g = ops.split_mlp_grad(r[key], Dx, H, Dout, layers)
+        assert [tuple(v.shape) for v in out[4 * i:4 * i + 4]] == [(Dx, H), (H,), (H, Dout), (Dout,)]
+        assert all(torch.equal(a, b) for a, b in zip(out[4 * i:4 * i + 4], g[:4]))
+        if layers == 2:
+            assert all(torch.equal(a, b) for a, b in zip(out[21 + 2 * i:23 + 2 * i], g[4:6]))
+    want = ("dsig_q1", "dsig_q2", "dsig_f", "dsig_g", "dmu2", "dm0", "dsig0", "dfm0", "dfsig0")
+    assert all(a is r[k] for a, k in zip(out[12:21], want))
+
+
+def test_filter_grads_tail_nones():
+    from psvo_amd.autograd import _filter_grads
+    # one tensor passed as both m0 and fm0 (sig0 and fsig0): its gradient once, in d m0 (d sig0); each pair on its own
+    desc, r, (m0, sig0, fm0, fsig0) = _filter_tail_case(same=True)
+    out = _filter_grads(r, desc, m0, sig0, fm0, fsig0, None)
+    assert out[17] is r["dm0"] and out[18] is r["dsig0"] and out[19] is None and out[20] is None
+    out = _filter_grads(r, desc, m0, sig0, m0.clone(), fsig0, None)
+    assert out[19] is r["dfm0"] and out[20] is None
+    out = _filter_grads(r, desc, m0, sig0, fm0, sig0.clone(), None)
+    assert out[19] is None and out[20] is r["dfsig0"]
+    # without two_q no d sig_q2 / d mu2; under bootstrap nothing for MLP_f and sig_f
+    desc, r, init = _filter_tail_case(two_q=False, boot=True)
+    out = _filter_grads(r, desc, *init, None)
+    assert out[13] is None and out[16] is None and out[4:8] == (None,) * 4 and out[14] is None
+    desc, r, init = _filter_tail_case(two_q=True, boot=False)
+    out = _filter_grads(r, desc, *init, None)
+    assert out[13] is r["dsig_q2"] and out[16] is r["dmu2"] and out[14] is r["dsig_f"] and all(v is not None for v in out[4:8])
+    # an MLP whose gradient the kernels accumulated into its slice of the flat buffer returns nothing, extras included
+    desc, r, init = _filter_tail_case(layers=2, boot=False)
+    out = _filter_grads(r, desc, *init, (torch.zeros(1), None, torch.zeros(1)))
+    assert out[0:4] == (None,) * 4 and out[8:12] == (None,) * 4 and all(v is not None for v in out[4:8])
+    assert out[21:23] == (None, None) and out[25:27] == (None, None) and all(v is not None for v in out[23:25])
+
+
+@pytest.mark.parametrize("layers", [1, 2])
+@pytest.mark.parametrize("node,op,route", [("FilterFunction", "filter_backward", {"gbufs": None}),
+                                           ("FilterWobsFunction", "filter_backward_wobs", {}),
+                                           ("FilterAdaptiveFunction", "filter_backward", {"adaptive": True}),
+                                           ("FilterWobsAdaptiveFunction", "filter_backward_wobs_adaptive", {})])
+def test_filter_nodes_return_one_gradient_per_input(monkeypatch, node, op, route, layers):
+    """each node's backward returns as many entries as its forward takes: None for the named non-tensor inputs, then the tail"""
+    import inspect
+    import types
+    from psvo_amd import autograd, ops
+    cls = getattr(autograd, node)
+    desc, r, init = _filter_tail_case(layers, boot=False, same=False)
+    seen = {}
+
+    def stub(d, *args, **kw):
+        seen.update(kw, nargs=len(args))
+        return r
+    monkeypatch.setattr(ops, op, stub)
+    rest = [None] * 5 + list(init)
+    ctx = types.SimpleNamespace(desc=desc, filt={}, gbufs=None, saved=("q1", "f", "g", rest, "obs", "eps"))
+    dlse = torch.ones(3, 2)
+    out = cls.backward(ctx, dlse) if "Adaptive" in node else cls.backward(ctx, dlse, None, None)
+    lead = len(inspect.signature(cls.forward).parameters) - 2          # (ctx and *t)
+    assert lead == (7 if "Adaptive" in node else 5)
+    assert len(out) == lead + 21 + (6 if layers == 2 else 0) and out[:lead] == (None,) * lead
+    assert out[lead] is not None and out[lead + 17] is r["dm0"]
+    assert seen["nargs"] == 3 + 9 + 2 + 1 and seen["dlse"] is dlse and seen["dFm"] is None and seen["dlogW"] is None
+    assert {k: seen[k] for k in route} == route and set(seen) == {"nargs", "dlse", "dFm", "dlogW"} | set(route)
