@@ -795,6 +795,49 @@ int psvo_filter_backward_wobs_adaptive(const psvo_desc* desc,
                               float* ws, const int32_t* rs, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Missing observations (added within ABI 6: purely additive).  psvo_filter_forward_wobs / psvo_filter_backward_wobs with one
+ * change of meaning: a NaN in obs is an observation that was not made.  There is no mask array -- no further pointer, no
+ * further stream from HBM; the observation row carries its own mask.  With o_e = (y_e == y_e):
+ *     emission 0 / 1:  log g(y | x) = sum_{e: o_e} [ -1/2 z_e^2 - log sig_g[e] - 1/2 log 2 pi ],   z_e = (y_e - mean_e) / sig_g[e]
+ *     emission 2:      log g(y | x) = sum_{e: o_e} [ y_e log lam_e - lam_e - log Gamma(y_e + 1) ]
+ *   terms added in the order e = 0 .. Dy-1, the constant with its term; a step with nothing observed has log g = 0 exactly, so
+ *   its weights are those of the transition over the proposal.  A NaN never reaches a sum: the term is computed and dropped by
+ *   a select (the row is a broadcast, so the choice is the same in every lane; no branch, barrier or store depends on it).
+ *   Every other value, +-inf included, is an observation as before.  lse, logW and the ELBO are then a bound on the log-density
+ *   of the observed entries; X, Xanc, Fm, idx keep their meaning, so psvo_elbo_filter, psvo_ffbs_smooth and psvo_ffbs_sample
+ *   consume the result unchanged.
+ *  reverse:  dG[t,b,e,:] of a missing (t,b,e) is WRITTEN as 0 (psvo_mlp_wgrad / psvo_mlp_wgrad_wobs read the row back), and
+ *            dsig_g[e] receives nothing from it; an output that is never observed gets exactly zero gradients in W2[:,e], b2[e]
+ *            and sig_g[e].  Upstream gradient dlse only.  One fixed order for every sum and no float atomics: two runs are
+ *            bit-identical.  ws: psvo_filter_wobs_ws_floats(B, T, N, Dx, Dy) floats, unchanged.
+ *  The argument lists are those of psvo_filter_forward_wobs and psvo_filter_backward_wobs.  The weight gradient of MLP_g from
+ *  the d G rows is psvo_mlp_wgrad_wobs for Dy >= 3 and the plain psvo_mlp_wgrad for Dy <= 2.
+ *  Envelope: 1 <= Dy <= 32 (the widths of the plain kernels included), Dx in {2,3,4}, H in {16,32,64}, N <= 512, one hidden
+ *  layer, emission 0 / 1 / 2, every bootstrap / two_q wiring, resampling on or off; anything else is PSVO_ERR_UNSUPPORTED.  A
+ *  missing required pointer, B <= 0, T < 2 or N <= 0 is PSVO_ERR_INVALID.  Both come back before a device is touched.  The
+ *  existing entry points keep their envelopes: psvo_filter_forward_wobs still refuses Dy < 3, psvo_mlp_wgrad_wobs Dout < 3.
+ * ------------------------------------------------------------------------------------------- */
+int psvo_filter_forward_wobs_missing(const psvo_desc* desc,
+                             const psvo_mlp* q1, const psvo_mlp* f, const psvo_mlp* g,
+                             const float* sig_q1, const float* sig_q2, const float* sig_f, const float* sig_g,
+                             const float* mu2,
+                             const float* m0, const float* sig0, const float* fm0, const float* fsig0,
+                             const float* obs, const float* eps, const float* u, const int32_t* idx_in,
+                             float* X, float* Xanc, float* Fm, float* P1, float* logW, int32_t* idx_out,
+                             float* lse, void* stream);
+int psvo_filter_backward_wobs_missing(const psvo_desc* desc,
+                              const psvo_mlp* q1, const psvo_mlp* f, const psvo_mlp* g,
+                              const float* sig_q1, const float* sig_q2, const float* sig_f, const float* sig_g,
+                              const float* mu2,
+                              const float* m0, const float* sig0, const float* fm0, const float* fsig0,
+                              const float* obs, const float* eps,
+                              const float* X, const float* Fm, const float* P1, const float* logW, const float* lse,
+                              const int32_t* idx, const float* dlse,
+                              float* dP, float* dF, float* dG, float* dmu2, float* dm0, float* dfm0,
+                              float* dsig_q1, float* dsig_q2, float* dsig_f, float* dsig_g, float* dsig0, float* dfsig0,
+                              float* ws, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * PSVO on wide observations: the backward simulation with proposal and its reverse pass for 3 <= Dy <= 32
  * (psvo_amd/csrc/bsim_wobs.hip), and the wide reverse filter with upstream gradients of Fm / logW (added within ABI 6).
  * The Dy <= 2 entry points are unchanged: psvo_bsim_forward, psvo_bsim_backward and psvo_bsim_backward_fold keep answering

@@ -10,7 +10,7 @@ import torch
 
 from .. import ops
 from ..autograd import (FilterAdaptiveFunction, FilterCovFunction, FilterFunction, FilterWobsAdaptiveFunction,
-                        FilterWobsFunction)
+                        FilterWobsFunction, FilterWobsMissingFunction)
 
 
 def check_resample_ess(raw, never_resamples=False, backward_simulation=False, output_cov=False, Dy=1, plain_dy=2,
@@ -51,6 +51,43 @@ def check_resample_ess(raw, never_resamples=False, backward_simulation=False, ou
     return tau
 
 
+def check_missing_obs(on, missing_rate=0.0, backward_simulation=False, resample_ess=0.0, particle_forecast=False,
+                      output_cov=False, Dy=1, layers=(), wobs_max_dy=32):
+    """--missing_obs (a NaN observation is an entry that was not observed) as a bool.  ValueError, naming the limit, for
+    everything the missing-observation kernels (psvo_filter_forward_wobs_missing) do not cover and for a --missing_rate that is
+    no probability or has nothing to act on (runner.main calls this on the flags before it touches a device, SVO.__init__ on the
+    model it is given).  `layers`: the hidden layers of the per-particle MLPs, one each."""
+    rate = float(0.0 if missing_rate is None else missing_rate)
+    if not (0.0 <= rate < 1.0):
+        raise ValueError("--missing_rate = %r: the probability of knocking an entry out lies in [0, 1)" % (missing_rate,))
+    if not on:
+        if rate != 0.0:
+            raise ValueError("--missing_rate without --missing_obs: the knocked-out entries are NaN, which only the "
+                             "missing-observation route scores; pass --missing_obs")
+        return False
+    limit = "missing observations run on psvo_filter_forward_wobs_missing, the filter of SVO / AESMC / IWAE"
+    if backward_simulation:
+        raise ValueError("--missing_obs with --PSVO / --PSVOwR: %s; the backward-simulation kernels evaluate the emission too and "
+                         "have no missing-observation form" % limit)
+    if float(resample_ess or 0.0) != 0.0:
+        raise ValueError("--missing_obs with --resample_ess: %s, which resamples at every step (or never); the adaptive kernels "
+                         "have no missing-observation form" % limit)
+    if particle_forecast:
+        raise ValueError("--missing_obs with --particle_forecast: the forecast's predictive log-density (lpd) scores whole "
+                         "observation rows; it has no missing-observation form")
+    if output_cov:
+        raise ValueError("--missing_obs with output_cov: %s, which takes state-independent scales; the state-dependent-scale "
+                         "kernels have no missing-observation form" % limit)
+    if Dy > wobs_max_dy or Dy < 1:
+        raise ValueError("--missing_obs with Dy = %d: %s, which takes 1 <= Dy <= %d; no fallback path exists"
+                         % (Dy, limit, wobs_max_dy))
+    deep = [v for v in (_layer_list(s) for s in layers) if len(v) != 1]
+    if deep:
+        raise ValueError("--missing_obs with per-particle MLP layers %s: %s, which takes one hidden layer per MLP; two hidden "
+                         "layers have no missing-observation form" % (deep, limit))
+    return True
+
+
 def _layer_list(spec):
     """a *_layers flag ("32" / "32,32") or a list of widths -> list of ints"""
     if isinstance(spec, str):
@@ -70,7 +107,9 @@ class SVO:
 
     def __init__(self, model, FLAGS, name="log_ZSMC"):
         self.model = model
-        self.wide_obs = self._route_wide_obs(model, bool(getattr(FLAGS, "BSim_wide_obs", False)))
+        # missing observations (FLAGS.missing_obs, not in the reference): a NaN observation is left out of the emission density
+        self.missing_obs = self._route_missing_obs(model, FLAGS)
+        self.wide_obs = self._route_wide_obs(model, bool(getattr(FLAGS, "BSim_wide_obs", False)), self.missing_obs)
 
         # SSM distributions
         self.q0 = model.q0_dist
@@ -105,7 +144,22 @@ class SVO:
         self.generator = None        # torch.Generator on the compute device; None = global RNG
 
     @classmethod
-    def _route_wide_obs(cls, model, bsim_wide_obs=False):
+    def _route_missing_obs(cls, model, FLAGS):
+        """True when the filter of this objective runs on psvo_filter_forward_wobs_missing / psvo_filter_backward_wobs_missing
+        (FLAGS.missing_obs, carried by the model; every 1 <= Dy <= 32, Dy <= 2 included, and all three emission forms).  What
+        those kernels do not cover is refused here, up front."""
+        trans = [t for t in (getattr(model, "q1_tran", None), getattr(model, "g_tran", None),
+                             None if getattr(model, "use_bootstrap", True) else getattr(model, "f_tran", None)) if t is not None]
+        return check_missing_obs(bool(getattr(model, "missing_obs", False) or getattr(FLAGS, "missing_obs", False)),
+                                 missing_rate=getattr(FLAGS, "missing_rate", 0.0),
+                                 backward_simulation=cls.uses_backward_simulation,
+                                 resample_ess=getattr(FLAGS, "resample_ess", 0.0),
+                                 particle_forecast=bool(getattr(FLAGS, "particle_forecast", False)),
+                                 output_cov=bool(getattr(model, "output_cov", False)), Dy=getattr(model, "Dy", cls._PLAIN_DY),
+                                 layers=[t.Dhs for t in dict.fromkeys(trans)], wobs_max_dy=cls._WOBS_MAX_DY)
+
+    @classmethod
+    def _route_wide_obs(cls, model, bsim_wide_obs=False, missing_obs=False):
         """True when the filter of this objective runs on the wide-observation kernels (model.Dy > 2: psvo_filter_forward_wobs /
         psvo_filter_backward_wobs / psvo_mlp_wgrad_wobs) -- and, for PSVO under FLAGS.BSim_wide_obs (`bsim_wide_obs`), its
         backward simulation on psvo_bsim_forward_wobs / psvo_bsim_backward_wobs.  What those kernels do not cover is refused
@@ -117,11 +171,11 @@ class SVO:
                 raise ValueError("--count_emission with --poisson_emission: one emission at a time -- count_emission is the "
                                  "Poisson likelihood of counts, poisson_emission the reference's unit-scale normal around "
                                  "the rate")
-            if Dy <= cls._PLAIN_DY:
+            if Dy <= cls._PLAIN_DY and not missing_obs:
                 raise ValueError("--count_emission with Dy = %d: the count emission runs on the wide-observation kernels, which "
                                  "take 3 <= Dy <= %d; the plain kernels (Dy <= %d) have no count form"
                                  % (Dy, cls._WOBS_MAX_DY, cls._PLAIN_DY))
-        if Dy <= cls._PLAIN_DY:
+        if Dy <= cls._PLAIN_DY or missing_obs:      # (missing observations: _route_missing_obs has routed the filter)
             return False
         limit = "observations wider than Dy = %d run on the wide-observation filter kernels" % cls._PLAIN_DY
         if Dy > cls._WOBS_MAX_DY:
@@ -191,6 +245,10 @@ class SVO:
         log["resampled"] (B,T) bool whether the sequence resampled there and log["filter"]["rs"] (T,B) int32 the same in the
         kernel's layout; log["Xs"] is the multinomial draw of every step whatever the decision (an equally weighted sample).
 
+        With FLAGS.missing_obs a NaN in `obs` is an entry that was not observed: the filter leaves its term out of the emission
+        density (psvo_filter_forward_wobs_missing), the proposal side reads 0 in its place, log_ZSMC bounds the log-density of
+        the observed entries and log["missing"] (B,T,Dy) bool is the mask; log["filter"] keeps its keys.
+
         With FLAGS.FFBS and autograd not recording (evaluation, trajectory saving, prediction) the marginal smoother runs
         behind the filter: log["Xs"] then holds particles resampled by the SMOOTHED weights (the filtered ones move to
         log["Xs_filter"]), and log["X_smooth_mean"] (B,T,Dx), log["ess_smooth"] (B,T), log["logW_smooth"] (T,B,N) and
@@ -215,6 +273,8 @@ class SVO:
         # (T, B, Dx, N) -> (batch_size, time, n_particles, Dx)
         log["Xs"] = filt["Xanc"].permute(1, 0, 3, 2)
         log["filter"] = filt
+        if self.missing_obs:
+            log["missing"] = self._missing              # (B, T, Dy) bool
         if filt.get("rs") is not None:
             log["ess"] = filt["ess"].transpose(0, 1)
             log["resampled"] = filt["rs"].transpose(0, 1) != 0
@@ -271,7 +331,7 @@ class SVO:
         with it the parameters' gradient accumulators, which remember the stream they were created on.  The next evaluation
         would reuse them: issued under a hipGraph capture on another stream the engine then synchronises that old stream
         into the capture, where it is never joined back (hipStreamEndCapture crashes on ROCm 7.2 instead of reporting it)."""
-        self._sigmas = self._m0 = self._sig0 = self._obs_TB = self._ov = None
+        self._sigmas = self._m0 = self._sig0 = self._obs_TB = self._ov = self._missing = None
         self.preprocessed_X0 = self.preprocessed_obs = None
 
     # hidden widths the kernels are instantiated for (template parameter H of csrc/*.hip)
@@ -404,11 +464,21 @@ class SVO:
         dev = obs.device
         noise = noise or {}
 
+        feat_TB = None
+        if self.missing_obs:
+            # the observed mask, once.  The kernel alone gets the NaN-carrying rows; the proposal side (q0, q2, the encoders, the X0
+            # feature) gets the observations with missing entries set to 0 -- the bound holds for any proposal
+            observed = torch.isfinite(obs)
+            self._missing = ~observed
+            obs_TB = obs.masked_fill(self._missing, float("nan")).transpose(0, 1).contiguous().float()
+            obs = obs.masked_fill(self._missing, 0.0)
+            feat_TB = obs.transpose(0, 1).contiguous().float()
         preprocessed_X0, preprocessed_obs = self.preprocess_obs(obs)
         both = model.use_bootstrap and model.use_2_q
-        obs_TB = obs.transpose(0, 1).contiguous().float()
+        if feat_TB is None:
+            obs_TB = feat_TB = obs.transpose(0, 1).contiguous().float()
         self._obs_TB = obs_TB                                                  # (reused by the backward simulation)
-        if not self.smooth_obs and both and obs.dtype == torch.float32:
+        if not self.smooth_obs and both and obs.dtype == torch.float32 and not self.missing_obs:
             # obs[:, 0] itself is the X0 feature (SVO.py:322-324, no X0_transformer in this wiring): row 0 of the
             # (T, B, Dy) copy the kernels need anyway is the same data, contiguous -- no second copy launch
             preprocessed_X0 = obs_TB[0]
@@ -426,7 +496,7 @@ class SVO:
             if preprocessed_obs is obs:
                 # raw observations as features (AESMC / IWAE / PSVO): rows in (T, B) order give mu2 in the kernels' layout
                 # directly -- no transposed copy of the output, none of its gradient
-                mu2 = self.q2.mean(obs_TB)                                     # (T, B, Dx)
+                mu2 = self.q2.mean(feat_TB)                                    # (T, B, Dx)
             else:
                 mu2 = self.q2.mean(preprocessed_obs).transpose(0, 1).contiguous()
             sig_q2 = self._sigma(self.q2)
@@ -445,6 +515,8 @@ class SVO:
         node = FilterFunction
         if self.wide_obs:
             node, desc._gbufs = FilterWobsFunction, None
+        if self.missing_obs:        # psvo_filter_forward_wobs_missing / _backward_wobs_missing at every 1 <= Dy <= 32
+            node, desc._gbufs = FilterWobsMissingFunction, None
         if self.resample_ess:
             # psvo_filter_forward_adaptive / psvo_filter_backward_adaptive: the decision per (step, sequence) is the kernel's
             # (wide observations, FLAGS.resample_ess_wide_obs: psvo_filter_forward_wobs_adaptive / _backward_wobs_adaptive)

@@ -404,6 +404,27 @@ class FilterWobsAdaptiveFunction(torch.autograd.Function):
         return _filter_backward(ctx, ops.filter_backward_wobs_adaptive, 7, dlse)
 
 
+class FilterWobsMissingFunction(torch.autograd.Function):
+    """psvo_filter_forward_wobs_missing / psvo_filter_backward_wobs_missing: the wide-observation filter with missing observations
+    (FLAGS.missing_obs; 1 <= Dy <= 32, one hidden layer, every emission form).  obs_TB (T,B,Dy) carries a NaN where nothing was
+    observed; the emission log-density then sums the observed entries only.
+
+    apply(...) takes FilterFunction's arguments and returns its outputs; only lse is differentiable (nothing runs behind this
+    filter under autograd).  The reverse uses psvo_mlp_wgrad_wobs for MLP_g at Dy >= 3 and the plain psvo_mlp_wgrad at Dy <= 2,
+    psvo_mlp_wgrad for MLP_q1 / MLP_f.  One stream, gradients returned as tensors."""
+
+    @staticmethod
+    def forward(ctx, desc, obs_TB, eps, u, idx_in, *t):
+        filt = _filter_forward(ctx, ops.filter_forward_wobs_missing, desc, obs_TB, eps, u, idx_in, t)
+        const = (filt["Fm"], filt["logW"], filt["X"], filt["Xanc"], filt["idx"])
+        ctx.mark_non_differentiable(*const)
+        return (filt["lse"],) + const
+
+    @staticmethod
+    def backward(ctx, dlse, *_):
+        return _filter_backward(ctx, ops.filter_backward_wobs_missing, 5, dlse)
+
+
 def _filter_node_of(Fm, ov):
     """the FilterFunction node that produced `Fm` in this evaluation (its ctx), if the overlap wiring is on: the
     backward-simulation node may launch that node's reverse kernel early.  (A downstream reference only: this node

@@ -17,6 +17,8 @@
 // H in {16,32,64} x one or two 16-wide output tiles (24).
 // The two filter kernels live in filter_wobs_impl.h, compiled twice: as they were, and in their adaptive-resampling form
 // (psvo_filter_forward_wobs_adaptive / psvo_filter_backward_wobs_adaptive: 18 forward and 18 reverse kernels more, no EXT form).
+// A third compilation is the missing-observation form (psvo_filter_forward_wobs_missing / psvo_filter_backward_wobs_missing: a NaN
+// in obs is an observation that was not made; 1 <= Dy <= 32; 18 forward and 18 reverse kernels more, no EXT form).
 #include "wobs_common.h"
 
 namespace psvo {
@@ -87,27 +89,36 @@ __device__ __forceinline__ const int32_t* arg_rs() {
 }
 static_assert(sizeof(BwdArgsAd) == sizeof(BwdArgs) + sizeof(const int32_t*), "rs is the last word of the adaptive arguments");
 
-// the kernels (filter_wobs_impl.h): the static pair, then the adaptive pair
+// the kernels (filter_wobs_impl.h): the static pair, then the adaptive pair, then the missing-observation pair
 #define PSVO_AD 0
 #include "filter_wobs_impl.h"
 #undef PSVO_AD
 #define PSVO_AD 1
 #include "filter_wobs_impl.h"
 #undef PSVO_AD
+#define PSVO_AD 0
+#define PSVO_MS 1
+#include "filter_wobs_impl.h"
+#undef PSVO_MS
+#undef PSVO_AD
 
+// (ms: the missing-observation form keeps one more row, the per-output constants, where the count form has its log-factorials)
 template <int DX, int H>
-static size_t fwd_lds_bytes(int NT, bool count) {
+static size_t fwd_lds_bytes(int NT, bool count, bool ms = false) {
     return sizeof(float) * (2 * MlpLds<DX, H, DX, 1>::kSize + GLds<DX, H>::kSize + 3 * kMaxDy + NT + 3 * DX * NT + 48 +
-                            (count ? 2 * kMaxDy : 0));
+                            (count ? 2 * kMaxDy : ms ? kMaxDy : 0));
 }
 
-template <int DX, int H, bool AD = false>
+template <int DX, int H, bool AD = false, bool MS = false>
 static int launch_fwd(const FwdArgsT<AD>& a, hipStream_t stream) {
     const int NT = (a.N + 63) & ~63;
     const bool count = a.emission == 2;
-    const size_t lds = fwd_lds_bytes<DX, H>(NT, count);
+    const size_t lds = fwd_lds_bytes<DX, H>(NT, count, MS);
     clear_hip_error();
-    if constexpr (AD) {
+    if constexpr (MS) {
+        if (count) hipLaunchKernelGGL((filter_fwd_wobs_ms_kernel<DX, H, true>), dim3(a.B), dim3(NT), lds, stream, a);
+        else hipLaunchKernelGGL((filter_fwd_wobs_ms_kernel<DX, H, false>), dim3(a.B), dim3(NT), lds, stream, a);
+    } else if constexpr (AD) {
         if (count) hipLaunchKernelGGL((filter_fwd_wobs_ad_kernel<DX, H, true>), dim3(a.B), dim3(NT), lds, stream, a);
         else hipLaunchKernelGGL((filter_fwd_wobs_ad_kernel<DX, H, false>), dim3(a.B), dim3(NT), lds, stream, a);
     } else {
@@ -128,13 +139,17 @@ static size_t bwd_lds_bytes(int NT, int Dy, bool bootstrap) {
                             + (size_t)(bootstrap ? DX : 2 * DX) * NT + (size_t)Dy * NT + 10 * DX);
 }
 
-template <int DX, int H, bool AD = false>
+template <int DX, int H, bool AD = false, bool MS = false>
 static int launch_bwd(const BwdArgsT<AD>& a, const BwdOut& o, hipStream_t stream) {
     const int NT = (a.N + 63) & ~63;
     const size_t lds = bwd_lds_bytes<DX, H>(NT, a.Dy, a.bootstrap != 0);
     clear_hip_error();
     const bool ext = a.dFm_ext || a.dlogW_ext;
-    if constexpr (AD) {     // (no EXT form: no backward simulation runs behind an adaptive filter)
+    if constexpr (MS) {     // (no EXT form: no backward simulation runs behind the missing-observation filter)
+        (void)ext;
+        if (a.emission == 2) hipLaunchKernelGGL((filter_bwd_wobs_ms_kernel<DX, H, false, true>), dim3(a.B), dim3(NT), lds, stream, a);
+        else hipLaunchKernelGGL((filter_bwd_wobs_ms_kernel<DX, H, false, false>), dim3(a.B), dim3(NT), lds, stream, a);
+    } else if constexpr (AD) {     // (no EXT form: no backward simulation runs behind an adaptive filter)
         (void)ext;
         if (a.emission == 2) hipLaunchKernelGGL((filter_bwd_wobs_ad_kernel<DX, H, false, true>), dim3(a.B), dim3(NT), lds, stream, a);
         else hipLaunchKernelGGL((filter_bwd_wobs_ad_kernel<DX, H, false, false>), dim3(a.B), dim3(NT), lds, stream, a);
@@ -155,8 +170,9 @@ static int launch_bwd(const BwdArgsT<AD>& a, const BwdOut& o, hipStream_t stream
 }
 
 // the envelope of the two filter entry points (host only): 3 <= Dy <= 32, one hidden layer, N <= 512; Dx and H by dispatch
-static bool filter_shape_ok(const psvo_desc* d) {
-    return d->Dy >= 3 && d->Dy <= kMaxDy && d->layers >= 0 && d->layers <= 1 && d->N <= 512 && d->B <= 65535;
+// (min_dy = 1: the missing-observation pair, which also serves the widths of the plain kernels)
+static bool filter_shape_ok(const psvo_desc* d, int min_dy = 3) {
+    return d->Dy >= min_dy && d->Dy <= kMaxDy && d->layers >= 0 && d->layers <= 1 && d->N <= 512 && d->B <= 65535;
 }
 
 template <class F>
@@ -374,13 +390,15 @@ static int launch_wgrad(const WgradArgs& a, int nblk, float* out, int accumulate
 }  // namespace wobs
 }  // namespace psvo
 
-// the checks and the launch behind psvo_filter_forward_wobs (ad == nullptr) and psvo_filter_forward_wobs_adaptive
+// the checks and the launch behind psvo_filter_forward_wobs (ad == nullptr), psvo_filter_forward_wobs_adaptive and
+// psvo_filter_forward_wobs_missing (ms)
 static int filter_forward_wobs_checked(const psvo_desc* desc, const psvo_mlp* q1, const psvo_mlp* f, const psvo_mlp* g,
                                        const float* sig_q1, const float* sig_q2, const float* sig_f, const float* sig_g,
                                        const float* mu2, const float* m0, const float* sig0, const float* fm0,
                                        const float* fsig0, const float* obs, const float* eps, const float* u,
                                        const int32_t* idx_in, float* X, float* Xanc, float* Fm, float* P1, float* logW,
-                                       int32_t* idx_out, float* lse, const psvo::wobs::FwdArgsAd* ad, void* stream) {
+                                       int32_t* idx_out, float* lse, const psvo::wobs::FwdArgsAd* ad, void* stream,
+                                       bool ms = false) {
     using namespace psvo;
     using namespace psvo::wobs;
     if (!desc_emission_ok(desc, 2)) return PSVO_ERR_UNSUPPORTED;
@@ -388,10 +406,11 @@ static int filter_forward_wobs_checked(const psvo_desc* desc, const psvo_mlp* q1
         !logW || !idx_out || !lse)
         return PSVO_ERR_INVALID;
     if (desc->B <= 0 || desc->T <= 0 || desc->N <= 0) return PSVO_ERR_INVALID;
+    if (ms && desc->T < 2) return PSVO_ERR_INVALID;
     if (desc->two_q && (!mu2 || !sig_q2)) return PSVO_ERR_INVALID;
     if (!desc->bootstrap && (!f || !sig_f)) return PSVO_ERR_INVALID;
     if (desc->resample && !u && !idx_in) return PSVO_ERR_INVALID;
-    if (!filter_shape_ok(desc)) return PSVO_ERR_UNSUPPORTED;
+    if (!filter_shape_ok(desc, ms ? 1 : 3)) return PSVO_ERR_UNSUPPORTED;
 
     FwdArgs a;
     a.B = desc->B; a.T = desc->T; a.N = desc->N; a.Dy = desc->Dy;
@@ -408,7 +427,18 @@ static int filter_forward_wobs_checked(const psvo_desc* desc, const psvo_mlp* q1
         aa.ess_frac = ad->ess_frac; aa.rs_in = ad->rs_in; aa.rs_out = ad->rs_out; aa.ess_out = ad->ess_out;
         return dispatch_dx_h(desc->Dx, desc->H, [&](auto dx, auto h) { return launch_fwd<dx(), h(), true>(aa, s); });
     }
+    if (ms) return dispatch_dx_h(desc->Dx, desc->H, [&](auto dx, auto h) { return launch_fwd<dx(), h(), false, true>(a, s); });
     return dispatch_dx_h(desc->Dx, desc->H, [&](auto dx, auto h) { return launch_fwd<dx(), h()>(a, s); });
+}
+
+extern "C" int psvo_filter_forward_wobs_missing(const psvo_desc* desc, const psvo_mlp* q1, const psvo_mlp* f, const psvo_mlp* g,
+                                                const float* sig_q1, const float* sig_q2, const float* sig_f, const float* sig_g,
+                                                const float* mu2, const float* m0, const float* sig0, const float* fm0,
+                                                const float* fsig0, const float* obs, const float* eps, const float* u,
+                                                const int32_t* idx_in, float* X, float* Xanc, float* Fm, float* P1, float* logW,
+                                                int32_t* idx_out, float* lse, void* stream) {
+    return filter_forward_wobs_checked(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, fm0, fsig0, obs, eps, u, idx_in,
+                                       X, Xanc, Fm, P1, logW, idx_out, lse, nullptr, stream, true);
 }
 
 extern "C" int psvo_filter_forward_wobs(const psvo_desc* desc, const psvo_mlp* q1, const psvo_mlp* f, const psvo_mlp* g,
@@ -441,7 +471,8 @@ extern "C" long long psvo_filter_wobs_ws_floats(int B, int T, int N, int Dx, int
     return (long long)B * (10 * Dx + Dy) + (long long)T * B * Dx * N;
 }
 
-// the checks and the launch behind psvo_filter_backward_wobs(_ext) (rs == nullptr) and psvo_filter_backward_wobs_adaptive
+// the checks and the launch behind psvo_filter_backward_wobs(_ext) (rs == nullptr), psvo_filter_backward_wobs_adaptive and
+// psvo_filter_backward_wobs_missing (ms)
 static int filter_backward_wobs_checked(
     const psvo_desc* desc, const psvo_mlp* q1, const psvo_mlp* f, const psvo_mlp* g, const float* sig_q1,
     const float* sig_q2, const float* sig_f, const float* sig_g, const float* mu2, const float* m0, const float* sig0,
@@ -449,7 +480,7 @@ static int filter_backward_wobs_checked(
     const float* P1, const float* logW, const float* lse, const int32_t* idx, const float* dlse, int nparts,
     const float* dFm_ext, const float* dlogW_ext, float* dP, float* dF, float* dG, float* dmu2, float* dm0, float* dfm0,
     float* dsig_q1, float* dsig_q2, float* dsig_f, float* dsig_g, float* dsig0, float* dfsig0, float* ws, const int32_t* rs,
-    void* stream) {
+    void* stream, bool ms = false) {
     using namespace psvo;
     using namespace psvo::wobs;
     if (!desc_emission_ok(desc, 2)) return PSVO_ERR_UNSUPPORTED;
@@ -457,11 +488,12 @@ static int filter_backward_wobs_checked(
         !lse || !dP || !dG || !dm0 || !dfm0 || !dsig_q1 || !dsig_q2 || !dsig_f || !dsig_g || !dsig0 || !dfsig0 || !ws)
         return PSVO_ERR_INVALID;
     if (desc->B <= 0 || desc->T <= 0 || desc->N <= 0) return PSVO_ERR_INVALID;
+    if (ms && desc->T < 2) return PSVO_ERR_INVALID;
     if (desc->two_q && (!mu2 || !sig_q2 || !dmu2)) return PSVO_ERR_INVALID;
     if (!desc->bootstrap && (!f || !sig_f || !P1 || !dF)) return PSVO_ERR_INVALID;
     if (desc->resample && !idx) return PSVO_ERR_INVALID;
     if ((dFm_ext || dlogW_ext) && nparts <= 0) return PSVO_ERR_INVALID;
-    if (!filter_shape_ok(desc)) return PSVO_ERR_UNSUPPORTED;
+    if (!filter_shape_ok(desc, ms ? 1 : 3)) return PSVO_ERR_UNSUPPORTED;
 
     BwdArgs a;
     a.B = desc->B; a.T = desc->T; a.N = desc->N; a.Dy = desc->Dy;
@@ -482,7 +514,20 @@ static int filter_backward_wobs_checked(
         aa.rs = rs;
         return dispatch_dx_h(desc->Dx, desc->H, [&](auto dx, auto h) { return launch_bwd<dx(), h(), true>(aa, o, s); });
     }
+    if (ms) return dispatch_dx_h(desc->Dx, desc->H, [&](auto dx, auto h) { return launch_bwd<dx(), h(), false, true>(a, o, s); });
     return dispatch_dx_h(desc->Dx, desc->H, [&](auto dx, auto h) { return launch_bwd<dx(), h()>(a, o, s); });
+}
+
+extern "C" int psvo_filter_backward_wobs_missing(
+    const psvo_desc* desc, const psvo_mlp* q1, const psvo_mlp* f, const psvo_mlp* g, const float* sig_q1,
+    const float* sig_q2, const float* sig_f, const float* sig_g, const float* mu2, const float* m0, const float* sig0,
+    const float* fm0, const float* fsig0, const float* obs, const float* eps, const float* X, const float* Fm,
+    const float* P1, const float* logW, const float* lse, const int32_t* idx, const float* dlse, float* dP, float* dF,
+    float* dG, float* dmu2, float* dm0, float* dfm0, float* dsig_q1, float* dsig_q2, float* dsig_f, float* dsig_g,
+    float* dsig0, float* dfsig0, float* ws, void* stream) {
+    return filter_backward_wobs_checked(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, fm0, fsig0, obs, eps, X, Fm,
+                                        P1, logW, lse, idx, dlse, 0, nullptr, nullptr, dP, dF, dG, dmu2, dm0, dfm0, dsig_q1,
+                                        dsig_q2, dsig_f, dsig_g, dsig0, dfsig0, ws, nullptr, stream, true);
 }
 
 extern "C" int psvo_filter_backward_wobs_ext(

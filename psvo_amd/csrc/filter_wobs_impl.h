@@ -1,6 +1,7 @@
-// The two wide-observation filter kernels.  filter_wobs.hip includes this file twice: PSVO_AD = 0 gives filter_fwd_wobs_kernel
-// and filter_bwd_wobs_kernel, text and code as they always were; PSVO_AD = 1 gives filter_fwd_wobs_ad_kernel and
-// filter_bwd_wobs_ad_kernel, the kernels of psvo_filter_forward_wobs_adaptive / psvo_filter_backward_wobs_adaptive.
+// The two wide-observation filter kernels.  filter_wobs.hip includes this file three times: PSVO_AD = 0 (and PSVO_MS = 0) gives
+// filter_fwd_wobs_kernel and filter_bwd_wobs_kernel, text and code as they always were; PSVO_AD = 1 gives filter_fwd_wobs_ad_kernel
+// and filter_bwd_wobs_ad_kernel, the kernels of psvo_filter_forward_wobs_adaptive / psvo_filter_backward_wobs_adaptive; PSVO_MS = 1
+// gives the missing-observation pair (below).
 //
 // Adaptive resampling (filter_fwd_impl.h / filter_bwd_impl.h have the definition; it is the same here): the draw is made and
 // written every step, and the sequence INHERITS it only when ESS = (sum w)^2 / sum w^2 has fallen below ess_frac N (or when
@@ -8,11 +9,23 @@
 // adds the same LDS words in the same order, and the decision only feeds selects.  Reverse: the decisions rs (T,B) are constants
 // like the indices, read as scalars; the ancestor of particle n at step t is rs[t-1] ? idx[t-1][n] : n, and the term of the
 // carried normalised weight (`!a.resample` in the static kernel) is applied at exactly the steps with rs[t] == 0.
+//
+// Missing observations (PSVO_MS = 1, PSVO_AD = 0: filter_fwd_wobs_ms_kernel / filter_bwd_wobs_ms_kernel, the kernels of
+// psvo_filter_forward_wobs_missing / psvo_filter_backward_wobs_missing): a NaN in obs is an observation that was not made, and its
+// term is left out of log g.  y_t[e] is a broadcast, so o_e = (y == y) is the same in every lane; it only feeds selects.  The
+// normalising constant of the Gaussian forms is no longer one number per launch: c_e = -(log sig_g[e] + 1/2 log 2 pi) is an LDS row
+// beside 1 / sig_g and a step adds the c_e of what it observed.  Reverse: the d G row of a missing entry is written as 0 (the
+// weight gradient and bwd_input read it back) and the d sig_g column receives nothing.  Same argument blocks as the static pair.
 #if PSVO_AD
 #define PSVO_WOBS_FWD_KERNEL filter_fwd_wobs_ad_kernel
 #define PSVO_WOBS_BWD_KERNEL filter_bwd_wobs_ad_kernel
 #define PSVO_WOBS_FWD_ARGS FwdArgsAd
 #define PSVO_WOBS_BWD_ARGS BwdArgsAd
+#elif PSVO_MS
+#define PSVO_WOBS_FWD_KERNEL filter_fwd_wobs_ms_kernel
+#define PSVO_WOBS_BWD_KERNEL filter_bwd_wobs_ms_kernel
+#define PSVO_WOBS_FWD_ARGS FwdArgs
+#define PSVO_WOBS_BWD_ARGS BwdArgs
 #else
 #define PSVO_WOBS_FWD_KERNEL filter_fwd_wobs_kernel
 #define PSVO_WOBS_BWD_KERNEL filter_bwd_wobs_kernel
@@ -49,6 +62,9 @@ __global__ void __launch_bounds__(512) PSVO_WOBS_FWD_KERNEL(const PSVO_WOBS_FWD_
     float* sf = sp + DX * NT;           // [DX][NT] staged MLP_f(X_t) (unused when bootstrap)
     float* red = sf + DX * NT;          // 48 floats scratch
     float* lfbuf = red + 48;            // CNT: [2][kMaxDy] log Gamma(y + 1) of the rows in ybuf
+#if PSVO_MS
+    float* cg = red + 48;               // !CNT (no lfbuf then): [kMaxDy] -(log sig_g + 1/2 log 2 pi), the constant of one term
+#endif
 
     MQ::load(wq1, a.q1, tid, NT);
     if (!a.bootstrap) MQ::load(wf, a.f, tid, NT);
@@ -56,6 +72,9 @@ __global__ void __launch_bounds__(512) PSVO_WOBS_FWD_KERNEL(const PSVO_WOBS_FWD_
     const float* wfm = a.bootstrap ? wq1 : wf;
     if (tid < Dy) {
         if constexpr (!CNT) isg[tid] = 1.f / a.sig_g[tid];
+#if PSVO_MS
+        if constexpr (!CNT) cg[tid] = -(logf(a.sig_g[tid]) + kHalfLog2Pi);
+#endif
         const float y0 = a.obs[(size_t)b * Dy + tid];
         ybuf[tid] = y0;
         if constexpr (CNT) lfbuf[tid] = log_factorial(y0);
@@ -70,10 +89,12 @@ __global__ void __launch_bounds__(512) PSVO_WOBS_FWD_KERNEL(const PSVO_WOBS_FWD_
         s0[d] = a.sig0[d];
         fs0[d] = a.fsig0[d];
     }
+#if !PSVO_MS
     float lg = -Dy * kHalfLog2Pi;
     if constexpr (!CNT) {
         for (int e = 0; e < Dy; ++e) lg -= logf(a.sig_g[e]);
     }
+#endif
     const StepK<DX> K0 = make_stepk<DX>(s0, sq2, fs0, a.two_q != 0);
     const StepK<DX> K1 = make_stepk<DX>(sq1, sq2, sfv, a.two_q != 0);
     const float neg_logN = -logf((float)N);
@@ -144,6 +165,30 @@ __global__ void __launch_bounds__(512) PSVO_WOBS_FWD_KERNEL(const PSVO_WOBS_FWD_
             float h[H];
             MG::hidden(wg_t, x, h);
             float acc = 0.f;
+#if PSVO_MS
+            // observed terms only, constant included, in the order e = 0 .. Dy - 1; nothing observed: exactly 0
+            if constexpr (CNT) {
+                const float* lf_t = lfbuf + (t & 1) * kMaxDy + zo;
+#pragma unroll 1
+                for (int e = 0; e < Dy; ++e) {
+                    const float y = y_t[e];
+                    const float term = count_term(y, MG::out(wg_t, e, h)) - lf_t[e];
+                    acc += (y == y) ? term : 0.f;
+                }
+            } else {
+                const float* cg_t = cg + zo;
+#pragma unroll 1
+                for (int e = 0; e < Dy; ++e) {
+                    float gm = MG::out(wg_t, e, h);
+                    if (a.emission) gm = emis_mean(gm);
+                    const float y = y_t[e];
+                    const float z = (y - gm) * isg[e];
+                    const float term = fmaf(-0.5f * z, z, cg_t[e]);
+                    acc += (y == y) ? term : 0.f;
+                }
+            }
+            g_lp = acc;
+#else
             if constexpr (CNT) {     // y log lam - lam - log Gamma(y + 1), one term per output
                 const float* lf_t = lfbuf + (t & 1) * kMaxDy + zo;
 #pragma unroll 1
@@ -159,6 +204,7 @@ __global__ void __launch_bounds__(512) PSVO_WOBS_FWD_KERNEL(const PSVO_WOBS_FWD_
                 }
                 g_lp = fmaf(-0.5f, acc, lg);
             }
+#endif
         }
         float lw = f_lp + g_lp - q_lp + lnw;
         if (!valid) lw = ninf;
@@ -444,6 +490,30 @@ __global__ void __launch_bounds__(512) PSVO_WOBS_BWD_KERNEL(const PSVO_WOBS_BWD_
         {
             float h[H];
             MG::hidden(wg_t, x, h);
+#if PSVO_MS
+            // a missing entry: its d G row is written as 0 (it is read back), its d sig_g column gets nothing
+            if constexpr (CNT) {
+#pragma unroll 1
+                for (int o = 0; o < Dy; ++o) {
+                    const float y = y_t[o];
+                    const float dr = dlw * count_dterm(y, MG::out(wg_t, o, h));
+                    if (valid) a.dG[(tb * Dy + o) * N + n] = (y == y) ? dr : 0.f;
+                }
+            } else {
+#pragma unroll 1
+                for (int o = 0; o < Dy; ++o) {
+                    float gm = MG::out(wg_t, o, h);
+                    float dmean = 1.f;
+                    if (a.emission) { dmean = emis_dmean(gm); gm = emis_mean(gm); }
+                    const float is = isg[o];
+                    const float y = y_t[o];
+                    const bool ob = (y == y);
+                    const float z = (y - gm) * is;
+                    sg[o * NT + tid] += ob ? dlw * (z * z - 1.f) * is : 0.f;
+                    if (valid) a.dG[(tb * Dy + o) * N + n] = ob ? dlw * z * is * dmean : 0.f;
+                }
+            }
+#else
             if constexpr (CNT) {
 #pragma unroll 1
                 for (int o = 0; o < Dy; ++o) {
@@ -462,6 +532,7 @@ __global__ void __launch_bounds__(512) PSVO_WOBS_BWD_KERNEL(const PSVO_WOBS_BWD_
                     if (valid) a.dG[(tb * Dy + o) * N + n] = dlw * z * is * dmean;
                 }
             }
+#endif
         }
         // (second walk over the outputs: the lane reads its own d G rows back -- H partial sums beside the H activations
         //  would not fit the 256 registers of a 512-lane workgroup)

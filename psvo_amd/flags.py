@@ -91,6 +91,10 @@ DEFINITIONS = [
     # pushes the cloud's mean through f): off by default, evaluation only; every objective
     ("particle_forecast", bool, False, "evaluate the k-step predictive mean, variance and log-density of the whole particle cloud"),
     ("forecast_noise", bool, True, "--particle_forecast: apply transition noise to every particle (off: noise-free propagation)"),
+    # missing observations (not in the reference's registry, whose data are dense): a NaN in the observations is an entry that was
+    # not observed; its term is left out of the emission log-density.  Filter objectives (SVO, AESMC, IWAE), 1 <= Dy <= 32
+    ("missing_obs", bool, False, "SVO / AESMC / IWAE: a NaN observation is missing, the ELBO bounds the density of the observed entries"),
+    ("missing_rate", float, 0.0, "--generateTrainingData --missing_obs: knock entries out independently with this probability, in [0, 1)"),
     # printing and data saving (runner_flag.py:131-153)
     ("print_freq", int, 1, "frequency to evaluate testing loss & other metrics and save results"),
     ("save_trajectory", bool, True, "whether to save hidden trajectories during training"),

@@ -149,6 +149,7 @@ class SSM(nn.Module):
         self.use_bootstrap, self.use_2_q = FLAGS.use_bootstrap, FLAGS.use_2_q
         self.poisson_emission = FLAGS.poisson_emission
         self.count_emission = bool(getattr(FLAGS, "count_emission", False))      # (not in the reference)
+        self.missing_obs = bool(getattr(FLAGS, "missing_obs", False))            # (not in the reference) NaN = not observed
         self.X0_use_separate_RNN, self.use_stack_rnn = FLAGS.X0_use_separate_RNN, FLAGS.use_stack_rnn
         self.PSVO, self.PSVOwR, self.SVO = FLAGS.PSVO, getattr(FLAGS, "PSVOwR", False), FLAGS.SVO
         self.BSim_use_single_RNN = FLAGS.BSim_use_single_RNN

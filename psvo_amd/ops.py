@@ -270,6 +270,13 @@ def filter_forward_wobs_adaptive(*args, ess_frac, rs_in=None, **kw):
     return filter_forward(*args, entry="psvo_filter_forward_wobs_adaptive", ess_frac=ess_frac, rs_in=rs_in, **kw)
 
 
+def filter_forward_wobs_missing(*args, **kw):
+    """psvo_filter_forward_wobs_missing: filter_forward_wobs where a NaN in obs (T,B,Dy) is an observation that was not made -- its
+    term is left out of the emission log-density (1 <= Dy <= 32, one hidden layer, every emission form); arguments, outputs and
+    layouts of filter_forward."""
+    return filter_forward(*args, entry="psvo_filter_forward_wobs_missing", **kw)
+
+
 # The plain backward simulations (PSVO: bsim_*, PSVOwR: bsimwr_*) take the same inputs ahead of their own and their reverse
 # launches write the same rows: what the four wrappers share is below; the argument lists mirror include/psvo_hip.h in each.
 def _bsim_structs(d, f, g, q1_inv):
@@ -518,13 +525,15 @@ def split_mlp_grad(g, Din, H, Dout, layers=1):
 
 def filter_backward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, fm0, fsig0, obs, eps, filt,
                     dlse=None, dFm=None, dlogW=None, gbufs=None, before_wgrad=None, defer_wgrad=False, wobs=False,
-                    nparts=None, ext=False, adaptive=False):
+                    nparts=None, ext=False, adaptive=False, missing=False):
     """psvo_filter_backward + psvo_mlp_wgrad (adaptive: psvo_filter_backward_adaptive, following the decisions filt["rs"]).
     `filt` = forward outputs.  dFm (T,B,Dx,N) / dlogW (T,B,N)
     are upstream gradients (or None); with nparts > 1 they come in parts, (T,B,nparts,Dx,N) / (T,B,nparts,N), which the
     kernel adds in part order.  Returns a dict of gradients.
     wobs: psvo_filter_backward_wobs + psvo_mlp_wgrad_wobs for MLP_g (wide observations); with dFm / dlogW -- a backward
-    simulation ran behind the wide filter -- or with ext=True, psvo_filter_backward_wobs_ext."""
+    simulation ran behind the wide filter -- or with ext=True, psvo_filter_backward_wobs_ext.
+    missing (with wobs): psvo_filter_backward_wobs_missing, 1 <= Dy <= 32, dlse only; MLP_g's weight gradient from the d G rows is
+    psvo_mlp_wgrad_wobs for Dy >= 3 and the plain psvo_mlp_wgrad for Dy <= 2."""
     lib = _lib.load()
     B, T, N, Dx, Dy, H = desc.B, desc.T, desc.N, desc.Dx, desc.Dy, desc.H
     dev = eps.device
@@ -542,6 +551,12 @@ def filter_backward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0,
     nparts = (parts[0] if parts else 1) if (dFm is not None or dlogW is not None) else 0
     ext = bool(ext or nparts)
     name = ("psvo_filter_backward_wobs_ext" if ext else "psvo_filter_backward_wobs") if wobs else "psvo_filter_backward"
+    wide_g = wobs                # MLP_g's weight gradient on psvo_mlp_wgrad_wobs
+    if missing:
+        if not wobs or adaptive or ext:
+            raise ValueError("filter_backward: missing observations run on the wide-observation route (wobs=True) with the upstream "
+                             "gradient dlse only, resampling at every step or never (no adaptive form, no gradients of Fm / logW)")
+        name, wide_g = "psvo_filter_backward_wobs_missing", Dy >= 3
     decisions = ()
     if adaptive:
         if wobs and adaptive != "wobs":     # (the wide adaptive route is filter_backward_wobs_adaptive)
@@ -580,9 +595,9 @@ def filter_backward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0,
             for t in (filt["X"], out["dG"]):
                 t.record_stream(g_stream)
             with launch_on(g_stream):
-                out["gg"] = mlp_wgrad(filt["X"], out["dG"], g, Dx, H, Dy, grad=gb[2], wobs=wobs)
+                out["gg"] = mlp_wgrad(filt["X"], out["dG"], g, Dx, H, Dy, grad=gb[2], wobs=wide_g)
         else:
-            out["gg"] = mlp_wgrad(filt["X"], out["dG"], g, Dx, H, Dy, grad=gb[2], wobs=wobs)
+            out["gg"] = mlp_wgrad(filt["X"], out["dG"], g, Dx, H, Dy, grad=gb[2], wobs=wide_g)
     if defer_wgrad:          # the caller issues them later (out["_wgrad"]()), e.g. after other writers of the same slices
         out["_wgrad"] = wgrad
         return out
@@ -602,6 +617,12 @@ def filter_backward_wobs_adaptive(*args, **kw):
     """psvo_filter_backward_wobs_adaptive + psvo_mlp_wgrad (q1, f) + psvo_mlp_wgrad_wobs (g): the reverse of
     filter_forward_wobs_adaptive, following the decisions filt["rs"]; arguments and result of filter_backward (dlse only)."""
     return filter_backward(*args, wobs=True, adaptive="wobs", **kw)
+
+
+def filter_backward_wobs_missing(*args, **kw):
+    """psvo_filter_backward_wobs_missing + psvo_mlp_wgrad (q1, f; g at Dy <= 2) + psvo_mlp_wgrad_wobs (g at Dy >= 3): the reverse
+    of filter_forward_wobs_missing; arguments and result of filter_backward (dlse only)."""
+    return filter_backward(*args, wobs=True, missing=True, **kw)
 
 
 # ---------------------------------------------------------------------------------------------

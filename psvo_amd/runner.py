@@ -27,9 +27,9 @@ from .SMC.AESMC import AESMC
 from .SMC.IWAE import IWAE
 from .SMC.PSVO import PSVO
 from .SMC.PSVOwR import PSVOwR
-from .SMC.SVO import SVO, check_resample_ess
+from .SMC.SVO import SVO, check_missing_obs, check_resample_ess
 from .trainer import trainer
-from .utils.data_generator import PoissonEmitter, count_loading, generate_dataset
+from .utils.data_generator import PoissonEmitter, count_loading, generate_dataset, knock_out
 from .utils.data_loader import load_data
 
 # flag name -> objective class, in the reference's order of precedence (src/runner.py:70-81)
@@ -47,32 +47,39 @@ def _device():
 def _dataset(FLAGS):
     """(hidden_train, hidden_test, obs_train, obs_test); updates the flags that describe the data"""
     count = bool(getattr(FLAGS, "count_emission", False))
+    missing = bool(getattr(FLAGS, "missing_obs", False))
     if FLAGS.generateTrainingData:
         # (count emission: Poisson counts of the FHN latent through a fixed loading, data_generator.count_loading)
         g = PoissonEmitter(*count_loading(FLAGS.Dy, 2)) if count else None
         data = generate_dataset(FLAGS.n_train, FLAGS.n_test, FLAGS.time, model="fhn", Dy=FLAGS.Dy, g=g, lb=-2.5, ub=2.5)
+        rate = float(getattr(FLAGS, "missing_rate", 0.0) or 0.0)
+        if missing and rate > 0.0:      # (after generation: training set, then test set)
+            data = data[:2] + (knock_out(data[2], rate), knock_out(data[3], rate))
     else:
         data = load_data(FLAGS.datadir + FLAGS.datadict, FLAGS.Dx, FLAGS.isPython2, FLAGS.q_uses_true_X)
         obs_train, obs_test = data[2], data[3]
         FLAGS.n_train, FLAGS.n_test, FLAGS.time = obs_train.shape[0], obs_test.shape[0], obs_test.shape[1]
     if count:
-        check_counts(data[2], "obs_train")
-        check_counts(data[3], "obs_test")
+        check_counts(data[2], "obs_train", missing_obs=missing)
+        check_counts(data[3], "obs_test", missing_obs=missing)
     FLAGS.MSE_steps = min(FLAGS.MSE_steps, FLAGS.time - 1)
     FLAGS.saving_num = min(FLAGS.saving_num, FLAGS.n_train, FLAGS.n_test)
     return data
 
 
-def check_counts(obs, name="obs"):
+def check_counts(obs, name="obs", missing_obs=False):
     """--count_emission scores observations with a Poisson law: they must be finite, non-negative and integer-valued
-    (checked once, on the host, when the data set is prepared; the kernels do not check)"""
+    (checked once, on the host, when the data set is prepared; the kernels do not check).  missing_obs (--missing_obs): a NaN is
+    an entry that was not observed and passes; +-inf, negative and fractional values are refused as before."""
     a = np.asarray(obs, dtype=np.float64)
-    if not np.isfinite(a).all():
+    bad = ~np.isfinite(a) & ~np.isnan(a) if missing_obs else ~np.isfinite(a)
+    if bad.any():
         raise ValueError("--count_emission: %s holds non-finite values (first at index %s)"
-                         % (name, tuple(int(i) for i in np.argwhere(~np.isfinite(a))[0])))
-    if a.size and a.min() < 0:
-        raise ValueError("--count_emission: %s holds negative values (minimum %r); counts are >= 0" % (name, float(a.min())))
-    frac = a != np.floor(a)
+                         % (name, tuple(int(i) for i in np.argwhere(bad)[0])))
+    seen = ~np.isnan(a)                 # (everything, unless missing_obs let NaN through)
+    if seen.any() and a[seen].min() < 0:
+        raise ValueError("--count_emission: %s holds negative values (minimum %r); counts are >= 0" % (name, float(a[seen].min())))
+    frac = seen & (a != np.floor(a))
     if frac.any():
         raise ValueError("--count_emission: %s holds non-integer values (first: %r at index %s); counts are integers"
                          % (name, float(a[frac][0]), tuple(int(i) for i in np.argwhere(frac)[0])))
@@ -98,6 +105,10 @@ def main(FLAGS):
                        backward_simulation=bool(FLAGS.PSVO or FLAGS.PSVOwR), output_cov=bool(FLAGS.output_cov), Dy=FLAGS.Dy,
                        wide_obs=bool(getattr(FLAGS, "resample_ess_wide_obs", False)),
                        layers=[FLAGS.q1_layers, FLAGS.g_layers] + ([] if FLAGS.use_bootstrap else [FLAGS.f_layers]))
+    check_missing_obs(bool(getattr(FLAGS, "missing_obs", False)), missing_rate=getattr(FLAGS, "missing_rate", 0.0),
+                      backward_simulation=bool(FLAGS.PSVO or FLAGS.PSVOwR), resample_ess=getattr(FLAGS, "resample_ess", 0.0),
+                      particle_forecast=bool(getattr(FLAGS, "particle_forecast", False)), output_cov=bool(FLAGS.output_cov),
+                      Dy=FLAGS.Dy, layers=[FLAGS.q1_layers, FLAGS.g_layers] + ([] if FLAGS.use_bootstrap else [FLAGS.f_layers]))
     if FLAGS.use_2_q:
         FLAGS.q_uses_true_X = False
     device = _device()

@@ -36,6 +36,11 @@ log-density over the (sequence, origin) pairs whose target lies inside the data,
 calibration mean((y - y_mean)^2 / y_var) (about 1 when calibrated) are printed and go into metric_<iter>.p as forecast_lpd_<split>,
 forecast_R_square_<split>, forecast_calibration_<split>; y_hat_<epoch>.p gains y_mean and y_var of the saved sequences.
 Training steps are untouched.
+
+Missing observations (FLAGS.missing_obs, off by default; SVO / AESMC / IWAE): a NaN observation was not made; training and evaluation
+run the missing-observation filter kernels, and the ELBO bounds the log-density of the observed entries.  The k-step R-square takes
+residuals and the centring mean over observed targets only; at every evaluation the share of missing entries of each split is
+printed and goes into metric_<iter>.p as missing_share_<split>.  y_hat at k = 0 is the model's imputation and is saved as before.
 """
 import math
 import os
@@ -60,9 +65,19 @@ def _shuffle(*arrays):
     return tuple(a[perm] for a in arrays)
 
 
-def _r_square(y_hat, y):
+def _r_square(y_hat, y, missing_obs=False):
     """1 - SS_res / SS_tot with the total sum of squares taken around the mean over the evaluation set (axis 0), per
-    time step and feature -- the reference's definition (trainer.py:325-329)."""
+    time step and feature -- the reference's definition (trainer.py:325-329).
+    missing_obs (FLAGS.missing_obs): a NaN target was not observed -- residuals and the centring mean are taken over the observed
+    targets only (a (time step, feature) that no sequence observed contributes nothing to either sum)."""
+    if missing_obs:
+        seen = ~np.isnan(y)
+        n = seen.sum(axis=0, keepdims=True)
+        y0 = np.where(seen, y, 0.0)
+        mean = y0.sum(axis=0, keepdims=True) / np.maximum(n, 1)
+        resid = np.where(seen, y_hat - y0, 0.0)
+        centred = np.where(seen, y0 - mean, 0.0)
+        return 1.0 - float(np.square(resid).sum()) / float(np.square(centred).sum())
     resid = y_hat - y
     centred = y - y.mean(axis=0, keepdims=True)
     return 1.0 - float(np.square(resid).sum()) / float(np.square(centred).sum())
@@ -296,6 +311,7 @@ class trainer:
         ffbsi = bool(getattr(self.SMC, "FFBSi", False))
         adaptive = bool(getattr(self.SMC, "resample_ess", 0.0))
         forecast = bool(getattr(self.SMC, "forecast", False))
+        missing = bool(getattr(self.SMC, "missing_obs", False))
         fetches = (["log_ZSMC", "y_hat", "y"] + (["ess", "resampled"] if adaptive else []) + (["ess_smooth"] if ffbs else [])
                    + (["path_distinct"] if ffbsi else []))
         if forecast:       # (last, so that the fetches ahead of them keep their places)
@@ -317,6 +333,8 @@ class trainer:
                 ess["ffbs_ess_mean_" + split], ess["ffbs_ess_min_" + split] = float(np.mean(rest[0])), float(np.min(rest[0]))
             if ffbsi:
                 ess["ffbsi_distinct_mean_" + split], ess["ffbsi_distinct_min_" + split] = float(np.mean(rest[-1])), float(np.min(rest[-1]))
+            if missing:     # the share of entries of this split that were not observed
+                ess["missing_share_" + split] = float(np.mean(np.isnan(np.asarray(obs, dtype=np.float64))))
             m["log_ZSMC_" + split] = np.mean(elbos)
             m["R_square_" + split] = self.evaluate_R_square(y_hat, y)
 
@@ -325,6 +343,9 @@ class trainer:
             print("iter", iter_num + 1)
             print("Train log_ZSMC: {:>7.3f}, valid log_ZSMC: {:>7.3f}".format(m["log_ZSMC_train"], m["log_ZSMC_test"]))
             print("Train, Valid k-step Rsq:\n", m["R_square_train"], "\n", m["R_square_test"])
+            if missing:
+                print("missing observations: share of entries not observed train {:.1%}, valid {:.1%}"
+                      .format(ess["missing_share_train"], ess["missing_share_test"]))
             if adaptive:
                 print("adaptive resampling (ESS < {:g} N): resampled steps train {:.1%}, valid {:.1%}; ESS / N mean / min: train "
                       "{:.3f} / {:.3f}, valid {:.3f} / {:.3f}"
@@ -474,4 +495,5 @@ class trainer:
 
     def evaluate_R_square(self, y_hat, y):
         """R-square of the k-step-ahead predictions, k = 0 .. MSE_steps (trainer.py:322-335): one number per horizon"""
-        return np.array([_r_square(np.asarray(p), np.asarray(t)) for p, t in zip(y_hat, y)])
+        missing = bool(getattr(getattr(self, "SMC", None), "missing_obs", False))
+        return np.array([_r_square(np.asarray(p), np.asarray(t), missing) for p, t in zip(y_hat, y)])

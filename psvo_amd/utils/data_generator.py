@@ -103,6 +103,16 @@ def generate_hidden_obs(time, Dx, Dy, x_0, f, g):
     return X, Y
 
 
+def knock_out(obs, rate):
+    """a float copy of `obs` with every entry replaced by NaN independently with probability `rate` (FLAGS.missing_rate): one
+    uniform per entry from numpy's GLOBAL generator, like everything else here, so FLAGS.seed reproduces the mask; rate 0 draws
+    nothing and leaves no NaN"""
+    out = np.array(obs, dtype=float)
+    if rate > 0.0:
+        out[np.random.uniform(size=out.shape) < rate] = np.nan
+    return out
+
+
 def generate_dataset(n_train, n_test, time, model="lorenz", Dy=1, Di=1, f=None, g=None, x_0_in=None, lb=-2.5, ub=2.5):
     if model not in _MODELS:
         raise ValueError("Unknown model {}".format(model))
