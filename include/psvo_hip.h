@@ -331,6 +331,23 @@ int psvo_particle_forecast(const psvo_desc* desc, int K,
                            float* ymean, float* yvar, float* xmean, float* lpd, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Particle forecast on missing observations (added within ABI 6: purely additive).  psvo_particle_forecast with one change of
+ * meaning: a NaN in obs[t+k,b,e] is an entry that was not observed (the rule of psvo_filter_forward_wobs_missing), and
+ *     lpd[k,t,b] = logsumexp_n(log w_n + sum_{e observed} term_e(x^(k)_n))
+ * with the terms added in the order e = 0 .. Dy-1: -1/2 z_e^2 - log sig_g[e] - 1/2 log 2 pi (emissions 0 and 1, the constant with
+ * its term) or y_e log mu_e - mu_e - log Gamma(y_e + 1) (emission 2).  The choice is a select on a broadcast; a NaN never reaches
+ * a sum.  lpd is exactly 0 where t + k >= T and where the target row has nothing observed.  ymean, yvar and xmean do not read
+ * obs and equal psvo_particle_forecast's bit for bit.  With every entry observed lpd equals psvo_particle_forecast's bit for
+ * bit for emission 2 and to rounding for emissions 0 and 1 (the sum groups differently).  No atomics, the same fold order: two
+ * calls give bit-identical outputs.  Arguments, envelope and refusals are those of psvo_particle_forecast, which itself still
+ * answers NaN for a NaN target.
+ * ------------------------------------------------------------------------------------------- */
+int psvo_particle_forecast_missing(const psvo_desc* desc, int K,
+                           const psvo_mlp* f, const psvo_mlp* g, const float* sig_f, const float* sig_g,
+                           const float* X, const float* logW, const float* obs, const float* eps,
+                           float* ymean, float* yvar, float* xmean, float* lpd, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Backward simulation with proposal, STATE-DEPENDENT diagonal scales (FLAGS.output_cov and FLAGS.diag_cov; see
  * psvo_filter_forward_cov).  Same loop and outputs as psvo_bsim_forward (PSVO.backward_simulation_w_proposal, reference
  * src/SMC/PSVO.py:69-203); differences:
@@ -836,6 +853,45 @@ int psvo_filter_backward_wobs_missing(const psvo_desc* desc,
                               float* dP, float* dF, float* dG, float* dmu2, float* dm0, float* dfm0,
                               float* dsig_q1, float* dsig_q2, float* dsig_f, float* dsig_g, float* dsig0, float* dfsig0,
                               float* ws, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Adaptive resampling on missing observations (added within ABI 6: purely additive).  The intersection of the two sections
+ * above and nothing new: psvo_filter_forward_wobs_missing / psvo_filter_backward_wobs_missing -- a NaN in obs is left out of
+ * log g, a step with nothing observed has log g = 0 exactly -- with the decision of psvo_filter_forward_wobs_adaptive, word for
+ * word: ESS[t,b] = (sum_n w_n)^2 / sum_n w_n^2 taken from the weights as the observed terms left them, the sequence inherits the
+ * draw iff !(ESS[t,b] >= ess_frac * N) or as rs_in says, and the draw is made and written at every step.  A step with nothing
+ * observed adds no information: in a bootstrap filter without q2 such a step behind a resampled one has ESS = N and is kept.
+ *  forward:  the arguments of psvo_filter_forward_wobs_adaptive.  With rs_in all ones the count emission's outputs equal
+ *            psvo_filter_forward_wobs_missing's bit for bit; with no NaN in obs they equal psvo_filter_forward_wobs_adaptive's
+ *            bit for bit for the count emission and to rounding for the Gaussian forms (the constant travels with each term).
+ *  reverse:  the arguments of psvo_filter_backward_wobs_adaptive; the decisions are constants; a missing entry writes dG = 0
+ *            and adds nothing to dsig_g.  Upstream gradient dlse only.  One fixed order for every sum and no float atomics:
+ *            two runs are bit-identical.  ws: psvo_filter_wobs_ws_floats(B, T, N, Dx, Dy) floats, unchanged.  The weight
+ *            gradient of MLP_g is psvo_mlp_wgrad_wobs for Dy >= 3 and the plain psvo_mlp_wgrad for Dy <= 2.
+ *  Refused before a device is touched, the adaptive contract first: ess_frac not > 0 (NaN included), desc->resample == 0, NULL
+ *  rs_out / ess_out / rs -- PSVO_ERR_INVALID; then the missing pair's envelope with its statuses: 1 <= Dy <= 32, Dx in {2,3,4},
+ *  H in {16,32,64}, N <= 512, one hidden layer, emission 0 / 1 / 2 (else PSVO_ERR_UNSUPPORTED); a missing required pointer,
+ *  B <= 0, T < 2 or N <= 0 is PSVO_ERR_INVALID.  psvo_filter_forward_wobs_adaptive still refuses Dy < 3.
+ * ------------------------------------------------------------------------------------------- */
+int psvo_filter_forward_wobs_missing_adaptive(const psvo_desc* desc,
+                             const psvo_mlp* q1, const psvo_mlp* f, const psvo_mlp* g,
+                             const float* sig_q1, const float* sig_q2, const float* sig_f, const float* sig_g,
+                             const float* mu2,
+                             const float* m0, const float* sig0, const float* fm0, const float* fsig0,
+                             const float* obs, const float* eps, const float* u, const int32_t* idx_in,
+                             float* X, float* Xanc, float* Fm, float* P1, float* logW, int32_t* idx_out,
+                             float* lse, float ess_frac, const int32_t* rs_in, int32_t* rs_out, float* ess_out, void* stream);
+int psvo_filter_backward_wobs_missing_adaptive(const psvo_desc* desc,
+                              const psvo_mlp* q1, const psvo_mlp* f, const psvo_mlp* g,
+                              const float* sig_q1, const float* sig_q2, const float* sig_f, const float* sig_g,
+                              const float* mu2,
+                              const float* m0, const float* sig0, const float* fm0, const float* fsig0,
+                              const float* obs, const float* eps,
+                              const float* X, const float* Fm, const float* P1, const float* logW, const float* lse,
+                              const int32_t* idx, const float* dlse,
+                              float* dP, float* dF, float* dG, float* dmu2, float* dm0, float* dfm0,
+                              float* dsig_q1, float* dsig_q2, float* dsig_f, float* dsig_g, float* dsig0, float* dfsig0,
+                              float* ws, const int32_t* rs, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * PSVO on wide observations: the backward simulation with proposal and its reverse pass for 3 <= Dy <= 32

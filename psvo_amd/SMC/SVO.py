@@ -10,16 +10,18 @@ import torch
 
 from .. import ops
 from ..autograd import (FilterAdaptiveFunction, FilterCovFunction, FilterFunction, FilterWobsAdaptiveFunction,
-                        FilterWobsFunction, FilterWobsMissingFunction)
+                        FilterWobsFunction, FilterWobsMissingAdaptiveFunction, FilterWobsMissingFunction)
 
 
 def check_resample_ess(raw, never_resamples=False, backward_simulation=False, output_cov=False, Dy=1, plain_dy=2,
-                       wide_obs=False, layers=(), wobs_max_dy=32):
+                       wide_obs=False, layers=(), wobs_max_dy=32, missing_obs=False):
     """--resample_ess as a float: 0.0 = off, else the ESS threshold tau as a fraction of N, 0 < tau <= 1.  ValueError, naming
     the limit, for a threshold outside that range and for everything the adaptive kernels do not cover (runner.main calls this
     on the flags before it touches a device, SVO.__init__ on the model it is given).  `wide_obs`: --resample_ess_wide_obs, the
     adaptive wide-observation kernels for plain_dy < Dy <= wobs_max_dy (`layers`: the hidden layers of the per-particle MLPs,
-    one each there); no effect at Dy <= plain_dy or with the threshold off."""
+    one each there); no effect at Dy <= plain_dy or with the threshold off.  `missing_obs`: --missing_obs with
+    --resample_ess_missing_obs, the adaptive missing-observation kernels at every width check_missing_obs accepts (which also
+    checks width and depth there); `wide_obs` is not needed and has no effect then."""
     tau = float(0.0 if raw is None else raw)
     if tau == 0.0:
         return 0.0
@@ -35,6 +37,8 @@ def check_resample_ess(raw, never_resamples=False, backward_simulation=False, ou
     if output_cov:
         raise ValueError("--resample_ess with output_cov: the state-dependent-scale kernels (psvo_filter_forward_cov) have "
                          "no adaptive form; adaptive resampling takes state-independent scales only")
+    if missing_obs:
+        return tau
     if Dy > plain_dy and not wide_obs:
         raise ValueError("--resample_ess with Dy = %d: without --resample_ess_wide_obs the adaptive kernels are the plain filter "
                          "kernels, which take Dy <= %d; pass --resample_ess_wide_obs for the adaptive wide-observation kernels "
@@ -52,11 +56,15 @@ def check_resample_ess(raw, never_resamples=False, backward_simulation=False, ou
 
 
 def check_missing_obs(on, missing_rate=0.0, backward_simulation=False, resample_ess=0.0, particle_forecast=False,
-                      output_cov=False, Dy=1, layers=(), wobs_max_dy=32):
+                      output_cov=False, Dy=1, layers=(), wobs_max_dy=32, resample_ess_missing_obs=False,
+                      particle_forecast_missing_obs=False):
     """--missing_obs (a NaN observation is an entry that was not observed) as a bool.  ValueError, naming the limit, for
     everything the missing-observation kernels (psvo_filter_forward_wobs_missing) do not cover and for a --missing_rate that is
     no probability or has nothing to act on (runner.main calls this on the flags before it touches a device, SVO.__init__ on the
-    model it is given).  `layers`: the hidden layers of the per-particle MLPs, one each."""
+    model it is given).  `layers`: the hidden layers of the per-particle MLPs, one each.  `resample_ess_missing_obs`
+    (--resample_ess_missing_obs): --resample_ess runs on psvo_filter_forward_wobs_missing_adaptive; `particle_forecast_missing_obs`
+    (--particle_forecast_missing_obs): --particle_forecast runs on psvo_particle_forecast_missing.  Neither has an effect without
+    --missing_obs, and without them the two combinations stay refused."""
     rate = float(0.0 if missing_rate is None else missing_rate)
     if not (0.0 <= rate < 1.0):
         raise ValueError("--missing_rate = %r: the probability of knocking an entry out lies in [0, 1)" % (missing_rate,))
@@ -69,10 +77,10 @@ def check_missing_obs(on, missing_rate=0.0, backward_simulation=False, resample_
     if backward_simulation:
         raise ValueError("--missing_obs with --PSVO / --PSVOwR: %s; the backward-simulation kernels evaluate the emission too and "
                          "have no missing-observation form" % limit)
-    if float(resample_ess or 0.0) != 0.0:
+    if float(resample_ess or 0.0) != 0.0 and not resample_ess_missing_obs:
         raise ValueError("--missing_obs with --resample_ess: %s, which resamples at every step (or never); the adaptive kernels "
                          "have no missing-observation form" % limit)
-    if particle_forecast:
+    if particle_forecast and not particle_forecast_missing_obs:
         raise ValueError("--missing_obs with --particle_forecast: the forecast's predictive log-density (lpd) scores whole "
                          "observation rows; it has no missing-observation form")
     if output_cov:
@@ -139,6 +147,9 @@ class SVO:
         # psvo_particle_forecast); FLAGS.forecast_noise off = every particle propagated without transition noise
         self.forecast = self._route_forecast(model, bool(getattr(FLAGS, "particle_forecast", False)))
         self.forecast_noise = bool(getattr(FLAGS, "forecast_noise", True))
+        # ... on gappy data (FLAGS.particle_forecast_missing_obs; _route_missing_obs refused the combination without it):
+        # psvo_particle_forecast_missing scores the observed entries of every target row
+        self.forecast_missing = bool(self.missing_obs and self.forecast)
 
         self.name = name
         self.generator = None        # torch.Generator on the compute device; None = global RNG
@@ -156,7 +167,9 @@ class SVO:
                                  resample_ess=getattr(FLAGS, "resample_ess", 0.0),
                                  particle_forecast=bool(getattr(FLAGS, "particle_forecast", False)),
                                  output_cov=bool(getattr(model, "output_cov", False)), Dy=getattr(model, "Dy", cls._PLAIN_DY),
-                                 layers=[t.Dhs for t in dict.fromkeys(trans)], wobs_max_dy=cls._WOBS_MAX_DY)
+                                 layers=[t.Dhs for t in dict.fromkeys(trans)], wobs_max_dy=cls._WOBS_MAX_DY,
+                                 resample_ess_missing_obs=bool(getattr(FLAGS, "resample_ess_missing_obs", False)),
+                                 particle_forecast_missing_obs=bool(getattr(FLAGS, "particle_forecast_missing_obs", False)))
 
     @classmethod
     def _route_wide_obs(cls, model, bsim_wide_obs=False, missing_obs=False):
@@ -231,7 +244,9 @@ class SVO:
                                   backward_simulation=cls.uses_backward_simulation,
                                   output_cov=bool(getattr(model, "output_cov", False)), Dy=getattr(model, "Dy", cls._PLAIN_DY),
                                   plain_dy=cls._PLAIN_DY, wide_obs=bool(getattr(FLAGS, "resample_ess_wide_obs", False)),
-                                  layers=[t.Dhs for t in dict.fromkeys(trans)], wobs_max_dy=cls._WOBS_MAX_DY)
+                                  layers=[t.Dhs for t in dict.fromkeys(trans)], wobs_max_dy=cls._WOBS_MAX_DY,
+                                  missing_obs=bool((getattr(model, "missing_obs", False) or getattr(FLAGS, "missing_obs", False))
+                                                   and getattr(FLAGS, "resample_ess_missing_obs", False)))
 
     # ------------------------------------------------------------------------------------------
     def get_log_ZSMC(self, obs, hidden, noise=None):
@@ -520,8 +535,11 @@ class SVO:
         if self.resample_ess:
             # psvo_filter_forward_adaptive / psvo_filter_backward_adaptive: the decision per (step, sequence) is the kernel's
             # (wide observations, FLAGS.resample_ess_wide_obs: psvo_filter_forward_wobs_adaptive / _backward_wobs_adaptive)
+            # (missing observations, FLAGS.resample_ess_missing_obs: psvo_filter_forward_wobs_missing_adaptive and its reverse)
             desc._gbufs = None
             node = FilterWobsAdaptiveFunction if self.wide_obs else FilterAdaptiveFunction
+            if self.missing_obs:
+                node = FilterWobsMissingAdaptiveFunction
             lse, Fm, logW, X, Xanc, idx, rs, ess = node.apply(
                 desc, obs_TB, eps, u, idx_in, self.resample_ess, noise.get("rs_f"),
                 *first, self._sigma(self.q1), sig_q2, sig_f, self._sigma(self.g), mu2, m0, sig0, fm0, fsig0, *extra)
@@ -645,7 +663,12 @@ class SVO:
 
         Returns {"y_mean", "y_var": (B,T,n_steps+1,Dy), "x_mean": (B,T,n_steps+1,Dx), "lpd": (B,T,n_steps+1) the predictive
         log-density of obs[b, t+k] (0 where t + k >= T), "valid": (T,n_steps+1) bool, t + k < T, "forecast": the kernel's
-        output dict in its own layout}.  `n_step_prediction` beside it stays the reference's metric."""
+        output dict in its own layout}.  `n_step_prediction` beside it stays the reference's metric.
+
+        With FLAGS.missing_obs and FLAGS.particle_forecast_missing_obs (psvo_particle_forecast_missing) a non-finite entry of `obs`
+        was not observed: "lpd" sums the observed entries of the target row and is 0 where it has none, "n_observed" (B,T,n_steps+1)
+        int is the number of observed entries of obs[b, t+k] (0 outside the data) and "valid" narrows to (B,T,n_steps+1): the
+        target lies inside the data and has at least one observed entry."""
         if torch.is_grad_enabled():
             raise ValueError("particle_forecast has no gradient: call it under torch.no_grad() (evaluation only)")
         self._route_forecast(self.model)
@@ -658,6 +681,10 @@ class SVO:
         model = self.model
         X = _c(hidden.permute(1, 0, 3, 2))                 # (T,B,Dx,N): no copy when `hidden` is a view of a kernel-layout tensor
         obs_TB = obs.transpose(0, 1).contiguous().float()
+        missing = bool(getattr(self, "forecast_missing", False))
+        if missing:                                        # (as SMC does: whatever is not finite was not observed)
+            observed = torch.isfinite(obs_TB)              # (T,B,Dy)
+            obs_TB = obs_TB.masked_fill(~observed, float("nan"))
         noise = noise or {}
         eps = noise.get("eps_p")
         if eps is None and self.forecast_noise and K > 0:
@@ -665,11 +692,19 @@ class SVO:
         f_tran, f_dist = (model.q1_tran, self.q1) if model.use_bootstrap else (model.f_tran, self.f)
         desc = ops.make_desc(B, T, N, 1, Dx, model.Dy, H, bootstrap=model.use_bootstrap, emission=self._emission_code(), layers=1)
         fc = ops.particle_forecast(desc, K, _c(self._mlp_params(f_tran)), _c(self._mlp_params(model.g_tran)),
-                                   _c(self._sigma(f_dist)), _c(self._sigma(self.g)), X, obs=obs_TB, eps=eps)
+                                   _c(self._sigma(f_dist)), _c(self._sigma(self.g)), X, obs=obs_TB, eps=eps,
+                                   **({"missing": True} if missing else {}))      # (without the flag: the call as it always was)
         t = torch.arange(T, device=X.device)
-        return {"y_mean": fc["ymean"].permute(2, 1, 0, 3), "y_var": fc["yvar"].permute(2, 1, 0, 3),
-                "x_mean": fc["xmean"].permute(2, 1, 0, 3), "lpd": fc["lpd"].permute(2, 1, 0),
-                "valid": (t[:, None] + torch.arange(K + 1, device=X.device)[None, :]) < T, "forecast": fc}
+        out = {"y_mean": fc["ymean"].permute(2, 1, 0, 3), "y_var": fc["yvar"].permute(2, 1, 0, 3),
+               "x_mean": fc["xmean"].permute(2, 1, 0, 3), "lpd": fc["lpd"].permute(2, 1, 0),
+               "valid": (t[:, None] + torch.arange(K + 1, device=X.device)[None, :]) < T, "forecast": fc}
+        if missing:
+            tk = t[:, None] + torch.arange(K + 1, device=X.device)[None, :]              # (T,K+1) target step
+            cnt = observed.sum(-1).to(torch.int32)                                       # (T,B)
+            n_obs = cnt[tk.clamp(max=T - 1)] * out["valid"][:, :, None].to(torch.int32)  # (T,K+1,B)
+            out["n_observed"] = n_obs.permute(2, 0, 1)
+            out["valid"] = out["n_observed"] > 0
+        return out
 
     def get_nextX(self, X):
         """SVO.py:406-409 (quiver plots)."""

@@ -61,6 +61,9 @@ SIGNATURES = {
     "psvo_filter_backward_wobs_adaptive": (ctypes.c_int, [_DESC, _MLP, _MLP, _MLP] + [_P] * 31 + [_P, _P]),
     "psvo_filter_forward_wobs_missing": (ctypes.c_int, [_DESC, _MLP, _MLP, _MLP] + [_P] * 20 + [_P]),
     "psvo_filter_backward_wobs_missing": (ctypes.c_int, [_DESC, _MLP, _MLP, _MLP] + [_P] * 31 + [_P]),
+    "psvo_filter_forward_wobs_missing_adaptive": (ctypes.c_int, [_DESC, _MLP, _MLP, _MLP] + [_P] * 20
+                                                  + [ctypes.c_float, _P, _P, _P] + [_P]),
+    "psvo_filter_backward_wobs_missing_adaptive": (ctypes.c_int, [_DESC, _MLP, _MLP, _MLP] + [_P] * 31 + [_P, _P]),
     "psvo_bsim_forward_wobs": (ctypes.c_int, [_DESC] + [_P] * 4 + [_MLP, _MLP, _MLP] + [_P] * 22 + [_P]),
     "psvo_bsim_wobs_blocks": (ctypes.c_int, [ctypes.c_int] * 2),
     "psvo_bsim_wobs_ws_floats": (ctypes.c_longlong, [ctypes.c_int] * 6),
@@ -73,6 +76,7 @@ SIGNATURES = {
     "psvo_ffbs_smooth": (ctypes.c_int, [_DESC] + [_P] * 12 + [_P]),
     "psvo_ffbs_sample": (ctypes.c_int, [_DESC] + [_P] * 11 + [_P]),
     "psvo_particle_forecast": (ctypes.c_int, [_DESC, ctypes.c_int, _MLP, _MLP] + [_P] * 10 + [_P]),
+    "psvo_particle_forecast_missing": (ctypes.c_int, [_DESC, ctypes.c_int, _MLP, _MLP] + [_P] * 10 + [_P]),
     "psvo_filter_backward_cov": (ctypes.c_int, [_DESC, _MLP, _MLP, _MLP] + [_P] * 39 + [_P]),
     "psvo_bsim_forward_cov": (ctypes.c_int, [_DESC] + [_P] * 4 + [_MLP, _MLP, _MLP] + [_P] * 23 + [_P]),
     "psvo_bsim_backward_cov": (ctypes.c_int, [_DESC] + [_P] * 4 + [_MLP, _MLP, _MLP] + [_P] * 38 + [_P]),

@@ -425,6 +425,25 @@ class FilterWobsMissingFunction(torch.autograd.Function):
         return _filter_backward(ctx, ops.filter_backward_wobs_missing, 5, dlse)
 
 
+class FilterWobsMissingAdaptiveFunction(torch.autograd.Function):
+    """psvo_filter_forward_wobs_missing_adaptive / psvo_filter_backward_wobs_missing_adaptive: FilterWobsMissingFunction resampling
+    a sequence only where its effective sample size has fallen below ess_frac N (FLAGS.missing_obs with FLAGS.resample_ess and
+    FLAGS.resample_ess_missing_obs; 1 <= Dy <= 32, one hidden layer, every emission form).
+
+    apply(...) takes FilterAdaptiveFunction's arguments and returns its outputs; only lse is differentiable.  The weight
+    gradients are FilterWobsMissingFunction's.  One stream, gradients returned as tensors."""
+
+    @staticmethod
+    def forward(ctx, desc, obs_TB, eps, u, idx_in, ess_frac, rs_in, *t):
+        filt = _filter_forward(ctx, ops.filter_forward_wobs_missing_adaptive, desc, obs_TB, eps, u, idx_in, t, ess_frac=ess_frac,
+                               rs_in=rs_in)
+        return _adaptive_outputs(ctx, filt)
+
+    @staticmethod
+    def backward(ctx, dlse, *_):
+        return _filter_backward(ctx, ops.filter_backward_wobs_missing_adaptive, 7, dlse)
+
+
 def _filter_node_of(Fm, ov):
     """the FilterFunction node that produced `Fm` in this evaluation (its ctx), if the overlap wiring is on: the
     backward-simulation node may launch that node's reverse kernel early.  (A downstream reference only: this node

@@ -19,6 +19,8 @@
 // (psvo_filter_forward_wobs_adaptive / psvo_filter_backward_wobs_adaptive: 18 forward and 18 reverse kernels more, no EXT form).
 // A third compilation is the missing-observation form (psvo_filter_forward_wobs_missing / psvo_filter_backward_wobs_missing: a NaN
 // in obs is an observation that was not made; 1 <= Dy <= 32; 18 forward and 18 reverse kernels more, no EXT form).
+// A fourth is both at once (psvo_filter_forward_wobs_missing_adaptive / psvo_filter_backward_wobs_missing_adaptive: the adaptive
+// argument blocks, the missing-observation form's LDS; 1 <= Dy <= 32; 18 forward and 18 reverse kernels more, no EXT form).
 #include "wobs_common.h"
 
 namespace psvo {
@@ -89,7 +91,8 @@ __device__ __forceinline__ const int32_t* arg_rs() {
 }
 static_assert(sizeof(BwdArgsAd) == sizeof(BwdArgs) + sizeof(const int32_t*), "rs is the last word of the adaptive arguments");
 
-// the kernels (filter_wobs_impl.h): the static pair, then the adaptive pair, then the missing-observation pair
+// the kernels (filter_wobs_impl.h): the static pair, then the adaptive pair, then the missing-observation pair, then the
+// adaptive missing-observation pair
 #define PSVO_AD 0
 #include "filter_wobs_impl.h"
 #undef PSVO_AD
@@ -98,6 +101,9 @@ static_assert(sizeof(BwdArgsAd) == sizeof(BwdArgs) + sizeof(const int32_t*), "rs
 #undef PSVO_AD
 #define PSVO_AD 0
 #define PSVO_MS 1
+#include "filter_wobs_impl.h"
+#undef PSVO_AD
+#define PSVO_AD 1
 #include "filter_wobs_impl.h"
 #undef PSVO_MS
 #undef PSVO_AD
@@ -115,7 +121,10 @@ static int launch_fwd(const FwdArgsT<AD>& a, hipStream_t stream) {
     const bool count = a.emission == 2;
     const size_t lds = fwd_lds_bytes<DX, H>(NT, count, MS);
     clear_hip_error();
-    if constexpr (MS) {
+    if constexpr (MS && AD) {     // (the missing-observation form's LDS: the adaptive form's red[40 + wave] lies ahead of the cg row)
+        if (count) hipLaunchKernelGGL((filter_fwd_wobs_msad_kernel<DX, H, true>), dim3(a.B), dim3(NT), lds, stream, a);
+        else hipLaunchKernelGGL((filter_fwd_wobs_msad_kernel<DX, H, false>), dim3(a.B), dim3(NT), lds, stream, a);
+    } else if constexpr (MS) {
         if (count) hipLaunchKernelGGL((filter_fwd_wobs_ms_kernel<DX, H, true>), dim3(a.B), dim3(NT), lds, stream, a);
         else hipLaunchKernelGGL((filter_fwd_wobs_ms_kernel<DX, H, false>), dim3(a.B), dim3(NT), lds, stream, a);
     } else if constexpr (AD) {
@@ -145,7 +154,11 @@ static int launch_bwd(const BwdArgsT<AD>& a, const BwdOut& o, hipStream_t stream
     const size_t lds = bwd_lds_bytes<DX, H>(NT, a.Dy, a.bootstrap != 0);
     clear_hip_error();
     const bool ext = a.dFm_ext || a.dlogW_ext;
-    if constexpr (MS) {     // (no EXT form: no backward simulation runs behind the missing-observation filter)
+    if constexpr (MS && AD) {     // (no EXT form, as for either twin)
+        (void)ext;
+        if (a.emission == 2) hipLaunchKernelGGL((filter_bwd_wobs_msad_kernel<DX, H, false, true>), dim3(a.B), dim3(NT), lds, stream, a);
+        else hipLaunchKernelGGL((filter_bwd_wobs_msad_kernel<DX, H, false, false>), dim3(a.B), dim3(NT), lds, stream, a);
+    } else if constexpr (MS) {     // (no EXT form: no backward simulation runs behind the missing-observation filter)
         (void)ext;
         if (a.emission == 2) hipLaunchKernelGGL((filter_bwd_wobs_ms_kernel<DX, H, false, true>), dim3(a.B), dim3(NT), lds, stream, a);
         else hipLaunchKernelGGL((filter_bwd_wobs_ms_kernel<DX, H, false, false>), dim3(a.B), dim3(NT), lds, stream, a);
@@ -390,8 +403,8 @@ static int launch_wgrad(const WgradArgs& a, int nblk, float* out, int accumulate
 }  // namespace wobs
 }  // namespace psvo
 
-// the checks and the launch behind psvo_filter_forward_wobs (ad == nullptr), psvo_filter_forward_wobs_adaptive and
-// psvo_filter_forward_wobs_missing (ms)
+// the checks and the launch behind psvo_filter_forward_wobs (ad == nullptr), psvo_filter_forward_wobs_adaptive,
+// psvo_filter_forward_wobs_missing (ms) and psvo_filter_forward_wobs_missing_adaptive (ad and ms)
 static int filter_forward_wobs_checked(const psvo_desc* desc, const psvo_mlp* q1, const psvo_mlp* f, const psvo_mlp* g,
                                        const float* sig_q1, const float* sig_q2, const float* sig_f, const float* sig_g,
                                        const float* mu2, const float* m0, const float* sig0, const float* fm0,
@@ -425,6 +438,7 @@ static int filter_forward_wobs_checked(const psvo_desc* desc, const psvo_mlp* q1
         FwdArgsAd aa;
         static_cast<FwdArgs&>(aa) = a;
         aa.ess_frac = ad->ess_frac; aa.rs_in = ad->rs_in; aa.rs_out = ad->rs_out; aa.ess_out = ad->ess_out;
+        if (ms) return dispatch_dx_h(desc->Dx, desc->H, [&](auto dx, auto h) { return launch_fwd<dx(), h(), true, true>(aa, s); });
         return dispatch_dx_h(desc->Dx, desc->H, [&](auto dx, auto h) { return launch_fwd<dx(), h(), true>(aa, s); });
     }
     if (ms) return dispatch_dx_h(desc->Dx, desc->H, [&](auto dx, auto h) { return launch_fwd<dx(), h(), false, true>(a, s); });
@@ -467,12 +481,28 @@ extern "C" int psvo_filter_forward_wobs_adaptive(const psvo_desc* desc, const ps
                                        X, Xanc, Fm, P1, logW, idx_out, lse, &ad, stream);
 }
 
+extern "C" int psvo_filter_forward_wobs_missing_adaptive(const psvo_desc* desc, const psvo_mlp* q1, const psvo_mlp* f,
+                                                         const psvo_mlp* g, const float* sig_q1, const float* sig_q2,
+                                                         const float* sig_f, const float* sig_g, const float* mu2,
+                                                         const float* m0, const float* sig0, const float* fm0,
+                                                         const float* fsig0, const float* obs, const float* eps, const float* u,
+                                                         const int32_t* idx_in, float* X, float* Xanc, float* Fm, float* P1,
+                                                         float* logW, int32_t* idx_out, float* lse, float ess_frac,
+                                                         const int32_t* rs_in, int32_t* rs_out, float* ess_out, void* stream) {
+    // the adaptive contract first, as psvo_filter_forward_wobs_adaptive has it; then the missing pair's envelope
+    if (!desc || !(ess_frac > 0.f) || !desc->resample || !rs_out || !ess_out) return PSVO_ERR_INVALID;
+    psvo::wobs::FwdArgsAd ad;
+    ad.ess_frac = ess_frac; ad.rs_in = rs_in; ad.rs_out = rs_out; ad.ess_out = ess_out;
+    return filter_forward_wobs_checked(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, fm0, fsig0, obs, eps, u, idx_in,
+                                       X, Xanc, Fm, P1, logW, idx_out, lse, &ad, stream, true);
+}
+
 extern "C" long long psvo_filter_wobs_ws_floats(int B, int T, int N, int Dx, int Dy) {
     return (long long)B * (10 * Dx + Dy) + (long long)T * B * Dx * N;
 }
 
-// the checks and the launch behind psvo_filter_backward_wobs(_ext) (rs == nullptr), psvo_filter_backward_wobs_adaptive and
-// psvo_filter_backward_wobs_missing (ms)
+// the checks and the launch behind psvo_filter_backward_wobs(_ext) (rs == nullptr), psvo_filter_backward_wobs_adaptive,
+// psvo_filter_backward_wobs_missing (ms) and psvo_filter_backward_wobs_missing_adaptive (rs and ms)
 static int filter_backward_wobs_checked(
     const psvo_desc* desc, const psvo_mlp* q1, const psvo_mlp* f, const psvo_mlp* g, const float* sig_q1,
     const float* sig_q2, const float* sig_f, const float* sig_g, const float* mu2, const float* m0, const float* sig0,
@@ -512,6 +542,7 @@ static int filter_backward_wobs_checked(
         BwdArgsAd aa;
         static_cast<BwdArgs&>(aa) = a;
         aa.rs = rs;
+        if (ms) return dispatch_dx_h(desc->Dx, desc->H, [&](auto dx, auto h) { return launch_bwd<dx(), h(), true, true>(aa, o, s); });
         return dispatch_dx_h(desc->Dx, desc->H, [&](auto dx, auto h) { return launch_bwd<dx(), h(), true>(aa, o, s); });
     }
     if (ms) return dispatch_dx_h(desc->Dx, desc->H, [&](auto dx, auto h) { return launch_bwd<dx(), h(), false, true>(a, o, s); });
@@ -554,6 +585,20 @@ extern "C" int psvo_filter_backward_wobs_adaptive(
     return filter_backward_wobs_checked(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, fm0, fsig0, obs, eps, X, Fm,
                                         P1, logW, lse, idx, dlse, 0, nullptr, nullptr, dP, dF, dG, dmu2, dm0, dfm0, dsig_q1,
                                         dsig_q2, dsig_f, dsig_g, dsig0, dfsig0, ws, rs, stream);
+}
+
+extern "C" int psvo_filter_backward_wobs_missing_adaptive(
+    const psvo_desc* desc, const psvo_mlp* q1, const psvo_mlp* f, const psvo_mlp* g, const float* sig_q1,
+    const float* sig_q2, const float* sig_f, const float* sig_g, const float* mu2, const float* m0, const float* sig0,
+    const float* fm0, const float* fsig0, const float* obs, const float* eps, const float* X, const float* Fm,
+    const float* P1, const float* logW, const float* lse, const int32_t* idx, const float* dlse, float* dP, float* dF,
+    float* dG, float* dmu2, float* dm0, float* dfm0, float* dsig_q1, float* dsig_q2, float* dsig_f, float* dsig_g,
+    float* dsig0, float* dfsig0, float* ws, const int32_t* rs, void* stream) {
+    // the adaptive contract first, as psvo_filter_backward_wobs_adaptive has it; then the missing pair's envelope
+    if (!desc || !desc->resample || !rs) return PSVO_ERR_INVALID;
+    return filter_backward_wobs_checked(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, fm0, fsig0, obs, eps, X, Fm,
+                                        P1, logW, lse, idx, dlse, 0, nullptr, nullptr, dP, dF, dG, dmu2, dm0, dfm0, dsig_q1,
+                                        dsig_q2, dsig_f, dsig_g, dsig0, dfsig0, ws, rs, stream, true);
 }
 
 extern "C" int psvo_filter_backward_wobs(

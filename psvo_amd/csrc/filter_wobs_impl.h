@@ -1,7 +1,7 @@
-// The two wide-observation filter kernels.  filter_wobs.hip includes this file three times: PSVO_AD = 0 (and PSVO_MS = 0) gives
+// The two wide-observation filter kernels.  filter_wobs.hip includes this file four times: PSVO_AD = 0 (and PSVO_MS = 0) gives
 // filter_fwd_wobs_kernel and filter_bwd_wobs_kernel, text and code as they always were; PSVO_AD = 1 gives filter_fwd_wobs_ad_kernel
 // and filter_bwd_wobs_ad_kernel, the kernels of psvo_filter_forward_wobs_adaptive / psvo_filter_backward_wobs_adaptive; PSVO_MS = 1
-// gives the missing-observation pair (below).
+// gives the missing-observation pair, and both together the adaptive missing-observation pair (below).
 //
 // Adaptive resampling (filter_fwd_impl.h / filter_bwd_impl.h have the definition; it is the same here): the draw is made and
 // written every step, and the sequence INHERITS it only when ESS = (sum w)^2 / sum w^2 has fallen below ess_frac N (or when
@@ -16,7 +16,19 @@
 // normalising constant of the Gaussian forms is no longer one number per launch: c_e = -(log sig_g[e] + 1/2 log 2 pi) is an LDS row
 // beside 1 / sig_g and a step adds the c_e of what it observed.  Reverse: the d G row of a missing entry is written as 0 (the
 // weight gradient and bwd_input read it back) and the d sig_g column receives nothing.  Same argument blocks as the static pair.
-#if PSVO_AD
+//
+// Both (PSVO_AD = 1 and PSVO_MS = 1: filter_fwd_wobs_msad_kernel / filter_bwd_wobs_msad_kernel, the kernels of
+// psvo_filter_forward_wobs_missing_adaptive / psvo_filter_backward_wobs_missing_adaptive): the two sets of lines do not touch each
+// other, and the semantics are the intersection of the two definitions above -- ESS is taken from the weights as the observed
+// terms left them, so a step with nothing observed (log g = 0 exactly) that follows a resampled step of a bootstrap filter
+// without q2 has ESS = N and is kept.  The adaptive argument blocks; the LDS of the missing-observation form: the adaptive form's
+// red[40 + wave], wave <= 7, ends at red[47], the last of the 48 floats ahead of the cg row (the log-factorial rows for counts).
+#if PSVO_AD && PSVO_MS
+#define PSVO_WOBS_FWD_KERNEL filter_fwd_wobs_msad_kernel
+#define PSVO_WOBS_BWD_KERNEL filter_bwd_wobs_msad_kernel
+#define PSVO_WOBS_FWD_ARGS FwdArgsAd
+#define PSVO_WOBS_BWD_ARGS BwdArgsAd
+#elif PSVO_AD
 #define PSVO_WOBS_FWD_KERNEL filter_fwd_wobs_ad_kernel
 #define PSVO_WOBS_BWD_KERNEL filter_bwd_wobs_ad_kernel
 #define PSVO_WOBS_FWD_ARGS FwdArgsAd

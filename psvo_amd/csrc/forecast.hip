@@ -38,7 +38,12 @@ struct ForecastArgs {
 
 // EMIS: psvo_desc.emission as a compile-time form, so that the Gaussian instantiations carry neither the softplus nor the fp64
 // log-factorial of the count emission
-template <int DX, int H, int EMIS>
+// MS: the missing-observation form (psvo_particle_forecast_missing), compile-time too, so that the MS = false instantiations keep
+// their code and registers.  A NaN in the target row is an entry that was not observed: y[e] is a broadcast, so y == y is the
+// same in every lane and only feeds a select; the log-density adds the observed terms in the order e = 0 .. Dy - 1, each Gaussian
+// term with its own constant c_e = -(log sig_g[e] + 1/2 log 2 pi) from one more LDS row (the filter's rule, filter_wobs_impl.h),
+// and a target row with nothing observed gives lpd = 0 exactly.  ymean, yvar and xmean do not read obs.
+template <int DX, int H, int EMIS, bool MS>
 __global__ void __launch_bounds__(512) forecast_kernel(const ForecastArgs a) {
     using MF = MlpLds<DX, H, DX, 1>;
     using MG = wobs::GLds<DX, H>;
@@ -48,6 +53,7 @@ __global__ void __launch_bounds__(512) forecast_kernel(const ForecastArgs a) {
     __shared__ float ybuf[2][kFcOrigins][kMaxDy];               // observation rows of horizon k (k & 1) and k + 1
     __shared__ float lfbuf[2][kFcOrigins][kMaxDy];              // count emission: log Gamma(y + 1) of the rows in ybuf
     __shared__ float red[2][kFcWaves][kFcSlot];                 // per-wave partial sums of horizon k (k & 1)
+    __shared__ float cg[kMaxDy];                                // MS, Gaussian forms: the constant of one term (else unused)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, NT = blockDim.x;
     const int N = a.N, Dy = a.Dy, K = a.K;
@@ -73,6 +79,9 @@ __global__ void __launch_bounds__(512) forecast_kernel(const ForecastArgs a) {
     MF::load(wf, a.f, tid, NT);
     MG::load(wg, a.g, Dy, tid, NT);
     if (tid < Dy) isg[tid] = emission == 2 ? 0.f : 1.f / a.sig_g[tid];
+    if constexpr (MS && EMIS != 2) {
+        if (tid < Dy) cg[tid] = -(logf(a.sig_g[tid]) + kHalfLog2Pi);
+    }
     // (the six pointers the horizon loop uses are re-read from the kernel arguments where they are used -- common.h: PSVO_ARG --
     //  held in scalar registers across the loop they do not fit beside the loop's own and hipcc spills them)
     const bool has_obs = a.obs != nullptr, has_eps = a.eps != nullptr, has_lpd = a.lpd != nullptr;
@@ -86,10 +95,12 @@ __global__ void __launch_bounds__(512) forecast_kernel(const ForecastArgs a) {
     };
     stage_row(0);
     float lg = -Dy * kHalfLog2Pi;
-    if (emission != 2) {
-        for (int e = 0; e < Dy; ++e) lg -= logf(a.sig_g[e]);
+    if constexpr (!MS) {    // (MS: the constant travels with each observed term)
+        if (emission != 2) {
+            for (int e = 0; e < Dy; ++e) lg -= logf(a.sig_g[e]);
+        }
+        keep_in_vgpr(lg);
     }
-    keep_in_vgpr(lg);
     // emission variance of output `lane` (the count emission takes the predictive mean itself)
     const float var0 = (emission == 0 && lane < Dy) ? a.sig_g[lane] * a.sig_g[lane] : 1.f;
 
@@ -133,6 +144,7 @@ __global__ void __launch_bounds__(512) forecast_kernel(const ForecastArgs a) {
         const float* lf = lfbuf[k & 1][og];
 
         // ---- emission: Dy outputs in the order e = 0 .. Dy - 1 -----------------------------------------------------------
+        [[maybe_unused]] int nobs = 0;      // MS: observed entries of the target row (the same number in every lane)
         {
             float h[H];
             MG::hidden(wg, x, h);
@@ -149,7 +161,19 @@ __global__ void __launch_bounds__(512) forecast_kernel(const ForecastArgs a) {
                     slot[kMaxDy + e] = s2;
                 }
                 if (has_lpd) {
-                    if (emission == 2) {
+                    if constexpr (MS) {     // observed terms only, constant included; the same choice in every lane
+                        const float ye = y[e];
+                        float term;
+                        if (emission == 2) {
+                            term = wobs::count_term(ye, r) - lf[e];
+                        } else {
+                            const float z = (ye - mu) * isg[e];
+                            term = fmaf(-0.5f * z, z, cg[e]);
+                        }
+                        const bool ob = (ye == ye);
+                        acc += ob ? term : 0.f;
+                        nobs += ob ? 1 : 0;
+                    } else if (emission == 2) {
                         acc += wobs::count_term(y[e], r) - lf[e];
                     } else {
                         const float z = (y[e] - mu) * isg[e];
@@ -158,7 +182,7 @@ __global__ void __launch_bounds__(512) forecast_kernel(const ForecastArgs a) {
                 }
             }
             if (has_lpd) {
-                const float g_lp = emission == 2 ? acc : fmaf(-0.5f, acc, lg);
+                const float g_lp = (MS || emission == 2) ? acc : fmaf(-0.5f, acc, lg);
                 const float v = valid ? logwn + g_lp : ninf;
                 const float vm = wave_max(v);
                 const float vb = (vm == ninf) ? 0.f : vm;
@@ -199,7 +223,7 @@ __global__ void __launch_bounds__(512) forecast_kernel(const ForecastArgs a) {
                 if (xmean) xmean[ko * DX + d] = m;
             } else if (lane == Dy + DX && has_lpd) {
                 float out = 0.f;
-                if (t + k < T) {
+                if (t + k < T && (!MS || nobs > 0)) {
                     float M = s0[2 * kMaxDy + 4];
                     for (int i = 1; i < nwo; ++i) M = fmaxf(M, s0[i * kFcSlot + 2 * kMaxDy + 4]);
                     const float Mb = (M == ninf) ? 0.f : M;
@@ -224,7 +248,7 @@ __global__ void __launch_bounds__(512) forecast_kernel(const ForecastArgs a) {
     }
 }
 
-template <int DX, int H, int EMIS>
+template <int DX, int H, int EMIS, bool MS>
 static int launch_forecast(ForecastArgs& a, hipStream_t stream) {
     const long long TB = (long long)a.T * a.B;
     a.nwo = (a.N + 63) >> 6;
@@ -232,15 +256,16 @@ static int launch_forecast(ForecastArgs& a, hipStream_t stream) {
     const int NT = 64 * a.nwo * a.G;
     const int blocks = (int)((TB + a.G - 1) / a.G);
     clear_hip_error();
-    hipLaunchKernelGGL((forecast_kernel<DX, H, EMIS>), dim3(blocks), dim3(NT), 0, stream, a);
+    hipLaunchKernelGGL((forecast_kernel<DX, H, EMIS, MS>), dim3(blocks), dim3(NT), 0, stream, a);
     return launch_status();
 }
 
 }  // namespace psvo
 
-extern "C" int psvo_particle_forecast(const psvo_desc* desc, int K, const psvo_mlp* f, const psvo_mlp* g, const float* sig_f,
-                                      const float* sig_g, const float* X, const float* logW, const float* obs, const float* eps,
-                                      float* ymean, float* yvar, float* xmean, float* lpd, void* stream) {
+// the checks and the launch behind psvo_particle_forecast and psvo_particle_forecast_missing (ms)
+static int particle_forecast_checked(const psvo_desc* desc, int K, const psvo_mlp* f, const psvo_mlp* g, const float* sig_f,
+                                     const float* sig_g, const float* X, const float* logW, const float* obs, const float* eps,
+                                     float* ymean, float* yvar, float* xmean, float* lpd, void* stream, bool ms) {
     using namespace psvo;
     if (!desc || !f || !g || !X) return PSVO_ERR_INVALID;
     if (!f->W1 || !f->b1 || !f->W2 || !f->b2 || !g->W1 || !g->b1 || !g->W2 || !g->b2) return PSVO_ERR_INVALID;
@@ -263,5 +288,19 @@ extern "C" int psvo_particle_forecast(const psvo_desc* desc, int K, const psvo_m
     hipStream_t s = static_cast<hipStream_t>(stream);
     return pick_dx(desc->Dx, [&](auto dx) {
         return pick_h(desc->H, [&](auto h) {
-            return pick<0, 1, 2>(desc->emission, [&](auto em) { return launch_forecast<dx(), h(), em()>(a, s); }); }); });
+            return pick<0, 1, 2>(desc->emission, [&](auto em) {
+                return ms ? launch_forecast<dx(), h(), em(), true>(a, s) : launch_forecast<dx(), h(), em(), false>(a, s); }); }); });
+}
+
+extern "C" int psvo_particle_forecast(const psvo_desc* desc, int K, const psvo_mlp* f, const psvo_mlp* g, const float* sig_f,
+                                      const float* sig_g, const float* X, const float* logW, const float* obs, const float* eps,
+                                      float* ymean, float* yvar, float* xmean, float* lpd, void* stream) {
+    return particle_forecast_checked(desc, K, f, g, sig_f, sig_g, X, logW, obs, eps, ymean, yvar, xmean, lpd, stream, false);
+}
+
+extern "C" int psvo_particle_forecast_missing(const psvo_desc* desc, int K, const psvo_mlp* f, const psvo_mlp* g,
+                                              const float* sig_f, const float* sig_g, const float* X, const float* logW,
+                                              const float* obs, const float* eps, float* ymean, float* yvar, float* xmean,
+                                              float* lpd, void* stream) {
+    return particle_forecast_checked(desc, K, f, g, sig_f, sig_g, X, logW, obs, eps, ymean, yvar, xmean, lpd, stream, true);
 }

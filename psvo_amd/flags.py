@@ -95,6 +95,10 @@ DEFINITIONS = [
     # not observed; its term is left out of the emission log-density.  Filter objectives (SVO, AESMC, IWAE), 1 <= Dy <= 32
     ("missing_obs", bool, False, "SVO / AESMC / IWAE: a NaN observation is missing, the ELBO bounds the density of the observed entries"),
     ("missing_rate", float, 0.0, "--generateTrainingData --missing_obs: knock entries out independently with this probability, in [0, 1)"),
+    # (not in the reference's registry) the two features gappy data needs beside --missing_obs, each on a missing-observation form
+    # of its kernel.  Off by default: without them the combinations stay refused
+    ("resample_ess_missing_obs", bool, False, "SVO / AESMC: run --resample_ess with --missing_obs on the adaptive missing-observation kernels"),
+    ("particle_forecast_missing_obs", bool, False, "run --particle_forecast with --missing_obs: lpd over the observed entries of each target row"),
     # printing and data saving (runner_flag.py:131-153)
     ("print_freq", int, 1, "frequency to evaluate testing loss & other metrics and save results"),
     ("save_trajectory", bool, True, "whether to save hidden trajectories during training"),

@@ -204,7 +204,8 @@ def _launch(name, fn, *args):
 # the entry points that take ess_frac / rs_in, by the `entry` they are asked for under (filter_forward_wobs with ess_frac stays a
 # refusal: the wide adaptive route is filter_forward_wobs_adaptive)
 _ADAPTIVE_ENTRY = {"psvo_filter_forward": "psvo_filter_forward_adaptive",
-                   "psvo_filter_forward_wobs_adaptive": "psvo_filter_forward_wobs_adaptive"}
+                   "psvo_filter_forward_wobs_adaptive": "psvo_filter_forward_wobs_adaptive",
+                   "psvo_filter_forward_wobs_missing_adaptive": "psvo_filter_forward_wobs_missing_adaptive"}
 
 
 def filter_forward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, fm0, fsig0,
@@ -275,6 +276,14 @@ def filter_forward_wobs_missing(*args, **kw):
     term is left out of the emission log-density (1 <= Dy <= 32, one hidden layer, every emission form); arguments, outputs and
     layouts of filter_forward."""
     return filter_forward(*args, entry="psvo_filter_forward_wobs_missing", **kw)
+
+
+def filter_forward_wobs_missing_adaptive(*args, ess_frac, rs_in=None, **kw):
+    """psvo_filter_forward_wobs_missing_adaptive: filter_forward_wobs_missing resampling where ESS < ess_frac N (1 <= Dy <= 32, one
+    hidden layer, every emission form); arguments of filter_forward, the result also holds rs (T,B) int32 and ess (T,B)."""
+    if ess_frac is None:
+        raise ValueError("filter_forward_wobs_missing_adaptive needs the threshold ess_frac")
+    return filter_forward(*args, entry="psvo_filter_forward_wobs_missing_adaptive", ess_frac=ess_frac, rs_in=rs_in, **kw)
 
 
 # The plain backward simulations (PSVO: bsim_*, PSVOwR: bsimwr_*) take the same inputs ahead of their own and their reverse
@@ -533,7 +542,8 @@ def filter_backward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0,
     wobs: psvo_filter_backward_wobs + psvo_mlp_wgrad_wobs for MLP_g (wide observations); with dFm / dlogW -- a backward
     simulation ran behind the wide filter -- or with ext=True, psvo_filter_backward_wobs_ext.
     missing (with wobs): psvo_filter_backward_wobs_missing, 1 <= Dy <= 32, dlse only; MLP_g's weight gradient from the d G rows is
-    psvo_mlp_wgrad_wobs for Dy >= 3 and the plain psvo_mlp_wgrad for Dy <= 2."""
+    psvo_mlp_wgrad_wobs for Dy >= 3 and the plain psvo_mlp_wgrad for Dy <= 2; with adaptive="wobs" as well,
+    psvo_filter_backward_wobs_missing_adaptive, following filt["rs"]."""
     lib = _lib.load()
     B, T, N, Dx, Dy, H = desc.B, desc.T, desc.N, desc.Dx, desc.Dy, desc.H
     dev = eps.device
@@ -553,12 +563,19 @@ def filter_backward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0,
     name = ("psvo_filter_backward_wobs_ext" if ext else "psvo_filter_backward_wobs") if wobs else "psvo_filter_backward"
     wide_g = wobs                # MLP_g's weight gradient on psvo_mlp_wgrad_wobs
     if missing:
-        if not wobs or adaptive or ext:
+        # (adaptive == "wobs" with missing: filter_backward_wobs_missing_adaptive, below)
+        if not wobs or (adaptive and adaptive != "wobs") or ext:
             raise ValueError("filter_backward: missing observations run on the wide-observation route (wobs=True) with the upstream "
                              "gradient dlse only, resampling at every step or never (no adaptive form, no gradients of Fm / logW)")
         name, wide_g = "psvo_filter_backward_wobs_missing", Dy >= 3
     decisions = ()
-    if adaptive:
+    if adaptive and missing:
+        if filt.get("rs") is None:
+            raise ValueError("filter_backward_wobs_missing_adaptive needs the forward pass's decisions filt['rs']")
+        _chk(filt["rs"], (T, B), "filt['rs']", torch.int32)
+        name = "psvo_filter_backward_wobs_missing_adaptive"
+        decisions = (_ptr(filt["rs"]),)
+    elif adaptive:
         if wobs and adaptive != "wobs":     # (the wide adaptive route is filter_backward_wobs_adaptive)
             raise ValueError("filter_backward: adaptive resampling belongs to the plain filter kernels (Dy <= 2)")
         if wobs and ext:
@@ -623,6 +640,12 @@ def filter_backward_wobs_missing(*args, **kw):
     """psvo_filter_backward_wobs_missing + psvo_mlp_wgrad (q1, f; g at Dy <= 2) + psvo_mlp_wgrad_wobs (g at Dy >= 3): the reverse
     of filter_forward_wobs_missing; arguments and result of filter_backward (dlse only)."""
     return filter_backward(*args, wobs=True, missing=True, **kw)
+
+
+def filter_backward_wobs_missing_adaptive(*args, **kw):
+    """psvo_filter_backward_wobs_missing_adaptive + the weight gradients of filter_backward_wobs_missing: the reverse of
+    filter_forward_wobs_missing_adaptive, following the decisions filt["rs"]; arguments and result of filter_backward (dlse only)."""
+    return filter_backward(*args, wobs=True, missing=True, adaptive="wobs", **kw)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -739,13 +762,14 @@ def ffbs_sample(desc, filt, sig_f=None, u=None, idx_in=None):
     return out
 
 
-def particle_forecast(desc, K, f, g, sig_f, sig_g, X, logW=None, obs=None, eps=None):
+def particle_forecast(desc, K, f, g, sig_f, sig_g, X, logW=None, obs=None, eps=None, missing=False):
     """psvo_particle_forecast: the k-step predictive distribution, k = 0..K, of the weighted cloud `X` (T,B,Dx,N) at every origin.
     `f`, `g` are the MLP tuples of the transition and the emission at the kernels' width (one hidden layer), `sig_f` (Dx) and
     `sig_g` (Dy) their scales (sig_g may be None for the count emission).  `logW` (T,B,N) log-weights or None = equal weights,
     `obs` (T,B,Dy) or None = no predictive log-density, `eps` (K,T,B,Dx,N) standard normals or None = noise-free propagation.
     Returns dict(ymean, yvar (K+1,T,B,Dy), xmean (K+1,T,B,Dx), lpd (K+1,T,B) or None without obs; lpd is 0 where t + k >= T).
-    Asynchronous on the launch stream."""
+    missing: psvo_particle_forecast_missing -- a NaN in `obs` is an entry that was not observed, lpd sums the observed entries of
+    the target row and is 0 where that row has none.  Asynchronous on the launch stream."""
     lib = _lib.load()
     B, T, N, Dx, Dy, H = desc.B, desc.T, desc.N, desc.Dx, desc.Dy, desc.H
     K = int(K)
@@ -763,7 +787,8 @@ def particle_forecast(desc, K, f, g, sig_f, sig_g, X, logW=None, obs=None, eps=N
     dev = X.device
     out = {"ymean": _empty(K + 1, T, B, Dy, device=dev), "yvar": _empty(K + 1, T, B, Dy, device=dev),
            "xmean": _empty(K + 1, T, B, Dx, device=dev), "lpd": _empty(K + 1, T, B, device=dev) if obs is not None else None}
-    _launch("psvo_particle_forecast", lib.psvo_particle_forecast, ctypes.byref(desc), K, ctypes.byref(fs), ctypes.byref(gs),
+    name = "psvo_particle_forecast_missing" if missing else "psvo_particle_forecast"
+    _launch(name, getattr(lib, name), ctypes.byref(desc), K, ctypes.byref(fs), ctypes.byref(gs),
             _ptr(sig_f), _ptr(sig_g), _ptr(X), _ptr(logW), _ptr(obs), _ptr(eps), _ptr(out["ymean"]), _ptr(out["yvar"]),
             _ptr(out["xmean"]), _ptr(out["lpd"]), _stream())
     return out

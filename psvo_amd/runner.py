@@ -104,11 +104,14 @@ def main(FLAGS):
     check_resample_ess(getattr(FLAGS, "resample_ess", 0.0), never_resamples=bool(FLAGS.IWAE),
                        backward_simulation=bool(FLAGS.PSVO or FLAGS.PSVOwR), output_cov=bool(FLAGS.output_cov), Dy=FLAGS.Dy,
                        wide_obs=bool(getattr(FLAGS, "resample_ess_wide_obs", False)),
-                       layers=[FLAGS.q1_layers, FLAGS.g_layers] + ([] if FLAGS.use_bootstrap else [FLAGS.f_layers]))
+                       layers=[FLAGS.q1_layers, FLAGS.g_layers] + ([] if FLAGS.use_bootstrap else [FLAGS.f_layers]),
+                       missing_obs=bool(getattr(FLAGS, "missing_obs", False) and getattr(FLAGS, "resample_ess_missing_obs", False)))
     check_missing_obs(bool(getattr(FLAGS, "missing_obs", False)), missing_rate=getattr(FLAGS, "missing_rate", 0.0),
                       backward_simulation=bool(FLAGS.PSVO or FLAGS.PSVOwR), resample_ess=getattr(FLAGS, "resample_ess", 0.0),
                       particle_forecast=bool(getattr(FLAGS, "particle_forecast", False)), output_cov=bool(FLAGS.output_cov),
-                      Dy=FLAGS.Dy, layers=[FLAGS.q1_layers, FLAGS.g_layers] + ([] if FLAGS.use_bootstrap else [FLAGS.f_layers]))
+                      Dy=FLAGS.Dy, layers=[FLAGS.q1_layers, FLAGS.g_layers] + ([] if FLAGS.use_bootstrap else [FLAGS.f_layers]),
+                      resample_ess_missing_obs=bool(getattr(FLAGS, "resample_ess_missing_obs", False)),
+                      particle_forecast_missing_obs=bool(getattr(FLAGS, "particle_forecast_missing_obs", False)))
     if FLAGS.use_2_q:
         FLAGS.q_uses_true_X = False
     device = _device()

@@ -41,6 +41,8 @@ Missing observations (FLAGS.missing_obs, off by default; SVO / AESMC / IWAE): a 
 run the missing-observation filter kernels, and the ELBO bounds the log-density of the observed entries.  The k-step R-square takes
 residuals and the centring mean over observed targets only; at every evaluation the share of missing entries of each split is
 printed and goes into metric_<iter>.p as missing_share_<split>.  y_hat at k = 0 is the model's imputation and is saved as before.
+With FLAGS.resample_ess_missing_obs the adaptive metrics above are reported beside it; with FLAGS.particle_forecast_missing_obs the
+forecast metrics are taken over observed targets (_forecast_metrics) and forecast_lpd_per_entry_<split> is added.
 """
 import math
 import os
@@ -83,18 +85,35 @@ def _r_square(y_hat, y, missing_obs=False):
     return 1.0 - float(np.square(resid).sum()) / float(np.square(centred).sum())
 
 
-def _forecast_metrics(y_mean, y_var, lpd, obs):
+def _forecast_metrics(y_mean, y_var, lpd, obs, missing_obs=False):
     """(lpd, R-square, calibration) per horizon k = 0 .. K of a particle forecast over one split: y_mean, y_var (n,T,K+1,Dy),
     lpd (n,T,K+1), obs (n,T,Dy).  Horizon k pairs origin t with obs[:, t + k], t + k < T; a horizon with no such pair (K >= T)
-    is NaN.  R-square as _r_square defines it."""
+    is NaN.  R-square as _r_square defines it.
+    missing_obs (FLAGS.missing_obs with FLAGS.particle_forecast_missing_obs): a NaN in obs was not observed and lpd scores the
+    observed entries of its target row.  A pair is valid when its target row has an observed entry: the mean lpd is over the
+    valid pairs, R-square is _r_square(.., missing_obs=True), the calibration is over observed entries, a horizon without an
+    observed target is NaN, and a fourth array is returned, lpd per entry = sum lpd / sum observed entries over the valid pairs
+    (rows of different completeness are scores of different dimension, which the plain mean mixes)."""
     n, T, K1, _ = y_mean.shape
-    out = np.full((3, K1), np.nan)
+    out = np.full((4 if missing_obs else 3, K1), np.nan)
     for k in range(min(K1, T)):
         y, m, v = obs[:, k:], y_mean[:, :T - k, k], y_var[:, :T - k, k]
+        if missing_obs:
+            seen = ~np.isnan(y)
+            n_obs = seen.sum(axis=-1)                   # (n, T - k) observed entries of every target row
+            pairs = n_obs > 0
+            if not pairs.any():
+                continue
+            lp = lpd[:, :T - k, k]
+            out[0, k] = float(np.mean(lp[pairs]))
+            out[1, k] = _r_square(m, y, missing_obs=True)
+            out[2, k] = float(np.mean((np.square(np.where(seen, y, 0.0) - m) / v)[seen]))
+            out[3, k] = float(np.sum(lp[pairs])) / float(np.sum(n_obs))
+            continue
         out[0, k] = float(np.mean(lpd[:, :T - k, k]))
         out[1, k] = _r_square(m, y)
         out[2, k] = float(np.mean(np.square(y - m) / v))
-    return out[0], out[1], out[2]
+    return tuple(out)
 
 
 def _collate(per_batch, keepdims):
@@ -321,9 +340,11 @@ class trainer:
             elbos, y_hat, y, *rest = self.evaluate(fetches, {self.obs: obs, self.hidden: hid})
             if forecast:
                 fc, rest = rest[-3:], rest[:-3]
-                lpd, rsq, cal = _forecast_metrics(*fc, np.asarray(obs, dtype=np.float32))
+                lpd, rsq, cal, *per_entry = _forecast_metrics(*fc, np.asarray(obs, dtype=np.float32), missing_obs=missing)
                 ess["forecast_lpd_" + split], ess["forecast_R_square_" + split] = lpd, rsq
                 ess["forecast_calibration_" + split] = cal
+                if missing:     # (FLAGS.particle_forecast_missing_obs: the score per observed entry)
+                    ess["forecast_lpd_per_entry_" + split] = per_entry[0]
             if adaptive:
                 frac, rest = np.asarray(rest[0]) / float(self.n_particles), rest[1:]
                 ess["adaptive_rate_" + split] = float(np.mean(rest[0]))
@@ -367,6 +388,9 @@ class trainer:
                 print("particle forecast Rsq train, valid:\n", ess["forecast_R_square_train"], "\n", ess["forecast_R_square_test"])
                 print("particle forecast calibration (1 = calibrated) train, valid:\n", ess["forecast_calibration_train"], "\n",
                       ess["forecast_calibration_test"])
+                if missing:
+                    print("particle forecast predictive log-density per observed entry train, valid:\n",
+                          ess["forecast_lpd_per_entry_train"], "\n", ess["forecast_lpd_per_entry_test"])
 
         if not math.isfinite(m["log_ZSMC_train"]):
             print("Nan in log_ZSMC, stop training")
