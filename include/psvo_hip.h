@@ -348,6 +348,50 @@ int psvo_particle_forecast_missing(const psvo_desc* desc, int K,
                            float* ymean, float* yvar, float* xmean, float* lpd, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * MAP trajectory (particle Viterbi; Godsill, Doucet and West 2001) on the particle system a forward filter left in HBM: the
+ * single most probable path through the T x N lattice of particles, where psvo_ffbs_smooth gives marginals and
+ * psvo_ffbs_sample random paths.  Added within ABI 6: purely additive.  Notation of psvo_ffbs_smooth; per sequence b:
+ *     G_t[j]   = sum_{e : obs[t,b,e] is not NaN} term_e(X[t,b,:,j])   terms, order e = 0..Dy-1 and constants exactly as in
+ *                                                                     psvo_particle_forecast_missing; exactly 0 where nothing
+ *                                                                     is observed
+ *     l_t[j,k] = log N(X[t+1,b,:,j]; Fm[t,b,:,k], sig_f)              diagonal, on scales, the -sum log sig_f term included
+ *     d_0[j]   = log N(X[0,b,:,j]; fm0[b,:], fsig0) + G_0[j]
+ *     d_t[j]   = G_t[j] + max_k (delta[t-1,b,k] + l_{t-1}[j,k])       bp[t,b,j] = the LOWEST k that attains the max;
+ *                                                                     bp[0,b,j] = j
+ *     lmax[t,b]    = max_j d_t[j]
+ *     delta[t,b,j] = d_t[j] - lmax[t,b]                               natural log; renormalised every step like the filter's lse
+ *     path[T-1,b]  = the lowest j with delta[T-1,b,j] == 0
+ *     path[t-1,b]  = bp[t,b,path[t,b]]
+ *     Xmap[t,b,:]  = X[t,b,:,path[t,b]]
+ * sum_t lmax[t,b] is the joint log-density of the best path, log p(x*_{0:T-1}, observed y), maximised over all N^T paths in
+ * O(T N^2).  logW is not read: every particle is a lattice node whatever its weight.  A NaN in obs is always an entry that was
+ * not observed (the rule of psvo_filter_forward_wobs_missing); there is no second form.  Precondition: X, Fm, scales and weights
+ * are finite.  Whatever the inputs hold, every bp and path entry lies in [0, N) and nothing is addressed with a value read from
+ * the data: every argmax starts at 0 and moves on strict `>`.
+ *
+ * Two launches: the emission terms G for every (t, b) at once (a lane per particle, written into delta), then one persistent
+ * workgroup per sequence that walks t upwards with one N x N pair phase per step (the tile is recomputed, never stored; no
+ * exponential) and backtracks behind a workgroup barrier.  No atomics, every maximum in a fixed order with the lowest index
+ * winning ties: two calls on the same inputs give bit-identical outputs, with or without PSVO_TUNE_DETERMINISTIC.  No gradient.
+ *
+ *  desc            B, T, N, Dx, Dy, H, emission, layers are read.  Dx in {2,3,4}, 1 <= Dy <= 32, H in {16,32,64}, N <= 512,
+ *                  emission in {0,1,2}, one hidden layer (everything outside this list: PSVO_ERR_UNSUPPORTED).  T = 1 and
+ *                  N = 1 are valid
+ *  g               MLP_g (Dx -> Dy), one hidden layer of width H
+ *  sig_f (Dx)      the constant transition scale the filter weighted with
+ *  sig_g (Dy)      emission scale; may be NULL for emission 2 only
+ *  fm0 (B,Dx), fsig0 (Dx)   mean and scale of the t = 0 transition term, as psvo_filter_forward takes them
+ *  obs (T,B,Dy)    observations; NaN = not observed
+ *  X, Fm (T,B,Dx,N) outputs of the forward filter
+ *  outputs: delta (T,B,N), lmax (T,B), bp (T,B,N) int32 (all required; delta and bp are also the kernel's workspace);
+ *           path (T,B) int32 and Xmap (T,B,Dx), each may be NULL (both NULL: no backtrack).
+ *  Every other NULL, and B, T or N <= 0, returns PSVO_ERR_INVALID before any launch.
+ * ------------------------------------------------------------------------------------------- */
+int psvo_map_path(const psvo_desc* desc, const psvo_mlp* g, const float* sig_f, const float* sig_g,
+                  const float* fm0, const float* fsig0, const float* obs, const float* X, const float* Fm,
+                  float* delta, float* lmax, int32_t* bp, int32_t* path, float* Xmap, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Backward simulation with proposal, STATE-DEPENDENT diagonal scales (FLAGS.output_cov and FLAGS.diag_cov; see
  * psvo_filter_forward_cov).  Same loop and outputs as psvo_bsim_forward (PSVO.backward_simulation_w_proposal, reference
  * src/SMC/PSVO.py:69-203); differences:

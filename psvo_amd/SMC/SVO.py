@@ -96,6 +96,29 @@ def check_missing_obs(on, missing_rate=0.0, backward_simulation=False, resample_
     return True
 
 
+def check_map_path(on, backward_simulation=False, output_cov=False, Dy=1, layers=(), wobs_max_dy=32):
+    """--MAP_path (the most probable trajectory through the filter's particles, psvo_map_path) as a bool.  ValueError, naming the
+    limit, for everything the kernel does not cover (runner.main calls this on the flags before it touches a device, SVO.__init__
+    on the model it is given).  `layers`: the hidden layers of the per-particle MLPs, one each."""
+    if not on:
+        return False
+    limit = "--MAP_path runs on the MAP-path kernel (psvo_map_path) behind the filter of SVO / AESMC / IWAE"
+    if backward_simulation:
+        raise ValueError("--MAP_path with --PSVO / --PSVOwR: %s; PSVO and PSVOwR already return backward-simulation "
+                         "trajectories" % limit)
+    if output_cov:
+        raise ValueError("--MAP_path with output_cov: %s, which takes a state-independent transition scale; the "
+                         "state-dependent-scale kernels have no MAP-path form" % limit)
+    if Dy > wobs_max_dy or Dy < 1:
+        raise ValueError("--MAP_path with Dy = %d: %s, which takes 1 <= Dy <= %d; no fallback path exists"
+                         % (Dy, limit, wobs_max_dy))
+    deep = [v for v in (_layer_list(s) for s in layers) if len(v) != 1]
+    if deep:
+        raise ValueError("--MAP_path with per-particle MLP layers %s: %s, which takes one hidden layer per MLP; two hidden "
+                         "layers have no MAP-path form" % (deep, limit))
+    return True
+
+
 def _layer_list(spec):
     """a *_layers flag ("32" / "32,32") or a list of widths -> list of ints"""
     if isinstance(spec, str):
@@ -150,6 +173,9 @@ class SVO:
         # ... on gappy data (FLAGS.particle_forecast_missing_obs; _route_missing_obs refused the combination without it):
         # psvo_particle_forecast_missing scores the observed entries of every target row
         self.forecast_missing = bool(self.missing_obs and self.forecast)
+        # the most probable trajectory through the filter's particles at evaluation time (FLAGS.MAP_path, not in the reference;
+        # psvo_map_path)
+        self.MAP_path = self._route_map_path(model, bool(getattr(FLAGS, "MAP_path", False)))
 
         self.name = name
         self.generator = None        # torch.Generator on the compute device; None = global RNG
@@ -232,6 +258,17 @@ class SVO:
         return True
 
     @classmethod
+    def _route_map_path(cls, model, on=True):
+        """`on` when the MAP-path kernel (psvo_map_path) covers this model and objective.  What it does not cover is refused
+        here, up front: it evaluates MLP_g with one hidden layer, a state-independent transition scale, Dy <= 32, and it reads
+        the particle system of a filter objective."""
+        trans = [t for t in (getattr(model, "q1_tran", None), getattr(model, "g_tran", None),
+                             None if getattr(model, "use_bootstrap", True) else getattr(model, "f_tran", None)) if t is not None]
+        return check_map_path(on, backward_simulation=cls.uses_backward_simulation,
+                              output_cov=bool(getattr(model, "output_cov", False)), Dy=getattr(model, "Dy", cls._PLAIN_DY),
+                              layers=[t.Dhs for t in dict.fromkeys(trans)], wobs_max_dy=cls._WOBS_MAX_DY)
+
+    @classmethod
     def _route_resample_ess(cls, model, FLAGS):
         """FLAGS.resample_ess as a float: 0.0 (off: resampling at every step, or never for IWAE) or the threshold tau of
         psvo_filter_forward_adaptive, 0 < tau <= 1.  What the adaptive kernels do not cover is refused here, up front.  With
@@ -276,6 +313,12 @@ class SVO:
         is the log-probability of every pick given the path's successor, log["path_distinct"] (B,T) the number of different
         particles the N paths pass through, log["paths"] the kernel's output dict.  With FLAGS.FFBS as well both kernels run
         and the smoother's per-step draws move to log["Xs_marginal"].
+
+        With FLAGS.MAP_path, under the same condition, the most probable trajectory through the filter's particles is decoded
+        (psvo_map_path; no random number is drawn): log["X_map"] (B,T,Dx) is the path, log["map_index"] (B,T) int32 the particle
+        it takes at every step, log["map_score"] (B,) fp64 its joint log-density log p(x*, observed y) and log["map"] the
+        kernel's output dict in its own layout (delta, lmax, bp, path, Xmap) with what the kernel was given beside it (g, sig_f,
+        sig_g, fm0, fsig0, obs).  log["Xs"] and every other key are unchanged.
         """
         batch_size, time, _ = obs.shape
         self.Dx, self.batch_size, self.time = self.model.Dx, batch_size, time
@@ -297,6 +340,8 @@ class SVO:
             self._smooth(filt, log, noise or {})
         if self.FFBSi and not torch.is_grad_enabled():
             self._sample_paths(filt, log, noise or {})
+        if self.MAP_path and not torch.is_grad_enabled():
+            self._map_path(filt, log)
         self._release()
         return log_ZSMC, log
 
@@ -339,6 +384,21 @@ class SVO:
         log["path_distinct"] = paths["distinct"].transpose(0, 1)
         log["paths"] = paths
 
+    def _map_path(self, filt, log):
+        """the MAP trajectory through the particle system `filt` (psvo_map_path): the transition scale of _smooth, the t = 0
+        transition term the filter was given and the observations as the filter saw them (NaN = not observed)"""
+        model = self.model
+        desc = ops.make_desc(self.batch_size, self.time, self.n_particles, 1, model.Dx, model.Dy, self._kernel_width()[0],
+                             bootstrap=model.use_bootstrap, emission=self._emission_code(), layers=1)
+        g = _c(self._mlp_params(model.g_tran))
+        given = {"sig_f": self._transition_scale(filt), "sig_g": _c(self._sigma(self.g)), "fm0": _c(self._fm0),
+                 "fsig0": _c(self._fsig0), "obs": self._obs_TB}
+        mp = ops.map_path(desc, filt, g, **given)
+        log["X_map"] = mp["Xmap"].transpose(0, 1)                       # (T, B, Dx) -> (batch_size, time, Dx)
+        log["map_index"] = mp["path"].transpose(0, 1)
+        log["map_score"] = mp["lmax"].double().sum(0)
+        log["map"] = dict(mp, g=g, **given)                             # (beside the outputs: what the kernel was given)
+
     def _release(self):
         """drop what one evaluation cached on the object (scale vectors, hoisted means, features, stream context).
 
@@ -346,7 +406,7 @@ class SVO:
         with it the parameters' gradient accumulators, which remember the stream they were created on.  The next evaluation
         would reuse them: issued under a hipGraph capture on another stream the engine then synchronises that old stream
         into the capture, where it is never joined back (hipStreamEndCapture crashes on ROCm 7.2 instead of reporting it)."""
-        self._sigmas = self._m0 = self._sig0 = self._obs_TB = self._ov = self._missing = None
+        self._sigmas = self._m0 = self._sig0 = self._fm0 = self._fsig0 = self._obs_TB = self._ov = self._missing = None
         self.preprocessed_X0 = self.preprocessed_obs = None
 
     # hidden widths the kernels are instantiated for (template parameter H of csrc/*.hip)
@@ -522,7 +582,7 @@ class SVO:
                                       None if model.use_bootstrap else self._mlp_params(model.f_tran),
                                       self._mlp_params(model.g_tran))
         sig_f = None if model.use_bootstrap else self._sigma(self.f)
-        self._m0, self._sig0 = m0, sig0
+        self._m0, self._sig0, self._fm0, self._fsig0 = m0, sig0, fm0, fsig0
         desc = self._desc()
         gb = (self._gbuf(model.q1_tran), None if model.use_bootstrap else self._gbuf(model.f_tran), self._gbuf(model.g_tran))
         desc._gbufs = gb if (gb[0] is not None and gb[2] is not None and (model.use_bootstrap or gb[1] is not None)) else None

@@ -77,6 +77,7 @@ SIGNATURES = {
     "psvo_ffbs_sample": (ctypes.c_int, [_DESC] + [_P] * 11 + [_P]),
     "psvo_particle_forecast": (ctypes.c_int, [_DESC, ctypes.c_int, _MLP, _MLP] + [_P] * 10 + [_P]),
     "psvo_particle_forecast_missing": (ctypes.c_int, [_DESC, ctypes.c_int, _MLP, _MLP] + [_P] * 10 + [_P]),
+    "psvo_map_path": (ctypes.c_int, [_DESC, _MLP] + [_P] * 12 + [_P]),
     "psvo_filter_backward_cov": (ctypes.c_int, [_DESC, _MLP, _MLP, _MLP] + [_P] * 39 + [_P]),
     "psvo_bsim_forward_cov": (ctypes.c_int, [_DESC] + [_P] * 4 + [_MLP, _MLP, _MLP] + [_P] * 23 + [_P]),
     "psvo_bsim_backward_cov": (ctypes.c_int, [_DESC] + [_P] * 4 + [_MLP, _MLP, _MLP] + [_P] * 38 + [_P]),

@@ -1,5 +1,6 @@
-// Pair-phase helpers shared by the marginal smoother (ffbs.hip) and the backward sampler (ffbsi.hip): the staged LDS rows of a
-// step and the max-shifted log-sum-exp over them.  Both kernels walk N x N pair terms
+// Pair-phase helpers shared by the marginal smoother (ffbs.hip), the backward sampler (ffbsi.hip) and the MAP decoder
+// (map_path.hip): the staged LDS rows of a step, the max-shifted log-sum-exp over them (pair_lse) and the running maximum with
+// its index (pair_argmax).  The kernels walk N x N pair terms
 //     log2(e) l[j,k] = cst[k] - sum_d ((x[j,d] - m[k,d]) r[k,d])^2
 // with the lane's own point in registers and the other index's rows broadcast from LDS.
 #pragma once
@@ -95,6 +96,48 @@ __device__ __forceinline__ float pair_lse(const float* __restrict__ sv, const fl
     const float mn = fmaxf(m[0], m[1]);
     const float mb = (mn == ninf) ? 0.f : mn;
     return mn + log2_fast(fmaf(s[0], exp2_fast(m[0] - mb), s[1] * exp2_fast(m[1] - mb)));
+}
+
+// max_i (sv[i] - sum_d ((sp[i][d] - own[d]) r[d])^2) over the n8 staged rows and the LOWEST i that attains it (map_path.hip):
+// pair_lse's walk -- the same read-ahead, the same packed squares, the same two accumulators over even and odd groups of four --
+// with a running (max, argmax) in place of the online sum, so no exponential.  An accumulator moves on strict `>` only and
+// sees its rows in rising order: it holds the lowest index of its own maximum.  The merge takes the odd accumulator where it is
+// larger, or equal with the lower index.  Both start at (-inf, 0): padding rows (sv = -inf) never win, and whatever the rows
+// hold -- NaN included, every comparison with it is false -- the index returned is one the loop counted, 0 <= arg < n8, or 0.
+template <int DX>
+__device__ __forceinline__ void pair_argmax(const float* __restrict__ sv, const float* __restrict__ sp,
+                                            const f2 (&own)[(DX + 1) / 2], const f2 (&r)[(DX + 1) / 2], int n8,
+                                            float& best, int& arg) {
+    constexpr int NP = (DX + 1) / 2;
+    const float ninf = -__builtin_huge_valf();
+    float m[2] = {ninf, ninf};
+    int am[2] = {0, 0};
+    auto fold = [&](const Rows4<DX, false>& R, int h, int i0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            f2 acc = f2{0.f, 0.f};
+#pragma unroll
+            for (int q = 0; q < NP; ++q) {
+                const f2 z = (R.p[i][q] - own[q]) * r[q];
+                acc = pk_fma(z, z, acc);
+            }
+            const float v = R.v[i] - (acc.x + acc.y);
+            const bool up = v > m[h];
+            m[h] = up ? v : m[h];
+            am[h] = up ? i0 + i : am[h];
+        }
+    };
+    Rows4<DX, false> even, odd;
+    even.load(sv, sp, nullptr, 0);
+    for (int i0 = 0; i0 < n8; i0 += 8) {
+        odd.load(sv, sp, nullptr, i0 + 4);
+        fold(even, 0, i0);
+        even.load(sv, sp, nullptr, i0 + 8 < n8 ? i0 + 8 : 0);      // (the last read-ahead wraps to group 0 and is not used)
+        fold(odd, 1, i0 + 4);
+    }
+    const bool take = m[1] > m[0] || (m[1] == m[0] && am[1] < am[0]);
+    best = take ? m[1] : m[0];
+    arg = take ? am[1] : am[0];
 }
 
 }  // namespace psvo

@@ -99,6 +99,9 @@ DEFINITIONS = [
     # of its kernel.  Off by default: without them the combinations stay refused
     ("resample_ess_missing_obs", bool, False, "SVO / AESMC: run --resample_ess with --missing_obs on the adaptive missing-observation kernels"),
     ("particle_forecast_missing_obs", bool, False, "run --particle_forecast with --missing_obs: lpd over the observed entries of each target row"),
+    # MAP trajectory for the filter objectives (not in the reference's registry, which has no decoder): the single most probable
+    # path through the filter's particles (particle Viterbi).  Off by default, evaluation only
+    ("MAP_path", bool, False, "SVO / AESMC / IWAE: return the most probable trajectory through the filter's particles (particle Viterbi)"),
     # printing and data saving (runner_flag.py:131-153)
     ("print_freq", int, 1, "frequency to evaluate testing loss & other metrics and save results"),
     ("save_trajectory", bool, True, "whether to save hidden trajectories during training"),

@@ -794,6 +794,39 @@ def particle_forecast(desc, K, f, g, sig_f, sig_g, X, logW=None, obs=None, eps=N
     return out
 
 
+def map_path(desc, filt, g, sig_f, sig_g, fm0, fsig0, obs):
+    """psvo_map_path: the MAP trajectory (particle Viterbi) through the particles of a forward filter.  `filt` is the dict the
+    filter returned (X and Fm (T,B,Dx,N) are read; the weights are not), `g` the emission's MLP tuple at the kernels' width (one
+    hidden layer), `sig_f` (Dx) the constant transition scale the filter weighted with, `sig_g` (Dy) the emission scale (may be
+    None for the count emission), `fm0` (B,Dx) and `fsig0` (Dx) the t = 0 transition term, `obs` (T,B,Dy) with NaN = not
+    observed.  Returns dict(delta (T,B,N), lmax (T,B), bp (T,B,N) int32, path (T,B) int32, Xmap (T,B,Dx)); sum_t lmax is the
+    joint log-density of the path.  Asynchronous on the launch stream."""
+    lib = _lib.load()
+    B, T, N, Dx, Dy, H = desc.B, desc.T, desc.N, desc.Dx, desc.Dy, desc.H
+    X, Fm = filt.get("X"), filt.get("Fm")
+    if X is None or Fm is None:
+        raise ValueError("map_path needs the filter's X and Fm")
+    if filt.get("Fs") is not None:
+        raise ValueError("map_path takes a constant transition scale `sig_f`; the filter left a scale per particle (Fs)")
+    if sig_f is None or fm0 is None or fsig0 is None or obs is None:
+        raise ValueError("map_path needs sig_f (Dx), fm0 (B,Dx), fsig0 (Dx) and obs (T,B,Dy)")
+    if N > 512:
+        raise ValueError("map_path: N = %d particles; the MAP-path kernel holds a sequence in one workgroup, N <= 512" % N)
+    _chk(X, (T, B, Dx, N), "X"); _chk(Fm, (T, B, Dx, N), "Fm"); _chk(obs, (T, B, Dy), "obs")
+    _chk(sig_f, (Dx,), "sig_f"); _chk(sig_g, (Dy,), "sig_g"); _chk(fm0, (B, Dx), "fm0"); _chk(fsig0, (Dx,), "fsig0")
+    if sig_g is None and desc.emission != 2:
+        raise ValueError("map_path: the emission scale `sig_g` may be None for the count emission only")
+    gs = _mlp_struct(g, Dx, H, Dy, "g")
+    dev = X.device
+    out = {"delta": _empty(T, B, N, device=dev), "lmax": _empty(T, B, device=dev),
+           "bp": _empty(T, B, N, device=dev, dtype=torch.int32), "path": _empty(T, B, device=dev, dtype=torch.int32),
+           "Xmap": _empty(T, B, Dx, device=dev)}
+    _launch("psvo_map_path", lib.psvo_map_path, ctypes.byref(desc), ctypes.byref(gs), _ptr(sig_f), _ptr(sig_g), _ptr(fm0),
+            _ptr(fsig0), _ptr(obs), _ptr(X), _ptr(Fm), _ptr(out["delta"]), _ptr(out["lmax"]), _ptr(out["bp"]), _ptr(out["path"]),
+            _ptr(out["Xmap"]), _stream())
+    return out
+
+
 def filter_backward_cov(desc, q1, f, g, sigc_q1, sigc_f, sigc_g, mu2, sig2, m0, sig0, fm0, fsig0, obs, eps, filt,
                         dlse=None, dFm=None, dFs=None, dlogW=None):
     """psvo_filter_backward_cov + two psvo_mlp_wgrad launches per MLP (one per head; both contribute to dW1 / db1).

@@ -27,7 +27,7 @@ from .SMC.AESMC import AESMC
 from .SMC.IWAE import IWAE
 from .SMC.PSVO import PSVO
 from .SMC.PSVOwR import PSVOwR
-from .SMC.SVO import SVO, check_missing_obs, check_resample_ess
+from .SMC.SVO import SVO, check_map_path, check_missing_obs, check_resample_ess
 from .trainer import trainer
 from .utils.data_generator import PoissonEmitter, count_loading, generate_dataset, knock_out
 from .utils.data_loader import load_data
@@ -112,6 +112,9 @@ def main(FLAGS):
                       Dy=FLAGS.Dy, layers=[FLAGS.q1_layers, FLAGS.g_layers] + ([] if FLAGS.use_bootstrap else [FLAGS.f_layers]),
                       resample_ess_missing_obs=bool(getattr(FLAGS, "resample_ess_missing_obs", False)),
                       particle_forecast_missing_obs=bool(getattr(FLAGS, "particle_forecast_missing_obs", False)))
+    check_map_path(bool(getattr(FLAGS, "MAP_path", False)), backward_simulation=bool(FLAGS.PSVO or FLAGS.PSVOwR),
+                   output_cov=bool(FLAGS.output_cov), Dy=FLAGS.Dy,
+                   layers=[FLAGS.q1_layers, FLAGS.g_layers] + ([] if FLAGS.use_bootstrap else [FLAGS.f_layers]))
     if FLAGS.use_2_q:
         FLAGS.q_uses_true_X = False
     device = _device()

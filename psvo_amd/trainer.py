@@ -26,6 +26,11 @@ behind the filter, so "Xs", the k-step predictions and the saved trajectories ar
 minimum over each split of the number of distinct particles the N paths pass through are printed and go into metric_<iter>.p
 as ffbsi_distinct_mean_<split> / ffbsi_distinct_min_<split>.  Training steps are untouched.
 
+MAP trajectory (FLAGS.MAP_path, off by default; SVO / AESMC / IWAE): every evaluation then also runs psvo_map_path behind the
+filter; the mean over each split of the path's joint log-density per time step, map_score / T, is printed and goes into
+metric_<iter>.p as map_score_<split>; trajectory_<epoch>.p gains X_map (saving_num, T, Dx) and map_index (saving_num, T) of the saved
+sequences.  "Xs" and everything derived from it are unchanged.  Training steps are untouched.
+
 Adaptive resampling (FLAGS.resample_ess, off by default; SVO / AESMC): training and evaluation run the adaptive filter kernels;
 at every evaluation the share of (sequence, step) pairs that resampled and the mean / minimum of ESS / N over each split are
 printed and go into metric_<iter>.p as adaptive_rate_<split>, adaptive_ess_mean_<split>, adaptive_ess_min_<split>.
@@ -279,6 +284,7 @@ class trainer:
         self.saving_feed_dict = {self.obs: obs_test[:self.saving_num], self.hidden: hidden_test[:self.saving_num]}
         Xs_val = None
         forecast = bool(getattr(self.SMC, "forecast", False))
+        map_path = bool(getattr(self.SMC, "MAP_path", False))
         for flag, fetch, stem in ((self.save_trajectory, "Xs", "trajectory"), (self.save_y_hat, "y_hat", "y_hat")):
             if not flag:
                 continue
@@ -286,6 +292,9 @@ class trainer:
             if forecast and fetch == "y_hat":      # (FLAGS.particle_forecast: the predictive moments beside the point forecast)
                 val, extra["y_mean"], extra["y_var"] = self.evaluate([fetch, "forecast_y_mean", "forecast_y_var"],
                                                                      self.saving_feed_dict, average=False)
+            elif map_path and fetch == "Xs":       # (FLAGS.MAP_path: the decoded path beside the cloud)
+                val, extra["X_map"], extra["map_index"] = self.evaluate([fetch, "X_map", "map_index"], self.saving_feed_dict,
+                                                                        average=False)
             else:
                 val = self.evaluate(fetch, self.saving_feed_dict, average=False)      # (collective: every rank takes part)
             if fetch == "Xs":
@@ -331,8 +340,9 @@ class trainer:
         adaptive = bool(getattr(self.SMC, "resample_ess", 0.0))
         forecast = bool(getattr(self.SMC, "forecast", False))
         missing = bool(getattr(self.SMC, "missing_obs", False))
+        map_path = bool(getattr(self.SMC, "MAP_path", False))
         fetches = (["log_ZSMC", "y_hat", "y"] + (["ess", "resampled"] if adaptive else []) + (["ess_smooth"] if ffbs else [])
-                   + (["path_distinct"] if ffbsi else []))
+                   + (["path_distinct"] if ffbsi else []) + (["map_score"] if map_path else []))
         if forecast:       # (last, so that the fetches ahead of them keep their places)
             fetches += ["forecast_y_mean", "forecast_y_var", "forecast_lpd"]
         m, ess = {}, {}
@@ -345,6 +355,9 @@ class trainer:
                 ess["forecast_calibration_" + split] = cal
                 if missing:     # (FLAGS.particle_forecast_missing_obs: the score per observed entry)
                     ess["forecast_lpd_per_entry_" + split] = per_entry[0]
+            if map_path:    # (behind the forecast's three, ahead of everything else: the fetches before it keep their places)
+                score, rest = rest[-1], rest[:-1]
+                ess["map_score_" + split] = float(np.mean(np.asarray(score, dtype=np.float64) / np.asarray(obs).shape[1]))
             if adaptive:
                 frac, rest = np.asarray(rest[0]) / float(self.n_particles), rest[1:]
                 ess["adaptive_rate_" + split] = float(np.mean(rest[0]))
@@ -381,6 +394,10 @@ class trainer:
                 print("FFBSi distinct particles per step (of {}), mean / min: train {:.2f} / {:.0f}, valid {:.2f} / {:.0f}"
                       .format(self.n_particles, ess["ffbsi_distinct_mean_train"], ess["ffbsi_distinct_min_train"],
                               ess["ffbsi_distinct_mean_test"], ess["ffbsi_distinct_min_test"]))
+
+            if map_path:
+                print("MAP path: joint log-density per time step, train {:.4f}, valid {:.4f}"
+                      .format(ess["map_score_train"], ess["map_score_test"]))
 
             if forecast:
                 print("particle forecast, k = 0 .. {}: predictive log-density train, valid:\n".format(self.MSE_steps),
@@ -487,6 +504,12 @@ class trainer:
                 out["ess_smooth"] = log["ess_smooth"].contiguous().cpu().numpy()      # (B, T); FLAGS.FFBS only
             if "path_distinct" in names:
                 out["path_distinct"] = log["path_distinct"].contiguous().cpu().numpy()      # (B, T) int32; FLAGS.FFBSi only
+            if "map_score" in names:
+                out["map_score"] = log["map_score"].cpu().numpy()                     # (B,) fp64; FLAGS.MAP_path only
+            if "X_map" in names:
+                out["X_map"] = log["X_map"].contiguous().cpu().numpy()                # (B, T, Dx)
+            if "map_index" in names:
+                out["map_index"] = log["map_index"].contiguous().cpu().numpy()        # (B, T) int32
         return [out[n] for n in names]
 
     def evaluate(self, fetches, feed_dict_w_batches={}, average=False, keepdims=False):
