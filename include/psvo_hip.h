@@ -1013,6 +1013,74 @@ int psvo_filter_backward_wobs_ext(const psvo_desc* desc,
                                   float* ws, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * PSVO on missing observations (added within ABI 6: purely additive).  The intersection of "Missing observations" and "PSVO on
+ * wide observations" above and nothing new (psvo_amd/csrc/bsim_wobs_ms.hip: the text of bsim_wobs.hip compiled a second time).
+ * A NaN in obs[t,b,e] is an entry that was not observed: with o_e = (y_e == y_e), log g(y_t | x) is the sum of the observed
+ * terms in the order e = 0 .. Dy-1, the constant c_e = -(log sig_g[e] + 1/2 log 2 pi) of a Gaussian term included (an LDS row,
+ * filled once); a step with nothing observed has glp == 0 exactly.  The select only feeds the sum: no branch, barrier or store
+ * depends on the data.  The proposal-side inputs (bmu2, minit) are the caller's: it computes them from observations with the
+ * missing entries set to 0.
+ *
+ * psvo_bsim_forward_wobs_missing: the argument list, outputs and layouts of psvo_bsim_forward_wobs.  With no NaN in obs the
+ *   count emission's outputs equal psvo_bsim_forward_wobs's bit for bit; the Gaussian forms add c_e term by term, not once per
+ *   launch, and differ by that rounding.
+ * psvo_bsim_backward_wobs_missing: the argument list and outputs of psvo_bsim_backward_wobs.  dGt[t,b,e,:,:] of a missing
+ *   (t,b,e) is WRITTEN as 0 (the weight gradient reads the row back) and the d sig_g column of the lane receives nothing: an
+ *   output that is never observed has exactly zero gradient in its column of W2, in b2 and in dsig_g.  ws:
+ *   psvo_bsim_wobs_ws_floats(B, T, N, M, Dx, Dy) floats with psvo_bsim_wobs_blocks(N, M), unchanged.  The sum orders are those
+ *   of psvo_bsim_backward_wobs; two runs are bit-identical.  MLP_g's weight gradient from the d G rows is psvo_mlp_wgrad_wobs
+ *   for Dy >= 3 and the plain psvo_mlp_wgrad for Dy <= 2.
+ * psvo_filter_backward_wobs_missing_ext: psvo_filter_backward_wobs_missing with the upstream gradients dFm_ext / dlogW_ext /
+ *   nparts of psvo_filter_backward_wobs_ext, added in part order.  With both NULL its outputs equal
+ *   psvo_filter_backward_wobs_missing's bit for bit; that entry point keeps its signature and its kernels.
+ *
+ * Envelope of the backward-simulation pair: 1 <= Dy <= 32, Dx in {2,3,4}, H in {16,32,64}, M in {4,8,16,32}, N <= 512, one
+ * hidden layer, emission 0 / 1 / 2.  The checks are those of psvo_bsim_forward_wobs / psvo_bsim_backward_wobs in the same
+ * order with the same statuses: a bad desc->emission is PSVO_ERR_UNSUPPORTED, then a missing required pointer, B <= 0, T < 2 or
+ * N <= 0 is PSVO_ERR_INVALID, then anything else outside the envelope is PSVO_ERR_UNSUPPORTED; all before a device is touched.
+ * psvo_filter_backward_wobs_missing_ext has the envelope and statuses of psvo_filter_backward_wobs_missing, and nparts <= 0 with
+ * an upstream gradient given is PSVO_ERR_INVALID.  psvo_bsim_forward_wobs / psvo_bsim_backward_wobs still refuse Dy < 3.
+ * ------------------------------------------------------------------------------------------- */
+int psvo_bsim_forward_wobs_missing(const psvo_desc* desc,
+                                   const float* X, const float* Fm, const float* logW, const float* lse,
+                                   const psvo_mlp* f, const psvo_mlp* g, const psvo_mlp* q1_inv,
+                                   const float* sig_f, const float* sig_g, const float* sig_q1inv, const float* sig_bq2,
+                                   const float* bmu2, const float* minit, const float* sig_init,
+                                   const float* imean, const float* isig,
+                                   const float* obs, const float* eps_b, const float* u_b, const int32_t* sel_in,
+                                   float* bwX, float* flp, float* glp, float* Omega, int32_t* sel_out,
+                                   float* score,
+                                   float* lam2_all, float* om_all, float* mu1_all,
+                                   void* stream);
+int psvo_bsim_backward_wobs_missing(const psvo_desc* desc,
+                                    const float* Fm, const float* logW, const float* lse,
+                                    const psvo_mlp* f, const psvo_mlp* g, const psvo_mlp* q1_inv,
+                                    const float* sig_f, const float* sig_g, const float* sig_q1inv, const float* sig_bq2,
+                                    const float* bmu2, const float* minit, const float* sig_init,
+                                    const float* imean, const float* isig,
+                                    const float* obs, const float* eps_b,
+                                    const float* bwX, const int32_t* sel,
+                                    const float* lam2_all, const float* om_all, const float* mu1_all,
+                                    const float* dscore,
+                                    float* xt, float* dFt, float* dGt, float* dmu1,
+                                    float* dbmu2_rows, float* dminit_rows, float* dimean_rows,
+                                    float* dFm, float* dlogW, float* dlse,
+                                    float* dsig_f, float* dsig_g, float* dsig_q1inv, float* dsig_bq2, float* dsig_init,
+                                    float* disig, float* ws, void* stream);
+int psvo_filter_backward_wobs_missing_ext(const psvo_desc* desc,
+                                          const psvo_mlp* q1, const psvo_mlp* f, const psvo_mlp* g,
+                                          const float* sig_q1, const float* sig_q2, const float* sig_f, const float* sig_g,
+                                          const float* mu2,
+                                          const float* m0, const float* sig0, const float* fm0, const float* fsig0,
+                                          const float* obs, const float* eps,
+                                          const float* X, const float* Fm, const float* P1, const float* logW, const float* lse,
+                                          const int32_t* idx,
+                                          const float* dlse, int nparts, const float* dFm_ext, const float* dlogW_ext,
+                                          float* dP, float* dF, float* dG, float* dmu2, float* dm0, float* dfm0,
+                                          float* dsig_q1, float* dsig_q2, float* dsig_f, float* dsig_g, float* dsig0, float* dfsig0,
+                                          float* ws, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * One-hidden-layer MLP over plain rows (the hoisted per-(sequence, step) networks q0, q2, BSim_q2,
  * BSim_q_init): tf_mvn.mean of MLP_transformation, reference src/transformation/MLP.py:48-68 as called
  * from src/SMC/SVO.py:80-84,134-138 and src/SMC/PSVO.py:86-87,120-122.

@@ -7,7 +7,8 @@ import torch
 
 from .. import ops
 from .. import autograd
-from ..autograd import BsimCovFunction, BsimFunction, BsimWobsFunction, ElboBsimFunction, Overlap, side_stream
+from ..autograd import (BsimCovFunction, BsimFunction, BsimWobsFunction, BsimWobsMissingFunction, ElboBsimFunction, Overlap,
+                        side_stream)
 from .SVO import SVO
 
 
@@ -28,7 +29,13 @@ class PSVO(SVO):
         self.BSim_q2 = model.BSim_q2_dist
 
     def get_log_ZSMC(self, obs, hidden, noise=None):
-        """PSVO.py:21-50.  Extra `noise` keys: eps_b (T,B,Dx,N,M), u_b (T,B,N) or sel_b (T,B,N) int32."""
+        """PSVO.py:21-50.  Extra `noise` keys: eps_b (T,B,Dx,N,M), u_b (T,B,N) or sel_b (T,B,N) int32.
+
+        With FLAGS.missing_obs and FLAGS.BSim_missing_obs a NaN in `obs` is an entry that was not observed: the filter and the
+        backward simulation leave its term out of the emission density (psvo_filter_forward_wobs_missing,
+        psvo_bsim_forward_wobs_missing), every proposal-side reader (q0, q2, the encoders, BSim_q2, BSim_q_init) reads 0 in its
+        place, log_ZSMC bounds the log-density of the observed entries and log["missing"] (B,T,Dy) bool is the mask; log["Xs"],
+        log["filter"] and log["bsim"] keep their keys."""
         batch_size, time, _ = obs.shape
         self.Dx, self.batch_size, self.time = self.model.Dx, batch_size, time
         if self.model.output_cov:
@@ -41,7 +48,8 @@ class PSVO(SVO):
         #  f.mean(mu_0) of the t = 0 term accumulates into the same gradient slice on the main stream)
         both = self.model.use_bootstrap and self.model.use_2_q
         self._release()
-        # (wide observations, FLAGS.BSim_wide_obs: the wide filter and the wide backward simulation on one stream)
+        # (wide observations, FLAGS.BSim_wide_obs: the wide filter and the wide backward simulation on one stream; likewise
+        #  missing observations, FLAGS.BSim_missing_obs, which _route_wide_obs sends there at every width)
         self._ov = (Overlap(side_stream(obs.device), side_stream(obs.device, 1) if both else None)
                     if (autograd.OVERLAP and obs.is_cuda and not self.wide_obs) else None)
         self._sigmas = self.model.sigmas()          # every scale vector of this evaluation, one fused launch
@@ -51,6 +59,8 @@ class PSVO(SVO):
         log_ZSMC = self.compute_log_ZSMC_bsim(bs["score"])
         log["Xs"] = bs["bwX"].permute(1, 0, 3, 2)                      # (B, T, N, Dx)
         log["filter"], log["bsim"] = filt, bs
+        if self.missing_obs:
+            log["missing"] = self._missing              # (B, T, Dy) bool
         self._release()
         return log_ZSMC, log
 
@@ -112,6 +122,10 @@ class PSVO(SVO):
         model = self.model
         M = self.n_particles_for_BSim_proposal
 
+        if self.missing_obs:
+            # the proposal side (the encoder, BSim_q2, BSim_q_init) reads 0 where nothing was observed, as the filter's does;
+            # the kernel alone gets the NaN-carrying rows (the copy SMC() made: _bsim_draws)
+            obs = obs.masked_fill(self._missing, 0.0)
         _, preprocessed_obs = self.BS_preprocess_obs(obs)                        # (B, T, 2Dh)
         bmu2 = self.BSim_q2.mean(preprocessed_obs).transpose(0, 1).contiguous()   # (T, B, Dx)
         minit = self.BSim_q_init.mean(preprocessed_obs[:, -1])                   # (B, Dx)
@@ -131,6 +145,8 @@ class PSVO(SVO):
         node = BsimFunction
         if self.wide_obs:
             node, desc._gbufs = BsimWobsFunction, None
+        if self.missing_obs:        # psvo_bsim_forward_wobs_missing / _backward_wobs_missing at every 1 <= Dy <= 32
+            node, desc._gbufs = BsimWobsMissingFunction, None
         first, extra = self._mlp_args(self._mlp_params(model.f_tran), self._mlp_params(model.g_tran),
                                       self._mlp_params(model.q1_inv_tran))
         score, bwX, flp, glp, Omega, sel = node.apply(

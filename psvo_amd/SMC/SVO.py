@@ -10,7 +10,8 @@ import torch
 
 from .. import ops
 from ..autograd import (FilterAdaptiveFunction, FilterCovFunction, FilterFunction, FilterWobsAdaptiveFunction,
-                        FilterWobsFunction, FilterWobsMissingAdaptiveFunction, FilterWobsMissingFunction)
+                        FilterWobsFunction, FilterWobsMissingAdaptiveFunction, FilterWobsMissingBsimFunction,
+                        FilterWobsMissingFunction)
 
 
 def check_resample_ess(raw, never_resamples=False, backward_simulation=False, output_cov=False, Dy=1, plain_dy=2,
@@ -57,14 +58,17 @@ def check_resample_ess(raw, never_resamples=False, backward_simulation=False, ou
 
 def check_missing_obs(on, missing_rate=0.0, backward_simulation=False, resample_ess=0.0, particle_forecast=False,
                       output_cov=False, Dy=1, layers=(), wobs_max_dy=32, resample_ess_missing_obs=False,
-                      particle_forecast_missing_obs=False):
+                      particle_forecast_missing_obs=False, bsim_missing_obs=False, cross_chain=False):
     """--missing_obs (a NaN observation is an entry that was not observed) as a bool.  ValueError, naming the limit, for
     everything the missing-observation kernels (psvo_filter_forward_wobs_missing) do not cover and for a --missing_rate that is
     no probability or has nothing to act on (runner.main calls this on the flags before it touches a device, SVO.__init__ on the
     model it is given).  `layers`: the hidden layers of the per-particle MLPs, one each.  `resample_ess_missing_obs`
     (--resample_ess_missing_obs): --resample_ess runs on psvo_filter_forward_wobs_missing_adaptive; `particle_forecast_missing_obs`
     (--particle_forecast_missing_obs): --particle_forecast runs on psvo_particle_forecast_missing.  Neither has an effect without
-    --missing_obs, and without them the two combinations stay refused."""
+    --missing_obs, and without them the two combinations stay refused.  `bsim_missing_obs` (--BSim_missing_obs): PSVO runs its
+    backward simulation on psvo_bsim_forward_wobs_missing / psvo_bsim_backward_wobs_missing behind that filter; without it
+    PSVO stays refused, and PSVOwR (`cross_chain`: the objective resamples across chains) stays refused with it.  No effect
+    without --missing_obs."""
     rate = float(0.0 if missing_rate is None else missing_rate)
     if not (0.0 <= rate < 1.0):
         raise ValueError("--missing_rate = %r: the probability of knocking an entry out lies in [0, 1)" % (missing_rate,))
@@ -74,9 +78,20 @@ def check_missing_obs(on, missing_rate=0.0, backward_simulation=False, resample_
                              "missing-observation route scores; pass --missing_obs")
         return False
     limit = "missing observations run on psvo_filter_forward_wobs_missing, the filter of SVO / AESMC / IWAE"
-    if backward_simulation:
+    if backward_simulation and not bsim_missing_obs:
         raise ValueError("--missing_obs with --PSVO / --PSVOwR: %s; the backward-simulation kernels evaluate the emission too and "
                          "have no missing-observation form" % limit)
+    if backward_simulation:
+        # --BSim_missing_obs: psvo_bsim_forward_wobs_missing behind the missing-observation filter, PSVO only
+        limit = ("missing observations under PSVO run on psvo_filter_forward_wobs_missing and psvo_bsim_forward_wobs_missing "
+                 "(--BSim_missing_obs)")
+        if cross_chain:
+            raise ValueError("--missing_obs --BSim_missing_obs with --PSVOwR: --BSim_missing_obs covers PSVO only; the cross-chain "
+                             "resampling kernels of PSVOwR have no missing-observation form")
+        if float(resample_ess or 0.0) != 0.0:
+            raise ValueError("--missing_obs --BSim_missing_obs with --resample_ess under --PSVO: the backward-simulation kernels "
+                             "assume a filter that resamples at every step; the adaptive missing-observation kernels cover the "
+                             "filter objectives (SVO, AESMC) only")
     if float(resample_ess or 0.0) != 0.0 and not resample_ess_missing_obs:
         raise ValueError("--missing_obs with --resample_ess: %s, which resamples at every step (or never); the adaptive kernels "
                          "have no missing-observation form" % limit)
@@ -187,7 +202,11 @@ class SVO:
         those kernels do not cover is refused here, up front."""
         trans = [t for t in (getattr(model, "q1_tran", None), getattr(model, "g_tran", None),
                              None if getattr(model, "use_bootstrap", True) else getattr(model, "f_tran", None)) if t is not None]
+        if cls.uses_backward_simulation:    # (FLAGS.BSim_missing_obs: the backward simulation evaluates MLP_f and MLP_q1inv too)
+            trans += [t for t in (getattr(model, "f_tran", None), getattr(model, "q1_inv_tran", None)) if t is not None]
         return check_missing_obs(bool(getattr(model, "missing_obs", False) or getattr(FLAGS, "missing_obs", False)),
+                                 bsim_missing_obs=bool(getattr(FLAGS, "BSim_missing_obs", False)),
+                                 cross_chain=cls.uses_backward_simulation and not cls.has_wide_backward_simulation,
                                  missing_rate=getattr(FLAGS, "missing_rate", 0.0),
                                  backward_simulation=cls.uses_backward_simulation,
                                  resample_ess=getattr(FLAGS, "resample_ess", 0.0),
@@ -214,6 +233,10 @@ class SVO:
                 raise ValueError("--count_emission with Dy = %d: the count emission runs on the wide-observation kernels, which "
                                  "take 3 <= Dy <= %d; the plain kernels (Dy <= %d) have no count form"
                                  % (Dy, cls._WOBS_MAX_DY, cls._PLAIN_DY))
+        if missing_obs and cls.uses_backward_simulation:
+            # PSVO under FLAGS.BSim_missing_obs (_route_missing_obs has accepted it, or refused it, by now): the wide backward
+            # simulation in its missing-observation form at every width, Dy <= 2 included; FLAGS.BSim_wide_obs is not needed
+            return True
         if Dy <= cls._PLAIN_DY or missing_obs:      # (missing observations: _route_missing_obs has routed the filter)
             return False
         limit = "observations wider than Dy = %d run on the wide-observation filter kernels" % cls._PLAIN_DY
@@ -592,6 +615,8 @@ class SVO:
             node, desc._gbufs = FilterWobsFunction, None
         if self.missing_obs:        # psvo_filter_forward_wobs_missing / _backward_wobs_missing at every 1 <= Dy <= 32
             node, desc._gbufs = FilterWobsMissingFunction, None
+            if self.uses_backward_simulation:       # (PSVO, FLAGS.BSim_missing_obs: Fm and logW carry gradients back)
+                node = FilterWobsMissingBsimFunction
         if self.resample_ess:
             # psvo_filter_forward_adaptive / psvo_filter_backward_adaptive: the decision per (step, sequence) is the kernel's
             # (wide observations, FLAGS.resample_ess_wide_obs: psvo_filter_forward_wobs_adaptive / _backward_wobs_adaptive)

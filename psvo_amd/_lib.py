@@ -68,6 +68,10 @@ SIGNATURES = {
     "psvo_bsim_wobs_blocks": (ctypes.c_int, [ctypes.c_int] * 2),
     "psvo_bsim_wobs_ws_floats": (ctypes.c_longlong, [ctypes.c_int] * 6),
     "psvo_bsim_backward_wobs": (ctypes.c_int, [_DESC] + [_P] * 3 + [_MLP, _MLP, _MLP] + [_P] * 34 + [_P]),
+    "psvo_bsim_forward_wobs_missing": (ctypes.c_int, [_DESC] + [_P] * 4 + [_MLP, _MLP, _MLP] + [_P] * 22 + [_P]),
+    "psvo_bsim_backward_wobs_missing": (ctypes.c_int, [_DESC] + [_P] * 3 + [_MLP, _MLP, _MLP] + [_P] * 34 + [_P]),
+    "psvo_filter_backward_wobs_missing_ext": (ctypes.c_int, [_DESC, _MLP, _MLP, _MLP] + [_P] * 18 + [ctypes.c_int, _P, _P]
+                                              + [_P] * 13 + [_P]),
     "psvo_mlp_wgrad_wobs_blocks": (ctypes.c_int, [ctypes.c_longlong]),
     "psvo_mlp_wgrad_wobs": (ctypes.c_int, [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                            _P, _P, _MLP, _P, _P, ctypes.c_int, _P]),

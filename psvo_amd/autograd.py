@@ -425,6 +425,25 @@ class FilterWobsMissingFunction(torch.autograd.Function):
         return _filter_backward(ctx, ops.filter_backward_wobs_missing, 5, dlse)
 
 
+class FilterWobsMissingBsimFunction(torch.autograd.Function):
+    """psvo_filter_forward_wobs_missing / psvo_filter_backward_wobs_missing_ext: FilterWobsMissingFunction in front of a
+    BsimWobsMissingFunction (PSVO under FLAGS.missing_obs with FLAGS.BSim_missing_obs).
+
+    apply(...) takes FilterFunction's arguments and returns its outputs; lse, Fm and logW are differentiable, and the gradients
+    on Fm / logW go through psvo_filter_backward_wobs_missing_ext.  The weight gradients are FilterWobsMissingFunction's.  One
+    stream, gradients returned as tensors."""
+
+    @staticmethod
+    def forward(ctx, desc, obs_TB, eps, u, idx_in, *t):
+        filt = _filter_forward(ctx, ops.filter_forward_wobs_missing, desc, obs_TB, eps, u, idx_in, t)
+        ctx.mark_non_differentiable(filt["X"], filt["Xanc"], filt["idx"])
+        return filt["lse"], filt["Fm"], filt["logW"], filt["X"], filt["Xanc"], filt["idx"]
+
+    @staticmethod
+    def backward(ctx, dlse, dFm, dlogW, *_):
+        return _filter_backward(ctx, ops.filter_backward_wobs_missing, 5, dlse, dFm, dlogW)
+
+
 class FilterWobsMissingAdaptiveFunction(torch.autograd.Function):
     """psvo_filter_forward_wobs_missing_adaptive / psvo_filter_backward_wobs_missing_adaptive: FilterWobsMissingFunction resampling
     a sequence only where its effective sample size has fallen below ess_frac N (FLAGS.missing_obs with FLAGS.resample_ess and
@@ -549,6 +568,23 @@ class BsimFunction(torch.autograd.Function):
         return _bsim_node_grads(ctx, r, 5)
 
 
+def _bsim_wobs_forward(ctx, op, desc, obs_TB, eps_b, u_b, sel_in, Fm, logW, lse, t):
+    """the forward of the two wide backward-simulation nodes: op is ops.bsim_forward_wobs or ops.bsim_forward_wobs_missing"""
+    bs = _bsim_forward(ctx, op, desc, obs_TB, eps_b, Fm, logW, lse, t, u_b=u_b, sel_in=sel_in)
+    ctx.gbufs = None                      # (this route returns every gradient as a tensor)
+    ctx.mark_non_differentiable(bs["bwX"], bs["flp"], bs["glp"], bs["Omega"], bs["sel"])
+    return bs["score"], bs["bwX"], bs["flp"], bs["glp"], bs["Omega"], bs["sel"]
+
+
+def _bsim_wobs_backward(ctx, op, dscore):
+    """their reverse: op is ops.bsim_backward_wobs or ops.bsim_backward_wobs_missing"""
+    desc = ctx.desc
+    f, g, q, rest, obs_TB, eps_b = ctx.saved
+    dscore = _cg(_or_zeros(ctx, dscore, desc.B, desc.N)).float()
+    r = op(desc, ctx.filt, f, g, q, *rest, obs_TB, eps_b, ctx.bs, dscore)
+    return _bsim_node_grads(ctx, r, 5)
+
+
 class BsimWobsFunction(torch.autograd.Function):
     """psvo_bsim_forward_wobs / psvo_bsim_backward_wobs: the backward simulation behind a wide filter (3 <= Dy <= 32, one hidden
     layer per particle MLP).
@@ -558,18 +594,27 @@ class BsimWobsFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, desc, obs_TB, eps_b, u_b, sel_in, Fm, logW, lse, *t):
-        bs = _bsim_forward(ctx, ops.bsim_forward_wobs, desc, obs_TB, eps_b, Fm, logW, lse, t, u_b=u_b, sel_in=sel_in)
-        ctx.gbufs = None                      # (this route returns every gradient as a tensor)
-        ctx.mark_non_differentiable(bs["bwX"], bs["flp"], bs["glp"], bs["Omega"], bs["sel"])
-        return bs["score"], bs["bwX"], bs["flp"], bs["glp"], bs["Omega"], bs["sel"]
+        return _bsim_wobs_forward(ctx, ops.bsim_forward_wobs, desc, obs_TB, eps_b, u_b, sel_in, Fm, logW, lse, t)
 
     @staticmethod
     def backward(ctx, dscore, *_):
-        desc = ctx.desc
-        f, g, q, rest, obs_TB, eps_b = ctx.saved
-        dscore = _cg(_or_zeros(ctx, dscore, desc.B, desc.N)).float()
-        r = ops.bsim_backward_wobs(desc, ctx.filt, f, g, q, *rest, obs_TB, eps_b, ctx.bs, dscore)
-        return _bsim_node_grads(ctx, r, 5)
+        return _bsim_wobs_backward(ctx, ops.bsim_backward_wobs, dscore)
+
+
+class BsimWobsMissingFunction(torch.autograd.Function):
+    """psvo_bsim_forward_wobs_missing / psvo_bsim_backward_wobs_missing: BsimWobsFunction with missing observations, behind a
+    FilterWobsMissingBsimFunction (1 <= Dy <= 32, one hidden layer, every emission form).  obs_TB (T,B,Dy) carries a NaN where
+    nothing was observed; the emission log-density then sums the observed entries only.
+
+    apply(...) takes BsimFunction's arguments and returns its outputs.  One stream, gradients returned as tensors."""
+
+    @staticmethod
+    def forward(ctx, desc, obs_TB, eps_b, u_b, sel_in, Fm, logW, lse, *t):
+        return _bsim_wobs_forward(ctx, ops.bsim_forward_wobs_missing, desc, obs_TB, eps_b, u_b, sel_in, Fm, logW, lse, t)
+
+    @staticmethod
+    def backward(ctx, dscore, *_):
+        return _bsim_wobs_backward(ctx, ops.bsim_backward_wobs_missing, dscore)
 
 
 def _bsim_cov_forward(ctx, op, desc, obs_TB, eps_b, Fm, Fs, logW, lse, t, **draws):

@@ -12,7 +12,7 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libpsvo_hip.so")
 # (longest compiles first: with 8 parallel hipcc jobs the build then ends when the work does, not when a late-started
 #  psvowr_bwd unit does; the *_l2 units are the same sources compiled with PSVO_L = 2 -- two hidden layers per particle MLP)
-SOURCES = ["bsim_wobs.hip", "bsim_cov.hip", "psvowr_bwd_l2.hip", "psvowr_bwd.hip", "bsim_bwd_dx4_l2.hip", "bsim_fwd_l2.hip", "bsim_fwd.hip",
+SOURCES = ["bsim_wobs.hip", "bsim_wobs_ms.hip", "bsim_cov.hip", "psvowr_bwd_l2.hip", "psvowr_bwd.hip", "bsim_bwd_dx4_l2.hip", "bsim_fwd_l2.hip", "bsim_fwd.hip",
            "bsim_bwd_dx2_l2.hip", "bsim_bwd_dx3_l2.hip", "psvowr_fwd.hip", "psvowr_fwd_l2.hip", "bsim_bwd_dx4.hip",
            "bsim_bwd_dx2.hip", "bsim_bwd_dx3.hip", "filter_bwd_l2.hip", "bsim_bwd2_dx2.hip", "filter_bwd.hip",
            "filter_fwd_l2.hip", "filter_cov.hip", "filter_wobs.hip", "filter_fwd.hip", "bsim_bwd2_dx4.hip", "bsim_bwd2_dx3.hip", "mlp_grad.hip", "lstm_bwd.hip",
@@ -26,7 +26,7 @@ UNIT_HEADERS = {"bsim_bwd_impl.h": ("bsim_bwd_dx", "bsim_bwd2_dx", "bsim_bwd.hip
                 "filter_fwd_impl.h": ("filter_fwd",),
                 "filter_bwd_impl.h": ("filter_bwd",),
                 "filter_wobs_impl.h": ("filter_wobs.hip",),
-                "wobs_common.h": ("filter_wobs.hip", "bsim_wobs.hip", "forecast.hip", "map_path.hip")}
+                "wobs_common.h": ("filter_wobs.hip", "bsim_wobs", "forecast.hip", "map_path.hip")}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-slp-vectorize"]
 # Round 2 built the two-hidden-layer units with `-mllvm -vgpr-regalloc=basic`: their per-lane H x H layer held 2 H values per
 # lane and under that pressure the default (greedy) allocator split live ranges around divergent regions, with hipcc 7.2 placing
@@ -53,6 +53,8 @@ def build_lib(force=False, verbose=True):
         deps = [src] + hdrs
         if s.endswith("_l2.hip"):
             deps.append(os.path.join(CSRC, s.replace("_l2.hip", ".hip")))       # (#include "X.hip")
+        if s.endswith("_ms.hip"):
+            deps.append(os.path.join(CSRC, s.replace("_ms.hip", ".hip")))       # (likewise, with PSVO_MS = 1)
         if s.startswith("bsim_bwd_dx"):
             deps.append(os.path.join(CSRC, s.replace("_l2", "")))
         deps += [os.path.join(CSRC, h) for h, users in UNIT_HEADERS.items() if s.startswith(users)]

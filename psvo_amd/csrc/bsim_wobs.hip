@@ -22,10 +22,31 @@
 //     lane order after the time loop), then reads the row back to accumulate d h for 16 or 32 hidden units at a time -- the
 //     register remedy of the wide reverse filter;
 //   * the other scale sums are per-lane registers folded by block_sum (lanes by the DPP scan, waves in wave order).
+//
+// Missing observations (PSVO_MS = 1: bsim_wobs_ms.hip is `#define PSVO_MS 1` + `#include "bsim_wobs.hip"`, the kernels of
+// psvo_bsim_forward_wobs_missing / psvo_bsim_backward_wobs_missing, 1 <= Dy <= 32): a NaN in obs is an observation that was not
+// made, as in filter_wobs_impl.h.  o_e = (y == y) is a broadcast and only feeds selects: log g sums the observed terms in the
+// order e = 0 .. Dy - 1 (nothing observed: exactly 0), and the normalising constant of the Gaussian forms is the LDS row
+// c_e = -(log sig_g[e] + 1/2 log 2 pi) where the count form has its log-factorials.  Reverse: the d G row entry and the lane's
+// d sig_g column entry of a missing output are selected to 0.  Everything that differs sits under `#if PSVO_MS`; the kernels
+// live in a namespace of their own (psvo::wbs_ms), so that the two units' instantiations are distinct symbols.
 #include "wobs_common.h"
 
+#ifndef PSVO_MS
+#define PSVO_MS 0
+#endif
+#if PSVO_MS
+#define PSVO_WBS wbs_ms
+#define PSVO_WBS_ENTRY(name) name##_missing
+#define PSVO_WBS_MIN_DY 1
+#else
+#define PSVO_WBS wbs
+#define PSVO_WBS_ENTRY(name) name
+#define PSVO_WBS_MIN_DY 3
+#endif
+
 namespace psvo {
-namespace wbs {
+namespace PSVO_WBS {
 
 using wobs::GLds;
 using wobs::kMaxDy;
@@ -86,12 +107,18 @@ __global__ void __launch_bounds__(256) bsim_wobs_fwd_kernel(const FwdArgs a) {
     float* ybuf = isg + kMaxDy;         // [2][kMaxDy] observation rows of step t (t & 1) and t - 1
     float* tile = ybuf + 2 * kMaxDy;    // [2][NP][TS]
     float* lfbuf = tile + 2 * NP * TS;  // CNT: [2][kMaxDy] log Gamma(y + 1) of the rows in ybuf
+#if PSVO_MS
+    float* cg = tile + 2 * NP * TS;     // !CNT (no lfbuf then): [kMaxDy] -(log sig_g + 1/2 log 2 pi), the constant of one term
+#endif
 
     MQ::load(wf, a.f, tid, NTB);
     MQ::load(wqi, a.q1inv, tid, NTB);
     MG::load(wg, a.g, Dy, tid, NTB);
     if (tid < Dy) {
         if constexpr (!CNT) isg[tid] = 1.f / a.sig_g[tid];
+#if PSVO_MS
+        if constexpr (!CNT) cg[tid] = -(logf(a.sig_g[tid]) + kHalfLog2Pi);
+#endif
         const float y0 = a.obs[((size_t)(T - 1) * B + b) * Dy + tid];
         ybuf[((T - 1) & 1) * kMaxDy + tid] = y0;
         if constexpr (CNT) lfbuf[((T - 1) & 1) * kMaxDy + tid] = wobs::log_factorial(y0);
@@ -108,10 +135,12 @@ __global__ void __launch_bounds__(256) bsim_wobs_fwd_kernel(const FwdArgs a) {
         rp[d] = isf[d] * rscale;
         kf -= logf(s);
     }
+#if !PSVO_MS
     float lg = -Dy * kHalfLog2Pi;
     if constexpr (!CNT) {
         for (int e = 0; e < Dy; ++e) lg -= logf(a.sig_g[e]);
     }
+#endif
     float pc[DX], pic[DX], pi1[DX], pi2[DX];
     float kq = -DX * kHalfLog2Pi;
 #pragma unroll
@@ -249,6 +278,30 @@ __global__ void __launch_bounds__(256) bsim_wobs_fwd_kernel(const FwdArgs a) {
             float h[H];
             MG::hidden(wg_t, x, h);
             float acc = 0.f;
+#if PSVO_MS
+            // observed terms only, constant included, in the order e = 0 .. Dy - 1; nothing observed: exactly 0
+            if constexpr (CNT) {
+                const float* lf_t = lfbuf + (t & 1) * kMaxDy + zo;
+#pragma unroll 1
+                for (int e = 0; e < Dy; ++e) {
+                    const float y = y_t[e];
+                    const float term = wobs::count_term(y, MG::out(wg_t, e, h)) - lf_t[e];
+                    acc += (y == y) ? term : 0.f;
+                }
+            } else {
+                const float* cg_t = cg + zo;
+#pragma unroll 1
+                for (int e = 0; e < Dy; ++e) {
+                    float gm = MG::out(wg_t, e, h);
+                    if (a.emission) gm = emis_mean(gm);
+                    const float y = y_t[e];
+                    const float z = (y - gm) * isg[e];
+                    const float term = fmaf(-0.5f * z, z, cg_t[e]);
+                    acc += (y == y) ? term : 0.f;
+                }
+            }
+            g_lp = acc;
+#else
             if constexpr (CNT) {     // y log lam - lam - log Gamma(y + 1), one term per output
                 const float* lf_t = lfbuf + (t & 1) * kMaxDy + zo;
 #pragma unroll 1
@@ -264,6 +317,7 @@ __global__ void __launch_bounds__(256) bsim_wobs_fwd_kernel(const FwdArgs a) {
                 }
                 g_lp = fmaf(-0.5f, acc, lg);
             }
+#endif
         }
 
         // ---- filter term: logsumexp_j( log f(x~ | X_{t-1}[j]) + W^_{t-1}[j] ), online in the log2 domain -----------------
@@ -357,8 +411,9 @@ __global__ void __launch_bounds__(256) bsim_wobs_fwd_kernel(const FwdArgs a) {
 template <int DX, int H>
 static size_t fwd_lds_bytes(int N, bool count) {
     const int NP = (N + 7) & ~7;
+    // (PSVO_MS: one more row, the per-output constants, where the count form has its log-factorials)
     return sizeof(float) * (2 * MlpLds<DX, H, DX, 1>::kSize + GLds<DX, H>::kSize + 3 * kMaxDy + 2 * (size_t)NP * (DX + 1) +
-                            (count ? 2 * kMaxDy : 0));
+                            (count ? 2 * kMaxDy : PSVO_MS ? kMaxDy : 0));
 }
 
 template <int DX, int H, int M>
@@ -406,7 +461,7 @@ __global__ void __launch_bounds__(256) bsim_wobs_bwd_kernel(const BwdArgs a) {
     const int NTB = blockDim.x, nwv = NTB >> 6;
     const int B = a.B, T = a.T, N = a.N, Dy = a.Dy;
     // (the host checked the envelope: the loops over Dy, N and the waves then need no uniform guard masks, which are SGPR pairs)
-    __builtin_assume(Dy >= 3 && Dy <= kMaxDy && N >= 1 && N <= 512 && T >= 2 && NTB >= 64 && NTB <= 256 && B >= 1);
+    __builtin_assume(Dy >= PSVO_WBS_MIN_DY && Dy <= kMaxDy && N >= 1 && N <= 512 && T >= 2 && NTB >= 64 && NTB <= 256 && B >= 1);
     const int NP = (N + 15) & ~15;            // tile padded (W' = -inf: zero weight) to whole tiles of 16
     const int b = blockIdx.y, blk = blockIdx.x, nblk = gridDim.x;
     const int cpb = NTB / M;
@@ -562,6 +617,30 @@ __global__ void __launch_bounds__(256) bsim_wobs_bwd_kernel(const BwdArgs a) {
         {
             float h[H];
             MG::hidden(wg_t, x, h);
+#if PSVO_MS
+            // a missing entry: its d G row entry is written as 0 (it is read back), its d sig_g column entry gets nothing
+            if constexpr (CNT) {
+#pragma unroll 1
+                for (int o = 0; o < Dy; ++o) {
+                    const float y = y_t[o];
+                    const float dr = dphi * wobs::count_dterm(y, MG::out(wg_t, o, h));
+                    if (valid) dGrow[o * gstride] = (y == y) ? dr : 0.f;
+                }
+            } else {
+#pragma unroll 1
+                for (int o = 0; o < Dy; ++o) {
+                    float gm = MG::out(wg_t, o, h);
+                    float dmean = 1.f;
+                    if (a.emission) { dmean = emis_dmean(gm); gm = emis_mean(gm); }
+                    const float is = isg[o];
+                    const float y = y_t[o];
+                    const bool ob = (y == y);
+                    const float z = (y - gm) * is;
+                    sg[o * NTB + tid] += ob ? dphi * (z * z - 1.f) * is : 0.f;
+                    if (valid) dGrow[o * gstride] = ob ? dphi * z * is * dmean : 0.f;
+                }
+            }
+#else
             if constexpr (CNT) {
 #pragma unroll 1
                 for (int o = 0; o < Dy; ++o) {
@@ -580,6 +659,7 @@ __global__ void __launch_bounds__(256) bsim_wobs_bwd_kernel(const BwdArgs a) {
                     if (valid) dGrow[o * gstride] = dphi * z * is * dmean;
                 }
             }
+#endif
         }
         // (second walk over the outputs: the lane reads its own d G row back, hidden units in chunks)
         MG::template bwd_input<(H >= 64 ? 32 : 16)>(wg_t, Dy, dGrow, gstride, valid, x, dx);
@@ -841,7 +921,7 @@ static int check_shape(const psvo_desc* d) {
     if (d->B <= 0 || d->T < 2 || d->N <= 0) return PSVO_ERR_INVALID;
     const bool dx = d->Dx >= 2 && d->Dx <= 4, h = d->H == 16 || d->H == 32 || d->H == 64;
     const bool m = d->M == 4 || d->M == 8 || d->M == 16 || d->M == 32;
-    if (d->Dy < 3 || d->Dy > kMaxDy || !dx || !h || !m || d->N > 512 || d->B > 65535 || d->layers < 0 || d->layers > 1)
+    if (d->Dy < PSVO_WBS_MIN_DY || d->Dy > kMaxDy || !dx || !h || !m || d->N > 512 || d->B > 65535 || d->layers < 0 || d->layers > 1)
         return PSVO_ERR_UNSUPPORTED;
     return PSVO_OK;
 }
@@ -861,21 +941,23 @@ static WsLayout ws_layout(int B, int T, int N, int M, int Dx, int Dy) {
     return {(size_t)T * B * nblk * Dx * N, (size_t)T * B * nblk * N, (size_t)B * nblk * (7 * Dx + Dy)};
 }
 
-}  // namespace wbs
+}  // namespace PSVO_WBS (wbs, or wbs_ms)
 }  // namespace psvo
 
+#if !PSVO_MS     // (the geometry and the workspace are those of the static pair: one definition, in its unit)
 extern "C" int psvo_bsim_wobs_blocks(int N, int M) {
     if (N <= 0 || M <= 0) return 0;
-    return psvo::wbs::geometry(N, M).nblk;
+    return psvo::PSVO_WBS::geometry(N, M).nblk;
 }
 
 extern "C" long long psvo_bsim_wobs_ws_floats(int B, int T, int N, int M, int Dx, int Dy) {
     if (B <= 0 || T <= 0 || N <= 0 || M <= 0 || Dx <= 0 || Dy <= 0) return 0;
-    const psvo::wbs::WsLayout l = psvo::wbs::ws_layout(B, T, N, M, Dx, Dy);
+    const psvo::PSVO_WBS::WsLayout l = psvo::PSVO_WBS::ws_layout(B, T, N, M, Dx, Dy);
     return (long long)(l.dFm_part + l.dlogW_part + l.sacc);
 }
+#endif
 
-extern "C" int psvo_bsim_forward_wobs(const psvo_desc* desc, const float* X, const float* Fm, const float* logW,
+extern "C" int PSVO_WBS_ENTRY(psvo_bsim_forward_wobs)(const psvo_desc* desc, const float* X, const float* Fm, const float* logW,
                                       const float* lse, const psvo_mlp* f, const psvo_mlp* g, const psvo_mlp* q1_inv,
                                       const float* sig_f, const float* sig_g, const float* sig_q1inv, const float* sig_bq2,
                                       const float* bmu2, const float* minit, const float* sig_init, const float* imean,
@@ -884,7 +966,7 @@ extern "C" int psvo_bsim_forward_wobs(const psvo_desc* desc, const float* X, con
                                       int32_t* sel_out, float* score, float* lam2_all, float* om_all, float* mu1_all,
                                       void* stream) {
     using namespace psvo;
-    using namespace psvo::wbs;
+    using namespace psvo::PSVO_WBS;
     if (!desc_emission_ok(desc, 2)) return PSVO_ERR_UNSUPPORTED;
     if (!desc || !Fm || !logW || !lse || !f || !g || !q1_inv || !sig_f || !sig_g || !sig_q1inv || !sig_bq2 || !bmu2 ||
         !minit || !sig_init || !imean || !isig || !obs || !eps_b || !bwX || !flp || !glp || !Omega || !sel_out || !score)
@@ -907,7 +989,7 @@ extern "C" int psvo_bsim_forward_wobs(const psvo_desc* desc, const float* X, con
     return dispatch(desc, [&](auto dx, auto h, auto m) { return launch_fwd<dx(), h(), m()>(a, s); });
 }
 
-extern "C" int psvo_bsim_backward_wobs(
+extern "C" int PSVO_WBS_ENTRY(psvo_bsim_backward_wobs)(
     const psvo_desc* desc, const float* Fm, const float* logW, const float* lse, const psvo_mlp* f, const psvo_mlp* g,
     const psvo_mlp* q1_inv, const float* sig_f, const float* sig_g, const float* sig_q1inv, const float* sig_bq2,
     const float* bmu2, const float* minit, const float* sig_init, const float* imean, const float* isig, const float* obs,
@@ -916,7 +998,7 @@ extern "C" int psvo_bsim_backward_wobs(
     float* dminit_rows, float* dimean_rows, float* dFm, float* dlogW, float* dlse, float* dsig_f, float* dsig_g,
     float* dsig_q1inv, float* dsig_bq2, float* dsig_init, float* disig, float* ws, void* stream) {
     using namespace psvo;
-    using namespace psvo::wbs;
+    using namespace psvo::PSVO_WBS;
     if (!desc_emission_ok(desc, 2)) return PSVO_ERR_UNSUPPORTED;
     if (!desc || !Fm || !logW || !lse || !f || !g || !q1_inv || !sig_f || !sig_g || !sig_q1inv || !sig_bq2 || !bmu2 ||
         !minit || !sig_init || !imean || !isig || !obs || !eps_b || !bwX || !sel || !lam2_all || !om_all || !mu1_all ||

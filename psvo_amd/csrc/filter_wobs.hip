@@ -18,7 +18,8 @@
 // The two filter kernels live in filter_wobs_impl.h, compiled twice: as they were, and in their adaptive-resampling form
 // (psvo_filter_forward_wobs_adaptive / psvo_filter_backward_wobs_adaptive: 18 forward and 18 reverse kernels more, no EXT form).
 // A third compilation is the missing-observation form (psvo_filter_forward_wobs_missing / psvo_filter_backward_wobs_missing: a NaN
-// in obs is an observation that was not made; 1 <= Dy <= 32; 18 forward and 18 reverse kernels more, no EXT form).
+// in obs is an observation that was not made; 1 <= Dy <= 32; 18 forward and 36 reverse kernels more: the EXT forms sit behind
+// psvo_filter_backward_wobs_missing_ext, for the missing-observation backward simulation of bsim_wobs_ms.hip).
 // A fourth is both at once (psvo_filter_forward_wobs_missing_adaptive / psvo_filter_backward_wobs_missing_adaptive: the adaptive
 // argument blocks, the missing-observation form's LDS; 1 <= Dy <= 32; 18 forward and 18 reverse kernels more, no EXT form).
 #include "wobs_common.h"
@@ -158,10 +159,14 @@ static int launch_bwd(const BwdArgsT<AD>& a, const BwdOut& o, hipStream_t stream
         (void)ext;
         if (a.emission == 2) hipLaunchKernelGGL((filter_bwd_wobs_msad_kernel<DX, H, false, true>), dim3(a.B), dim3(NT), lds, stream, a);
         else hipLaunchKernelGGL((filter_bwd_wobs_msad_kernel<DX, H, false, false>), dim3(a.B), dim3(NT), lds, stream, a);
-    } else if constexpr (MS) {     // (no EXT form: no backward simulation runs behind the missing-observation filter)
-        (void)ext;
-        if (a.emission == 2) hipLaunchKernelGGL((filter_bwd_wobs_ms_kernel<DX, H, false, true>), dim3(a.B), dim3(NT), lds, stream, a);
-        else hipLaunchKernelGGL((filter_bwd_wobs_ms_kernel<DX, H, false, false>), dim3(a.B), dim3(NT), lds, stream, a);
+    } else if constexpr (MS) {     // (EXT: psvo_filter_backward_wobs_missing_ext, the missing backward simulation behind it)
+        if (a.emission == 2) {
+            if (ext) hipLaunchKernelGGL((filter_bwd_wobs_ms_kernel<DX, H, true, true>), dim3(a.B), dim3(NT), lds, stream, a);
+            else hipLaunchKernelGGL((filter_bwd_wobs_ms_kernel<DX, H, false, true>), dim3(a.B), dim3(NT), lds, stream, a);
+        } else {
+            if (ext) hipLaunchKernelGGL((filter_bwd_wobs_ms_kernel<DX, H, true, false>), dim3(a.B), dim3(NT), lds, stream, a);
+            else hipLaunchKernelGGL((filter_bwd_wobs_ms_kernel<DX, H, false, false>), dim3(a.B), dim3(NT), lds, stream, a);
+        }
     } else if constexpr (AD) {     // (no EXT form: no backward simulation runs behind an adaptive filter)
         (void)ext;
         if (a.emission == 2) hipLaunchKernelGGL((filter_bwd_wobs_ad_kernel<DX, H, false, true>), dim3(a.B), dim3(NT), lds, stream, a);
@@ -559,6 +564,19 @@ extern "C" int psvo_filter_backward_wobs_missing(
     return filter_backward_wobs_checked(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, fm0, fsig0, obs, eps, X, Fm,
                                         P1, logW, lse, idx, dlse, 0, nullptr, nullptr, dP, dF, dG, dmu2, dm0, dfm0, dsig_q1,
                                         dsig_q2, dsig_f, dsig_g, dsig0, dfsig0, ws, nullptr, stream, true);
+}
+
+// (the EXT = true instantiations of filter_bwd_wobs_ms_kernel when dFm_ext or dlogW_ext is given: 18 kernels, no new text)
+extern "C" int psvo_filter_backward_wobs_missing_ext(
+    const psvo_desc* desc, const psvo_mlp* q1, const psvo_mlp* f, const psvo_mlp* g, const float* sig_q1,
+    const float* sig_q2, const float* sig_f, const float* sig_g, const float* mu2, const float* m0, const float* sig0,
+    const float* fm0, const float* fsig0, const float* obs, const float* eps, const float* X, const float* Fm,
+    const float* P1, const float* logW, const float* lse, const int32_t* idx, const float* dlse, int nparts,
+    const float* dFm_ext, const float* dlogW_ext, float* dP, float* dF, float* dG, float* dmu2, float* dm0, float* dfm0,
+    float* dsig_q1, float* dsig_q2, float* dsig_f, float* dsig_g, float* dsig0, float* dfsig0, float* ws, void* stream) {
+    return filter_backward_wobs_checked(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, fm0, fsig0, obs, eps, X, Fm,
+                                        P1, logW, lse, idx, dlse, nparts, dFm_ext, dlogW_ext, dP, dF, dG, dmu2, dm0, dfm0,
+                                        dsig_q1, dsig_q2, dsig_f, dsig_g, dsig0, dfsig0, ws, nullptr, stream, true);
 }
 
 extern "C" int psvo_filter_backward_wobs_ext(

@@ -92,13 +92,17 @@ DEFINITIONS = [
     ("particle_forecast", bool, False, "evaluate the k-step predictive mean, variance and log-density of the whole particle cloud"),
     ("forecast_noise", bool, True, "--particle_forecast: apply transition noise to every particle (off: noise-free propagation)"),
     # missing observations (not in the reference's registry, whose data are dense): a NaN in the observations is an entry that was
-    # not observed; its term is left out of the emission log-density.  Filter objectives (SVO, AESMC, IWAE), 1 <= Dy <= 32
+    # not observed; its term is left out of the emission log-density.  Filter objectives (SVO, AESMC, IWAE), 1 <= Dy <= 32 (PSVO:
+    # with --BSim_missing_obs, below)
     ("missing_obs", bool, False, "SVO / AESMC / IWAE: a NaN observation is missing, the ELBO bounds the density of the observed entries"),
     ("missing_rate", float, 0.0, "--generateTrainingData --missing_obs: knock entries out independently with this probability, in [0, 1)"),
     # (not in the reference's registry) the two features gappy data needs beside --missing_obs, each on a missing-observation form
     # of its kernel.  Off by default: without them the combinations stay refused
     ("resample_ess_missing_obs", bool, False, "SVO / AESMC: run --resample_ess with --missing_obs on the adaptive missing-observation kernels"),
     ("particle_forecast_missing_obs", bool, False, "run --particle_forecast with --missing_obs: lpd over the observed entries of each target row"),
+    # (not in the reference's registry) PSVO on gappy data: the missing-observation filter, then the wide backward simulation in its
+    # missing-observation form, at every 1 <= Dy <= 32.  Off by default: without it --missing_obs with --PSVO stays refused
+    ("BSim_missing_obs", bool, False, "PSVO: run --missing_obs on the missing-observation backward-simulation kernels (1 <= Dy <= 32)"),
     # MAP trajectory for the filter objectives (not in the reference's registry, which has no decoder): the single most probable
     # path through the filter's particles (particle Viterbi).  Off by default, evaluation only
     ("MAP_path", bool, False, "SVO / AESMC / IWAE: return the most probable trajectory through the filter's particles (particle Viterbi)"),

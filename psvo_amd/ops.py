@@ -370,6 +370,13 @@ def bsim_forward_wobs(*args, **kw):
     return bsim_forward(*args, entry="psvo_bsim_forward_wobs", **kw)
 
 
+def bsim_forward_wobs_missing(*args, **kw):
+    """psvo_bsim_forward_wobs_missing: bsim_forward_wobs where a NaN in obs (T,B,Dy) is an observation that was not made -- its
+    term is left out of the emission log-density (1 <= Dy <= 32, one hidden layer, every emission form); arguments, outputs and
+    layouts of bsim_forward."""
+    return bsim_forward(*args, entry="psvo_bsim_forward_wobs_missing", **kw)
+
+
 def elbo_filter(desc, lse):
     lib = _lib.load()
     _chk(lse, (desc.T, desc.B), "lse")
@@ -541,9 +548,10 @@ def filter_backward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0,
     kernel adds in part order.  Returns a dict of gradients.
     wobs: psvo_filter_backward_wobs + psvo_mlp_wgrad_wobs for MLP_g (wide observations); with dFm / dlogW -- a backward
     simulation ran behind the wide filter -- or with ext=True, psvo_filter_backward_wobs_ext.
-    missing (with wobs): psvo_filter_backward_wobs_missing, 1 <= Dy <= 32, dlse only; MLP_g's weight gradient from the d G rows is
+    missing (with wobs): psvo_filter_backward_wobs_missing, 1 <= Dy <= 32 (with dFm / dlogW or ext=True -- the missing-observation
+    backward simulation ran behind it -- psvo_filter_backward_wobs_missing_ext); MLP_g's weight gradient from the d G rows is
     psvo_mlp_wgrad_wobs for Dy >= 3 and the plain psvo_mlp_wgrad for Dy <= 2; with adaptive="wobs" as well,
-    psvo_filter_backward_wobs_missing_adaptive, following filt["rs"]."""
+    psvo_filter_backward_wobs_missing_adaptive, following filt["rs"] (dlse only)."""
     lib = _lib.load()
     B, T, N, Dx, Dy, H = desc.B, desc.T, desc.N, desc.Dx, desc.Dy, desc.H
     dev = eps.device
@@ -564,10 +572,11 @@ def filter_backward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0,
     wide_g = wobs                # MLP_g's weight gradient on psvo_mlp_wgrad_wobs
     if missing:
         # (adaptive == "wobs" with missing: filter_backward_wobs_missing_adaptive, below)
-        if not wobs or (adaptive and adaptive != "wobs") or ext:
-            raise ValueError("filter_backward: missing observations run on the wide-observation route (wobs=True) with the upstream "
-                             "gradient dlse only, resampling at every step or never (no adaptive form, no gradients of Fm / logW)")
-        name, wide_g = "psvo_filter_backward_wobs_missing", Dy >= 3
+        if not wobs or (adaptive and adaptive != "wobs") or (ext and adaptive):
+            raise ValueError("filter_backward: missing observations run on the wide-observation route (wobs=True), resampling at "
+                             "every step or never; the adaptive form takes the upstream gradient dlse only (no gradients of "
+                             "Fm / logW)")
+        name, wide_g = "psvo_filter_backward_wobs_missing_ext" if ext else "psvo_filter_backward_wobs_missing", Dy >= 3
     decisions = ()
     if adaptive and missing:
         if filt.get("rs") is None:
@@ -1095,10 +1104,12 @@ def bsim_backward(desc, filt, f, g, q1_inv, sig_f, sig_g, sig_q1inv, sig_bq2, bm
 
 
 def bsim_backward_wobs(desc, filt, f, g, q1_inv, sig_f, sig_g, sig_q1inv, sig_bq2, bmu2, minit, sig_init, imean, isig,
-                       obs, eps_b, bs, dscore):
+                       obs, eps_b, bs, dscore, missing=False):
     """psvo_bsim_backward_wobs + psvo_mlp_wgrad (f, q1_inv) + psvo_mlp_wgrad_wobs (g): the reverse of bsim_forward_wobs.
     `bs` = bsim_forward_wobs(..., save=True) outputs.  One stream; the result has bsim_backward's keys (no partials: the
-    entry point folds them itself)."""
+    entry point folds them itself).
+    missing: psvo_bsim_backward_wobs_missing, the reverse of bsim_forward_wobs_missing (1 <= Dy <= 32); MLP_g's weight gradient
+    from the d G rows is psvo_mlp_wgrad_wobs for Dy >= 3 and the plain psvo_mlp_wgrad for Dy <= 2."""
     lib = _lib.load()
     B, T, N, M, Dx, Dy, H = desc.B, desc.T, desc.N, desc.M, desc.Dx, desc.Dy, desc.H
     dev = eps_b.device
@@ -1111,8 +1122,9 @@ def bsim_backward_wobs(desc, filt, f, g, q1_inv, sig_f, sig_g, sig_q1inv, sig_bq
     out = _bsim_grads(desc, dev, 0, (("dFm", (T, B, Dx, N)), ("dlogW", (T, B, N)), ("dlse", (T, B))))
     _chain_rows(out, z, T, B, Dx, N)
     ws = z(max(1, lib.psvo_bsim_wobs_ws_floats(B, T, N, M, Dx, Dy)))
+    name = "psvo_bsim_backward_wobs_missing" if missing else "psvo_bsim_backward_wobs"
     _launch(
-        "psvo_bsim_backward_wobs", lib.psvo_bsim_backward_wobs,
+        name, getattr(lib, name),
         ctypes.byref(desc), _ptr(filt["Fm"]), _ptr(filt["logW"]), _ptr(filt["lse"]),
         ctypes.byref(fs), ctypes.byref(gs), ctypes.byref(qs),
         _ptr(sig_f), _ptr(sig_g), _ptr(sig_q1inv), _ptr(sig_bq2), _ptr(bmu2), _ptr(minit), _ptr(sig_init),
@@ -1125,9 +1137,15 @@ def bsim_backward_wobs(desc, filt, f, g, q1_inv, sig_f, sig_g, sig_q1inv, sig_bq
         _ptr(out["disig"]), _ptr(ws), _stream())
     # weight gradients from rows: MLP_g's through the wide-output kernel with L = N M rows per (t, b) segment
     out["gf"] = mlp_wgrad(out["xt"][:T - 1], out["dFt"][:T - 1], f, Dx, H, Dx)
-    out["gg"] = mlp_wgrad(out["xt"], out["dGt"], g, Dx, H, Dy, wobs=True)
+    out["gg"] = mlp_wgrad(out["xt"], out["dGt"], g, Dx, H, Dy, wobs=not missing or Dy >= 3)
     out["gq1inv"] = mlp_wgrad(bs["bwX"][1:], out["dmu1"][:T - 1], q1_inv, Dx, H, Dx)
     return out
+
+
+def bsim_backward_wobs_missing(*args, **kw):
+    """psvo_bsim_backward_wobs_missing + the weight gradients: the reverse of bsim_forward_wobs_missing; arguments and result of
+    bsim_backward_wobs."""
+    return bsim_backward_wobs(*args, missing=True, **kw)
 
 
 def bsimwr_forward(desc, filt, f, g, q1_inv, sig_f, sig_g, sig_q1inv, sig_bq2, bmu2, minit, sig_init,

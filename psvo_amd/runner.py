@@ -111,7 +111,8 @@ def main(FLAGS):
                       particle_forecast=bool(getattr(FLAGS, "particle_forecast", False)), output_cov=bool(FLAGS.output_cov),
                       Dy=FLAGS.Dy, layers=[FLAGS.q1_layers, FLAGS.g_layers] + ([] if FLAGS.use_bootstrap else [FLAGS.f_layers]),
                       resample_ess_missing_obs=bool(getattr(FLAGS, "resample_ess_missing_obs", False)),
-                      particle_forecast_missing_obs=bool(getattr(FLAGS, "particle_forecast_missing_obs", False)))
+                      particle_forecast_missing_obs=bool(getattr(FLAGS, "particle_forecast_missing_obs", False)),
+                      bsim_missing_obs=bool(getattr(FLAGS, "BSim_missing_obs", False)), cross_chain=bool(FLAGS.PSVOwR))
     check_map_path(bool(getattr(FLAGS, "MAP_path", False)), backward_simulation=bool(FLAGS.PSVO or FLAGS.PSVOwR),
                    output_cov=bool(FLAGS.output_cov), Dy=FLAGS.Dy,
                    layers=[FLAGS.q1_layers, FLAGS.g_layers] + ([] if FLAGS.use_bootstrap else [FLAGS.f_layers]))

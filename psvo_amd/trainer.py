@@ -42,8 +42,9 @@ calibration mean((y - y_mean)^2 / y_var) (about 1 when calibrated) are printed a
 forecast_R_square_<split>, forecast_calibration_<split>; y_hat_<epoch>.p gains y_mean and y_var of the saved sequences.
 Training steps are untouched.
 
-Missing observations (FLAGS.missing_obs, off by default; SVO / AESMC / IWAE): a NaN observation was not made; training and evaluation
-run the missing-observation filter kernels, and the ELBO bounds the log-density of the observed entries.  The k-step R-square takes
+Missing observations (FLAGS.missing_obs, off by default; SVO / AESMC / IWAE, and PSVO with FLAGS.BSim_missing_obs): a NaN observation
+was not made; training and evaluation run the missing-observation filter kernels (PSVO: and the missing-observation backward
+simulation behind them), and the ELBO bounds the log-density of the observed entries.  The k-step R-square takes
 residuals and the centring mean over observed targets only; at every evaluation the share of missing entries of each split is
 printed and goes into metric_<iter>.p as missing_share_<split>.  y_hat at k = 0 is the model's imputation and is saved as before.
 With FLAGS.resample_ess_missing_obs the adaptive metrics above are reported beside it; with FLAGS.particle_forecast_missing_obs the
