@@ -87,43 +87,7 @@ __device__ __forceinline__ float rs_bit2(float lo, float hi) {   // banks 0,2: l
                  : "=&v"(r) : "v"(lo), "v"(hi));
     return r;
 }
-// v + v(lane ^ MASK) in every lane, bit for bit what  v + xor_lane<MASK>(v)  gives (the two terms may swap places).  With
-// BOTH operands of a stage above the lane's own value no select is left over: lane bit 2 is the two bank-masked DPP adds
-// (xor_lane<4>: copy, two DPP moves, add), lane bits 4 and 5 one copy, the swap and the add (xor_lane<16>: two copies, the
-// swap, a select on the lane's row, the add).
-template <int MASK>
-__device__ __forceinline__ float add_xor(float v) {
-    if constexpr (MASK == 4) {
-        float r;
-        asm("s_nop 1\n\t"
-            "v_add_f32_dpp %0, %1, %1 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"
-            "v_add_f32_dpp %0, %1, %1 row_shr:4 row_mask:0xf bank_mask:0xa"
-            : "=&v"(r) : "v"(v));
-        return r;
-    } else if constexpr (MASK == 16) {
-        float w = v;
-        asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(v), "+v"(w));
-        return v + w;
-    } else if constexpr (MASK == 32) {
-        float w = v;
-        asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(v), "+v"(w));
-        return v + w;
-    } else {
-        return v + xor_lane<MASK>(v);
-    }
-}
-// common.h: group_sum, on add_xor
-template <int G>
-__device__ __forceinline__ float group_sum2(float v) {
-    if constexpr (G > 1) v = add_xor<1>(v);
-    if constexpr (G > 2) v = add_xor<2>(v);
-    if constexpr (G > 4) v = add_xor<4>(v);
-    if constexpr (G > 8) v = add_xor<8>(v);
-    if constexpr (G > 16) v = add_xor<16>(v);
-    if constexpr (G > 32) v = add_xor<32>(v);
-    return v;
-}
-
+// (add_xor<MASK>, group_sum2<G>: common.h)
 template <int K>
 __device__ __forceinline__ void row_reduce_scatter(const float (&v)[4 * K], float (&out)[K]) {
     float h[2 * K];

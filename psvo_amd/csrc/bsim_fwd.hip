@@ -79,6 +79,13 @@ __global__ void __launch_bounds__(256, (kBsimFwdWaves<DX, DY, H, M, HS>)) bsim_f
     constexpr int PS = TileSlot<DX>::kFloats;
     constexpr int kMaxStage = 4;
     constexpr bool kRolled = (2 * MQ::kSize + MG::kSize) > 330;
+    // the forms of profiles/bsim_fwd_valu_diet.md (cross-lane sums and maxima on add_xor / max_xor, the cross-half add of the merge
+    // behind the select, the first 16-entry block without a rescale) hold for the one-hidden-layer unit.  In the two-layer
+    // unit each of them alone cost some instantiation scalar registers or scratch (the note's table): it keeps the plain forms.
+    constexpr bool kDiet = PSVO_L == 1;
+    // the first-block form only with two half-chains: with whole chains (HS = 1, four and more blocks per step, where it saves
+    // the least) hipcc allocated the kernel 166 registers instead of 235 and the C4 step got 0.8 % slower
+    constexpr bool kFirstBlock = kDiet && HS == 2;
     constexpr bool kPeel = (DX <= 3);   // (the Dx = 4 kernel measured slower peeled: C5 14.4 -> 17.6 ms)
     extern __shared__ __attribute__((aligned(16))) float smem[];
 
@@ -341,7 +348,7 @@ __global__ void __launch_bounds__(256, (kBsimFwdWaves<DX, DY, H, M, HS>)) bsim_f
                 constexpr int kQS = (H / 4 < G) ? H / 4 : G;
                 MQ::template eval_part<kQS>(wqi, (tid % G) & (kQS - 1), xp, m1);
 #pragma unroll
-                for (int d = 0; d < DX; ++d) m1[d] = group_sum<kQS>(m1[d]);
+                for (int d = 0; d < DX; ++d) m1[d] = kDiet ? group_sum2<kQS>(m1[d]) : group_sum<kQS>(m1[d]);
             }
             if (stores(kMu1)) {
 #pragma unroll
@@ -365,7 +372,7 @@ __global__ void __launch_bounds__(256, (kBsimFwdWaves<DX, DY, H, M, HS>)) bsim_f
             } else {
                 MQ::template eval_part<HS, ilog2(M)>(wf, hpart, x, fmx);
 #pragma unroll
-                for (int d = 0; d < DX; ++d) fmx[d] += xor_lane<M>(fmx[d]);
+                for (int d = 0; d < DX; ++d) fmx[d] = kDiet ? add_xor<M>(fmx[d]) : fmx[d] + xor_lane<M>(fmx[d]);
             }
             phi = diag_lp<DX>(xp, fmx, isf, kf);
         }
@@ -375,7 +382,7 @@ __global__ void __launch_bounds__(256, (kBsimFwdWaves<DX, DY, H, M, HS>)) bsim_f
         } else {
             MG::template eval_part<HS, ilog2(M)>(wg, hpart, x, gm);
 #pragma unroll
-            for (int k = 0; k < DY; ++k) gm[k] += xor_lane<M>(gm[k]);
+            for (int k = 0; k < DY; ++k) gm[k] = kDiet ? add_xor<M>(gm[k]) : gm[k] + xor_lane<M>(gm[k]);
         }
         if (a.emission) {
 #pragma unroll
@@ -409,8 +416,11 @@ __global__ void __launch_bounds__(256, (kBsimFwdWaves<DX, DY, H, M, HS>)) bsim_f
             f2 mxa = f2{ninf, ninf}, mxb = mxa, sma = f2{0.f, 0.f}, smb = sma;
             const int nqh = (NP >> 2) / HS;       // forward-tile entries per quad lane and half (multiple of 4)
             const int j0 = hpart * nqh;
-            auto block = [&](auto jb_tag, int k0) {
+            // (the first block of a step takes its sums from its own exponentials and its maximum as the running one:
+            //  0 * exp2(-inf - base) + x == x bit for bit, so the rescale of sums that are still zero is left out)
+            auto block = [&](auto jb_tag, auto first_tag, int k0) {
                 constexpr int JB = decltype(jb_tag)::value;
+                constexpr bool kFirst = decltype(first_tag)::value;
                 f2 va[JB], vb[JB];
                 f2 bma = f2{ninf, ninf}, bmb = bma;
 #pragma unroll
@@ -441,50 +451,86 @@ __global__ void __launch_bounds__(256, (kBsimFwdWaves<DX, DY, H, M, HS>)) bsim_f
                     bma = pk_max(bma, la);
                     bmb = pk_max(bmb, lb);
                 }
-                const f2 nma = pk_max(mxa, bma), nmb = pk_max(mxb, bmb);
+                f2 nma = bma, nmb = bmb;
+                if constexpr (!kFirst) {
+                    nma = pk_max(mxa, bma);
+                    nmb = pk_max(mxb, bmb);
+                }
                 // nm == -inf only if every term so far is -inf: keep s = 0 without NaNs
                 const f2 ba = f2{nma.x == ninf ? 0.f : nma.x, nma.y == ninf ? 0.f : nma.y};
                 const f2 bb = f2{nmb.x == ninf ? 0.f : nmb.x, nmb.y == ninf ? 0.f : nmb.y};
-                const f2 ra = mxa - ba, rb = mxb - bb;
-                sma = sma * f2{exp2_fast(ra.x), exp2_fast(ra.y)};
-                smb = smb * f2{exp2_fast(rb.x), exp2_fast(rb.y)};
+                if constexpr (!kFirst) {
+                    const f2 ra = mxa - ba, rb = mxb - bb;
+                    sma = sma * f2{exp2_fast(ra.x), exp2_fast(ra.y)};
+                    smb = smb * f2{exp2_fast(rb.x), exp2_fast(rb.y)};
+                }
 #pragma unroll
                 for (int c = 0; c < JB; ++c) {
                     const f2 da = va[c] - ba, db = vb[c] - bb;
-                    sma += f2{exp2_fast(da.x), exp2_fast(da.y)};
-                    smb += f2{exp2_fast(db.x), exp2_fast(db.y)};
+                    const f2 ea = f2{exp2_fast(da.x), exp2_fast(da.y)}, eb = f2{exp2_fast(db.x), exp2_fast(db.y)};
+                    if (kFirst && c == 0) {
+                        sma = ea;
+                        smb = eb;
+                    } else {
+                        sma += ea;
+                        smb += eb;
+                    }
                 }
                 mxa = nma;
                 mxb = nmb;
             };
-            int k0 = 0;                           // (nqh is wave-uniform and a multiple of 4)
-            for (; k0 + 16 <= nqh; k0 += 16) block(std::integral_constant<int, 16>{}, k0);
+            // (nqh is wave-uniform and a multiple of 4.  Only the 16-entry arm has a first-block form: with one for the 8- and
+            //  the 4-entry arm as well most instantiations spilled two to four scalar registers more, profiles/bsim_fwd_valu_diet.md;
+            //  a slice shorter than 16 entries starts with the general form, which is right for a first block too.)
+            using I16 = std::integral_constant<int, 16>;
+            int k0 = 0;
+            if constexpr (kFirstBlock) {
+                if (nqh >= 16) {
+                    block(I16{}, std::true_type{}, 0);
+                    k0 = 16;
+                }
+            }
+            for (; k0 + 16 <= nqh; k0 += 16) block(I16{}, std::false_type{}, k0);
             if (nqh - k0 >= 8) {
-                block(std::integral_constant<int, 8>{}, k0);
+                block(std::integral_constant<int, 8>{}, std::false_type{}, k0);
                 k0 += 8;
             }
-            if (nqh - k0 >= 4) block(std::integral_constant<int, 4>{}, k0);
+            if (nqh - k0 >= 4) block(std::integral_constant<int, 4>{}, std::false_type{}, k0);
             SEC(4);   // pair loop
             const float mx[4] = {mxa.x, mxa.y, mxb.x, mxb.y};
             const float sm[4] = {sma.x, sma.y, smb.x, smb.y};
             // merge the four j-slices of the quad (lane q keeps sub-particle i == q) and the chain's halves:
-            // common maximum first, then ONE rescale of the lane's own sum and plain adds
+            // common maximum first, then ONE rescale of the lane's own sum and plain adds.  The maxima are all-reduced over
+            // the quad and the halves (every lane rescales all four of its sums); the sums are all-reduced over the quad
+            // only, and the other half's quad sum is added to the ONE sum the lane keeps (the partner lane, lane ^ M, has
+            // the same q): (quad sum) + (other half's quad sum), as before.
             float lm = ninf, ls = 0.f;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                float gm = fmaxf(mx[i], xor_lane<1>(mx[i]));
-                gm = fmaxf(gm, xor_lane<2>(gm));
-                if constexpr (HS == 2) gm = fmaxf(gm, xor_lane<M>(gm));
+                float gm;
+                if constexpr (kDiet) {
+                    gm = max_xor<2>(max_xor<1>(mx[i]));
+                    if constexpr (HS == 2) gm = max_xor<M>(gm);
+                } else {
+                    gm = fmaxf(mx[i], xor_lane<1>(mx[i]));
+                    gm = fmaxf(gm, xor_lane<2>(gm));
+                    if constexpr (HS == 2) gm = fmaxf(gm, xor_lane<M>(gm));
+                }
                 const float base = (gm == ninf) ? 0.f : gm;
                 float sc = sm[i] * exp2_fast(mx[i] - base);    // (mx = -inf: sm = 0 and exp2(-inf) = 0)
-                sc += xor_lane<1>(sc);
-                sc += xor_lane<2>(sc);
-                if constexpr (HS == 2) sc += xor_lane<M>(sc);
+                if constexpr (kDiet) {
+                    sc = add_xor<2>(add_xor<1>(sc));
+                } else {
+                    sc += xor_lane<1>(sc);
+                    sc += xor_lane<2>(sc);
+                }
+                if constexpr (HS == 2 && !kDiet) sc += xor_lane<M>(sc);
                 if (i == q) {
                     lm = gm;
                     ls = sc;
                 }
             }
+            if constexpr (HS == 2 && kDiet) ls = add_xor<M>(ls);
             const float lam2 = lm + log2_fast(ls);
             lam = fmaf(kLn2, lam2, kf);
             if (stores(kLam2)) stf(as_global<float>(p_lam2), here(o_nm), lam2);
@@ -495,9 +541,9 @@ __global__ void __launch_bounds__(256, (kBsimFwdWaves<DX, DY, H, M, HS>)) bsim_f
         SEC(5);   // quad / half merges, lam2
         // ---- omega, normalise over the M sub-particles, draw one ---------------------------------------
         const float om_raw = lam + phi + g_lp - q_lp;
-        const float omx = group_max<M>(om_raw);
+        const float omx = kDiet ? group_max2<M>(om_raw) : group_max<M>(om_raw);
         const float pw = exp2_fast((om_raw - omx) * kLog2e);
-        const float cdfv = group_incl_scan<M>(pw, m);  // inclusive scan across the chain's M lanes
+        const float cdfv = kDiet ? group_incl_scan2<M>(pw, m) : group_incl_scan<M>(pw, m);  // inclusive scan across the chain's M lanes
         const float total = __shfl(cdfv, gbase + M - 1);
         const float omega = om_raw - fmaf(kLn2, log2_fast(total), omx);
         if (stores(kOm)) stf(as_global<float>(p_omall), here(o_nm), omega);

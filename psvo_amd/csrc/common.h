@@ -882,6 +882,100 @@ __device__ __forceinline__ float group_incl_scan(float v, int m) {
     return v;
 }
 
+// v + v(lane ^ MASK) in every lane, bit for bit what  v + xor_lane<MASK>(v)  gives (the two terms may swap places).  With
+// BOTH operands of a stage above the lane's own value no select is left over: lane bit 2 is the two bank-masked DPP adds
+// (xor_lane<4>: copy, two DPP moves, add), lane bits 4 and 5 one copy, the swap and the add (xor_lane<16>: two copies, the
+// swap, a select on the lane's row, the add).
+// (s_nop 1: a DPP source, or a swap operand, written by the preceding VALU instruction needs two wait states, which hipcc
+// does not insert inside an asm statement.)
+template <int MASK>
+__device__ __forceinline__ float add_xor(float v) {
+    if constexpr (MASK == 4) {
+        float r;
+        asm("s_nop 1\n\t"
+            "v_add_f32_dpp %0, %1, %1 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"
+            "v_add_f32_dpp %0, %1, %1 row_shr:4 row_mask:0xf bank_mask:0xa"
+            : "=&v"(r) : "v"(v));
+        return r;
+    } else if constexpr (MASK == 16) {
+        float w = v;
+        asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(v), "+v"(w));
+        return v + w;
+    } else if constexpr (MASK == 32) {
+        float w = v;
+        asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(v), "+v"(w));
+        return v + w;
+    } else {
+        return v + xor_lane<MASK>(v);
+    }
+}
+// max(v, v(lane ^ MASK)) in every lane, bit for bit what  fmaxf(v, xor_lane<MASK>(v))  gives for values that are no NaNs.
+// The same structure; the maximum is an instruction of the asm statement (inside a row it carries the DPP modifier itself),
+// because fmaxf on a value that comes out of a DPP move or an asm statement is preceded by a canonicalising v_max x, x, x.
+template <int MASK>
+__device__ __forceinline__ float max_xor(float v) {
+    float r;
+    if constexpr (MASK == 1) {
+        asm("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf" : "=&v"(r) : "v"(v));
+    } else if constexpr (MASK == 2) {
+        asm("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf" : "=&v"(r) : "v"(v));
+    } else if constexpr (MASK == 4) {
+        asm("s_nop 1\n\t"
+            "v_max_f32_dpp %0, %1, %1 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"
+            "v_max_f32_dpp %0, %1, %1 row_shr:4 row_mask:0xf bank_mask:0xa"
+            : "=&v"(r) : "v"(v));
+    } else if constexpr (MASK == 8) {
+        asm("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 row_ror:8 row_mask:0xf bank_mask:0xf" : "=&v"(r) : "v"(v));
+    } else if constexpr (MASK == 16) {
+        r = v;
+        asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\tv_max_f32 %0, %0, %1" : "+v"(r), "+v"(v));
+    } else {
+        static_assert(MASK == 32, "max_xor mask");
+        r = v;
+        asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\tv_max_f32 %0, %0, %1" : "+v"(r), "+v"(v));
+    }
+    return r;
+}
+// group_sum / group_max on add_xor / max_xor
+template <int G>
+__device__ __forceinline__ float group_sum2(float v) {
+    if constexpr (G > 1) v = add_xor<1>(v);
+    if constexpr (G > 2) v = add_xor<2>(v);
+    if constexpr (G > 4) v = add_xor<4>(v);
+    if constexpr (G > 8) v = add_xor<8>(v);
+    if constexpr (G > 16) v = add_xor<16>(v);
+    if constexpr (G > 32) v = add_xor<32>(v);
+    return v;
+}
+template <int G>
+__device__ __forceinline__ float group_max2(float v) {
+    if constexpr (G > 1) v = max_xor<1>(v);
+    if constexpr (G > 2) v = max_xor<2>(v);
+    if constexpr (G > 4) v = max_xor<4>(v);
+    if constexpr (G > 8) v = max_xor<8>(v);
+    if constexpr (G > 16) v = max_xor<16>(v);
+    if constexpr (G > 32) v = max_xor<32>(v);
+    return v;
+}
+
+// group_incl_scan for groups that are whole DPP rows (G >= 16), bit for bit: a lane with m < k is one of the first k lanes of
+// its row, where row_shr:k with bound_ctrl already reads zero, so the selects of group_incl_scan choose between zero and
+// zero, and every stage is one DPP add (wave_incl_scan's).  Narrower groups keep the selects.
+template <int G>
+__device__ __forceinline__ float group_incl_scan2(float v, int m) {
+    if constexpr (G >= 16) {
+        v += dpp_mov<0x111, 0xF, 0xF, true>(0.f, v);        // row_shr:1
+        v += dpp_mov<0x112, 0xF, 0xF, true>(0.f, v);        // row_shr:2
+        v += dpp_mov<0x114, 0xF, 0xF, true>(0.f, v);        // row_shr:4
+        v += dpp_mov<0x118, 0xF, 0xF, true>(0.f, v);        // row_shr:8
+        if constexpr (G > 16) v += dpp_mov<0x142, 0xA, 0xF, false>(0.f, v);   // row_bcast:15 -> rows 1, 3
+        if constexpr (G > 32) v += dpp_mov<0x143, 0xC, 0xF, false>(0.f, v);   // row_bcast:31 -> rows 2, 3
+        return v;
+    } else {
+        return group_incl_scan<G>(v, m);
+    }
+}
+
 // value of lane `src` (wave-uniform index) in every lane
 __device__ __forceinline__ float lane_bcast(float v, int src) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), src));
