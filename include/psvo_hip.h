@@ -899,6 +899,60 @@ int psvo_filter_backward_wobs_missing(const psvo_desc* desc,
                               float* ws, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Exogenous inputs (added within ABI 6: purely additive).  psvo_filter_forward_wobs_missing / psvo_filter_backward_wobs_missing
+ * with input-driven transitions.  v (B,T,Di) is data, given and finite.  The first layer of the per-particle networks q1 and f
+ * (one network under bootstrap) is W1 (Dx + Di, H), keras layout, applied to concat[x_t, v_t]:
+ *     MLP(x_t[n]; v_t) = relu(x_t[n] W1[:Dx] + (b1 + v_t W1[Dx:])) W2 + b2
+ *     x_{t+1} ~ f(. | x_t, v_t),   proposal q1(. | x_t, v_t),   Fm[t] = MLP_f(X_t; v_t),   P1[t] = MLP_q1(X_t; v_t)
+ *   so v_t drives the step from t to t + 1, and v_{T-1} is read (into Fm[T-1]) but matters only to prediction.  The t = 0 terms
+ *   m0 / fm0 are the caller's, evaluated with a zero input.  The emission, q0 and q2 do not see v.
+ *   The kernels do not take v: the input's share of the hidden pre-activation does not depend on the particle, and the caller
+ *   passes it as hb_q1, hb_f (T,B,H), hb[t,b,:] = v[b,t,:] W1[Dx:] (zero in hidden units beyond the model's width), with the
+ *   psvo_mlp structs holding W1[:Dx] (Dx,H).  The effective first-layer bias of step t is b1[k] + hb[t,b,k]: ONE fp32 add per
+ *   word, made by the lane that stages it, then used as b1 is; a reference that rounds b1 + hb once and adds x W1[:Dx] to it
+ *   follows the kernels exactly, and hb = 0 reproduces the missing-observation pair bit for bit.
+ *  forward:  the arguments of psvo_filter_forward_wobs_missing, then hb_q1, hb_f.  hb_q1 is required; hb_f is required unless
+ *            desc->bootstrap, where it is ignored.  Same outputs and layouts.
+ *  reverse:  the arguments of psvo_filter_backward_wobs_missing, then hb_q1, hb_f; upstream gradient dlse only.  The relu masks
+ *            of step t use the bias row of step t.  dP / dF are the rows d MLP_q1 / d MLP_f as always; the gradients of W1[:Dx],
+ *            b1, W2, b2 and of hb come from psvo_mlp_wgrad_rowbias below, and d W1[Dx:] = sum_{t,b} v[b,t,:]^T d hb[t,b,:],
+ *            d v[b,t,:] = d hb[t,b,:] W1[Dx:]^T are plain matrix products of the caller.
+ *  Envelope: that of the missing-observation pair (1 <= Dy <= 32, Dx in {2,3,4}, H in {16,32,64}, N <= 512, one hidden layer,
+ *  emission 0 / 1 / 2; anything else PSVO_ERR_UNSUPPORTED; a missing required pointer, B <= 0, T < 2 or N <= 0
+ *  PSVO_ERR_INVALID), both before a device is touched.
+ *
+ * psvo_mlp_wgrad_rowbias: psvo_mlp_wgrad (Din, Dout <= 4, H in {16,32,64}) for a first-layer bias that changes with the segment,
+ *   hb (S,H): the hidden layer of segment s is recomputed with b1 + hb[s] (the same single add).  grad = [dW1|db1|dW2|db2] as
+ *   before (db1 = sum over all rows of d pre; accumulate applies to grad only); dhb (S,H) = sum_l d pre[s,l,:] is written, never
+ *   accumulated.  Orders: a lane adds its rows l = lane, lane + 64, .. in that order, a segment's sum folds the 64 lanes in lane
+ *   order; grad folds lanes, then the four waves of a workgroup in wave order, then the workgroups in workgroup order.  No float
+ *   atomics: two calls on the same inputs are bit-identical.  partial: psvo_mlp_wgrad_rowbias_blocks(S) * len(grad) floats.
+ * ------------------------------------------------------------------------------------------- */
+int psvo_filter_forward_wobs_input(const psvo_desc* desc,
+                             const psvo_mlp* q1, const psvo_mlp* f, const psvo_mlp* g,
+                             const float* sig_q1, const float* sig_q2, const float* sig_f, const float* sig_g,
+                             const float* mu2,
+                             const float* m0, const float* sig0, const float* fm0, const float* fsig0,
+                             const float* obs, const float* eps, const float* u, const int32_t* idx_in,
+                             float* X, float* Xanc, float* Fm, float* P1, float* logW, int32_t* idx_out,
+                             float* lse, const float* hb_q1, const float* hb_f, void* stream);
+int psvo_filter_backward_wobs_input(const psvo_desc* desc,
+                              const psvo_mlp* q1, const psvo_mlp* f, const psvo_mlp* g,
+                              const float* sig_q1, const float* sig_q2, const float* sig_f, const float* sig_g,
+                              const float* mu2,
+                              const float* m0, const float* sig0, const float* fm0, const float* fsig0,
+                              const float* obs, const float* eps,
+                              const float* X, const float* Fm, const float* P1, const float* logW, const float* lse,
+                              const int32_t* idx, const float* dlse,
+                              float* dP, float* dF, float* dG, float* dmu2, float* dm0, float* dfm0,
+                              float* dsig_q1, float* dsig_q2, float* dsig_f, float* dsig_g, float* dsig0, float* dfsig0,
+                              float* ws, const float* hb_q1, const float* hb_f, void* stream);
+int psvo_mlp_wgrad_rowbias_blocks(long long S);
+int psvo_mlp_wgrad_rowbias(long long S, int L, int Din, int H, int Dout, const float* X, const float* dOut,
+                           const float* hb, const psvo_mlp* w, float* partial, float* grad, float* dhb,
+                           int accumulate, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Adaptive resampling on missing observations (added within ABI 6: purely additive).  The intersection of the two sections
  * above and nothing new: psvo_filter_forward_wobs_missing / psvo_filter_backward_wobs_missing -- a NaN in obs is left out of
  * log g, a step with nothing observed has log g = 0 exactly -- with the decision of psvo_filter_forward_wobs_adaptive, word for

@@ -10,8 +10,8 @@ import torch
 
 from .. import ops
 from ..autograd import (FilterAdaptiveFunction, FilterCovFunction, FilterFunction, FilterWobsAdaptiveFunction,
-                        FilterWobsFunction, FilterWobsMissingAdaptiveFunction, FilterWobsMissingBsimFunction,
-                        FilterWobsMissingFunction)
+                        FilterWobsFunction, FilterWobsInputFunction, FilterWobsMissingAdaptiveFunction,
+                        FilterWobsMissingBsimFunction, FilterWobsMissingFunction)
 
 
 def check_resample_ess(raw, never_resamples=False, backward_simulation=False, output_cov=False, Dy=1, plain_dy=2,
@@ -111,6 +111,39 @@ def check_missing_obs(on, missing_rate=0.0, backward_simulation=False, resample_
     return True
 
 
+def check_inputs(Di, backward_simulation=False, resample_ess=0.0, particle_forecast=False, output_cov=False, Dy=1, layers=(),
+                 wobs_max_dy=32):
+    """--Di (the width of the exogenous input v_t that drives f and q1) as an int, 0 = off.  ValueError, naming the limit, for a
+    negative width and for everything the input-driven kernels (psvo_filter_forward_wobs_input) do not cover (runner.main calls
+    this on the flags before it touches a device, SVO.__init__ on the model it is given).  `layers`: the hidden layers of the
+    per-particle MLPs, one each."""
+    Di = int(0 if Di is None else Di)
+    if Di < 0:
+        raise ValueError("--Di = %d: the input dimension is a count, Di >= 0 (0 = autonomous dynamics)" % Di)
+    if Di == 0:
+        return 0
+    limit = "exogenous inputs run on psvo_filter_forward_wobs_input, the filter of SVO / AESMC / IWAE"
+    if backward_simulation:
+        raise ValueError("--Di with --PSVO / --PSVOwR: %s; the backward simulations' own proposal networks have no input form"
+                         % limit)
+    if float(resample_ess or 0.0) != 0.0:
+        raise ValueError("--Di with --resample_ess: %s, which resamples at every step (or never); the adaptive kernels have no "
+                         "input form" % limit)
+    if particle_forecast:
+        raise ValueError("--Di with --particle_forecast: the forecast kernel (psvo_particle_forecast) propagates the cloud through "
+                         "an autonomous f; it has no input form")
+    if output_cov:
+        raise ValueError("--Di with output_cov: %s, which takes state-independent scales; the state-dependent-scale kernels have "
+                         "no input form" % limit)
+    deep = [v for v in (_layer_list(s) for s in layers) if len(v) != 1]
+    if deep:
+        raise ValueError("--Di with per-particle MLP layers %s: %s, which takes one hidden layer per MLP; two hidden layers have "
+                         "no input form" % (deep, limit))
+    if Dy > wobs_max_dy or Dy < 1:
+        raise ValueError("--Di with Dy = %d: %s, which takes 1 <= Dy <= %d; no fallback path exists" % (Dy, limit, wobs_max_dy))
+    return Di
+
+
 def check_map_path(on, backward_simulation=False, output_cov=False, Dy=1, layers=(), wobs_max_dy=32):
     """--MAP_path (the most probable trajectory through the filter's particles, psvo_map_path) as a bool.  ValueError, naming the
     limit, for everything the kernel does not cover (runner.main calls this on the flags before it touches a device, SVO.__init__
@@ -155,7 +188,10 @@ class SVO:
         self.model = model
         # missing observations (FLAGS.missing_obs, not in the reference): a NaN observation is left out of the emission density
         self.missing_obs = self._route_missing_obs(model, FLAGS)
-        self.wide_obs = self._route_wide_obs(model, bool(getattr(FLAGS, "BSim_wide_obs", False)), self.missing_obs)
+        # exogenous inputs (FLAGS.Di, not in the reference): f and q1 are driven by a given input v_t; 0 = off.  The input route
+        # is the missing-observation filter with a bias row per step, so it owns every width and emission form as that one does
+        self.Di = self._route_inputs(model, FLAGS)
+        self.wide_obs = self._route_wide_obs(model, bool(getattr(FLAGS, "BSim_wide_obs", False)), self.missing_obs or self.Di > 0)
 
         # SSM distributions
         self.q0 = model.q0_dist
@@ -215,6 +251,18 @@ class SVO:
                                  layers=[t.Dhs for t in dict.fromkeys(trans)], wobs_max_dy=cls._WOBS_MAX_DY,
                                  resample_ess_missing_obs=bool(getattr(FLAGS, "resample_ess_missing_obs", False)),
                                  particle_forecast_missing_obs=bool(getattr(FLAGS, "particle_forecast_missing_obs", False)))
+
+    @classmethod
+    def _route_inputs(cls, model, FLAGS):
+        """FLAGS.Di (carried by the model) as an int: 0, or the input width of a filter that runs on
+        psvo_filter_forward_wobs_input / psvo_filter_backward_wobs_input.  What those kernels do not cover is refused here."""
+        trans = [t for t in (getattr(model, "q1_tran", None), getattr(model, "g_tran", None),
+                             None if getattr(model, "use_bootstrap", True) else getattr(model, "f_tran", None)) if t is not None]
+        return check_inputs(getattr(model, "Di", 0) or getattr(FLAGS, "Di", 0), backward_simulation=cls.uses_backward_simulation,
+                            resample_ess=getattr(FLAGS, "resample_ess", 0.0),
+                            particle_forecast=bool(getattr(FLAGS, "particle_forecast", False)),
+                            output_cov=bool(getattr(model, "output_cov", False)), Dy=getattr(model, "Dy", cls._PLAIN_DY),
+                            layers=[t.Dhs for t in dict.fromkeys(trans)], wobs_max_dy=cls._WOBS_MAX_DY)
 
     @classmethod
     def _route_wide_obs(cls, model, bsim_wide_obs=False, missing_obs=False):
@@ -309,8 +357,12 @@ class SVO:
                                                    and getattr(FLAGS, "resample_ess_missing_obs", False)))
 
     # ------------------------------------------------------------------------------------------
-    def get_log_ZSMC(self, obs, hidden, noise=None):
+    def get_log_ZSMC(self, obs, hidden, noise=None, inputs=None):
         """obs (batch, time, Dy), hidden (batch, time, Dx) -> (log_ZSMC scalar, {"Xs": (B,T,N,Dx)}).
+
+        With FLAGS.Di > 0 `inputs` (batch, time, Di) is the exogenous input: x_{t+1} ~ f(. | x_t, v_t) with the proposal
+        q1(. | x_t, v_t), the t = 0 terms evaluated with a zero input; the emission, q0, q2 and the encoders do not see it
+        (psvo_filter_forward_wobs_input).  ValueError when it is missing or mis-shaped; log["filter"] keeps its keys.
 
         `noise` optionally injects the random draws in the HBM layout of include/psvo_hip.h:
         eps_f (T,B,Dx,N), u_f (T,B,N) or idx_f (T,B,N) int32; with FLAGS.FFBS also u_s (T,B,N) or idx_s (T,B,N) int32, the
@@ -349,7 +401,12 @@ class SVO:
         log = {}
         self._release()
         self._sigmas = self.model.sigmas()          # every scale vector of this evaluation, one fused launch
-        filt = self.SMC(hidden, obs, noise=noise)
+        if self.Di:
+            filt = self.SMC(hidden, obs, noise=noise, inputs=self._check_input_rows(inputs, batch_size, time))
+        elif inputs is not None:
+            raise ValueError("get_log_ZSMC: inputs given to a model without an input channel (--Di = 0)")
+        else:
+            filt = self.SMC(hidden, obs, noise=noise)
         log_ZSMC = self.compute_log_ZSMC(filt["lse"])
         # (T, B, Dx, N) -> (batch_size, time, n_particles, Dx)
         log["Xs"] = filt["Xanc"].permute(1, 0, 3, 2)
@@ -367,6 +424,15 @@ class SVO:
             self._map_path(filt, log)
         self._release()
         return log_ZSMC, log
+
+    def _check_input_rows(self, inputs, batch_size, time):
+        """the exogenous input of an evaluation with FLAGS.Di > 0: (batch, time, Di), else ValueError"""
+        if inputs is None:
+            raise ValueError("--Di = %d: the model's transitions are driven by an input; pass inputs (batch, time, Di)" % self.Di)
+        if tuple(inputs.shape) != (batch_size, time, self.Di):
+            raise ValueError("--Di = %d: inputs must be (batch, time, Di) = %s, got %s"
+                             % (self.Di, (batch_size, time, self.Di), tuple(inputs.shape)))
+        return inputs
 
     def _transition_scale(self, filt):
         """the constant scale the filter weighted the transition with (sigma_q1 when f shares q1's network, else sigma_f), or
@@ -549,9 +615,10 @@ class SVO:
             u = self._rand(T, B, N, device=dev)
         return eps, u, idx_in
 
-    def SMC(self, hidden, obs, q_cov=1.0, noise=None):
+    def SMC(self, hidden, obs, q_cov=1.0, noise=None, inputs=None):
         """SVO.py:60-180.  Returns the kernel's output dict: X (pre-resampling, Xs_ta),
-        Xanc (X_ancestors_ta), Fm, logW (log_Ws_ta), idx, lse -- all (T, B, ...)-major."""
+        Xanc (X_ancestors_ta), Fm, logW (log_Ws_ta), idx, lse -- all (T, B, ...)-major.
+        inputs (B,T,Di): the exogenous input of a model with FLAGS.Di > 0."""
         if self.q_uses_true_X:
             # debug proposal around the true latents (SVO.py:73-77,127-131); run_flag forces it off
             # whenever use_2_q is set (runner.py:38-39)
@@ -601,9 +668,18 @@ class SVO:
 
         eps, u, idx_in = self._filter_draws(noise, dev)
 
-        first, extra = self._mlp_args(self._mlp_params(model.q1_tran),
-                                      None if model.use_bootstrap else self._mlp_params(model.f_tran),
-                                      self._mlp_params(model.g_tran))
+        q1p = self._mlp_params(model.q1_tran)
+        fp = None if model.use_bootstrap else self._mlp_params(model.f_tran)
+        hb = None
+        if self.Di:
+            # the input's share of the hidden pre-activation does not depend on the particle: hb[t,b,:] = v[b,t,:] W1[Dx:], one
+            # small matrix product per network on the B T rows (torch differentiates it: d W1[Dx:] and d v come from d hb); the
+            # kernels take W1[:Dx] and add hb to b1 step by step.  (W1 is padded to the kernel width: zeros in hb beyond it.)
+            v_TB = inputs.transpose(0, 1).contiguous().float()
+            hb = (v_TB @ q1p[0][self.Dx:], None if fp is None else v_TB @ fp[0][self.Dx:])
+            q1p = (q1p[0][:self.Dx],) + tuple(q1p[1:])
+            fp = None if fp is None else (fp[0][:self.Dx],) + tuple(fp[1:])
+        first, extra = self._mlp_args(q1p, fp, self._mlp_params(model.g_tran))
         sig_f = None if model.use_bootstrap else self._sigma(self.f)
         self._m0, self._sig0, self._fm0, self._fsig0 = m0, sig0, fm0, fsig0
         desc = self._desc()
@@ -617,6 +693,12 @@ class SVO:
             node, desc._gbufs = FilterWobsMissingFunction, None
             if self.uses_backward_simulation:       # (PSVO, FLAGS.BSim_missing_obs: Fm and logW carry gradients back)
                 node = FilterWobsMissingBsimFunction
+        if self.Di:                 # psvo_filter_forward_wobs_input / _backward_wobs_input: the same envelope, a bias row per step
+            desc._gbufs = None
+            lse, Fm, logW, X, Xanc, idx = FilterWobsInputFunction.apply(
+                desc, obs_TB, eps, u, idx_in,
+                *first, self._sigma(self.q1), sig_q2, sig_f, self._sigma(self.g), mu2, m0, sig0, fm0, fsig0, *extra, *hb)
+            return {"lse": lse, "Fm": Fm, "logW": logW, "X": X, "Xanc": Xanc, "idx": idx, "eps": eps, "u": u}
         if self.resample_ess:
             # psvo_filter_forward_adaptive / psvo_filter_backward_adaptive: the decision per (step, sequence) is the kernel's
             # (wide observations, FLAGS.resample_ess_wide_obs: psvo_filter_forward_wobs_adaptive / _backward_wobs_adaptive)
@@ -725,14 +807,22 @@ class SVO:
             preprocessed_X0 = torch.cat([outputs[:, -1, :Dh], outputs[:, 0, Dh:]], dim=-1)  # (B, 2Dh)
         return preprocessed_X0, preprocessed_obs
 
-    def n_step_prediction(self, n_steps, hidden, obs):
-        """SVO.py:371-404: k-step predictions from the particle mean."""
+    def n_step_prediction(self, n_steps, hidden, obs, inputs=None):
+        """SVO.py:371-404: k-step predictions from the particle mean.  With FLAGS.Di > 0 `inputs` (B,T,Di) drives f: the state
+        of origin t at horizon k meets v_{t+k}."""
         batch_size, time, _, _ = hidden.shape
         assert n_steps < time, "n_steps = {} >= time".format(n_steps)
+        if getattr(self, "Di", 0):
+            inputs = self._check_input_rows(inputs, batch_size, time)
+        elif inputs is not None:
+            raise ValueError("n_step_prediction: inputs given to a model without an input channel (--Di = 0)")
         x_BxTmkxDz = hidden.mean(dim=2)
         y_hat_N_BxTxDy = []
         for k in range(n_steps):
             y_hat_N_BxTxDy.append(self.g.mean(x_BxTmkxDz))
+            if inputs is not None:
+                x_BxTmkxDz = self.f.mean(x_BxTmkxDz[:, :-1], inputs=inputs[:, k:time - 1])
+                continue
             x_BxTmkxDz = self.f.mean(x_BxTmkxDz[:, :-1])
         y_hat_N_BxTxDy.append(self.g.mean(x_BxTmkxDz))
         y_N_BxTxDy = [obs[:, k:, :] for k in range(n_steps + 1)]

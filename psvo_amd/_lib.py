@@ -64,6 +64,11 @@ SIGNATURES = {
     "psvo_filter_forward_wobs_missing_adaptive": (ctypes.c_int, [_DESC, _MLP, _MLP, _MLP] + [_P] * 20
                                                   + [ctypes.c_float, _P, _P, _P] + [_P]),
     "psvo_filter_backward_wobs_missing_adaptive": (ctypes.c_int, [_DESC, _MLP, _MLP, _MLP] + [_P] * 31 + [_P, _P]),
+    "psvo_filter_forward_wobs_input": (ctypes.c_int, [_DESC, _MLP, _MLP, _MLP] + [_P] * 20 + [_P, _P] + [_P]),
+    "psvo_filter_backward_wobs_input": (ctypes.c_int, [_DESC, _MLP, _MLP, _MLP] + [_P] * 31 + [_P, _P] + [_P]),
+    "psvo_mlp_wgrad_rowbias_blocks": (ctypes.c_int, [ctypes.c_longlong]),
+    "psvo_mlp_wgrad_rowbias": (ctypes.c_int, [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                              _P, _P, _P, _MLP, _P, _P, _P, ctypes.c_int, _P]),
     "psvo_bsim_forward_wobs": (ctypes.c_int, [_DESC] + [_P] * 4 + [_MLP, _MLP, _MLP] + [_P] * 22 + [_P]),
     "psvo_bsim_wobs_blocks": (ctypes.c_int, [ctypes.c_int] * 2),
     "psvo_bsim_wobs_ws_floats": (ctypes.c_longlong, [ctypes.c_int] * 6),

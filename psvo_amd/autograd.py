@@ -425,6 +425,31 @@ class FilterWobsMissingFunction(torch.autograd.Function):
         return _filter_backward(ctx, ops.filter_backward_wobs_missing, 5, dlse)
 
 
+class FilterWobsInputFunction(torch.autograd.Function):
+    """psvo_filter_forward_wobs_input / psvo_filter_backward_wobs_input: FilterWobsMissingFunction with input-driven transitions
+    (FLAGS.Di > 0; 1 <= Dy <= 32, one hidden layer, every emission form).
+
+    apply(<the arguments of FilterFunction>, hb_q1, hb_f) takes two more positional tensors (T,B,H), the input's share
+    v_t W1[Dx:] of the hidden pre-activations of MLP_q1 / MLP_f (hb_f None under bootstrap); the W1 it receives are the blocks
+    W1[:Dx].  Outputs of FilterWobsMissingFunction; only lse is differentiable.  The reverse returns d hb_q1 / d hb_f as the
+    gradients of the two (psvo_mlp_wgrad_rowbias), so that torch, which made hb = v @ W1[Dx:], finds d W1[Dx:] and d v itself.
+    One stream, gradients returned as tensors."""
+
+    @staticmethod
+    def forward(ctx, desc, obs_TB, eps, u, idx_in, *t):
+        ctx.hb = (_cf(t[-2]), _cf(t[-1]))
+        filt = _filter_forward(ctx, ops.filter_forward_wobs_input, desc, obs_TB, eps, u, idx_in, t[:-2], hb=ctx.hb)
+        const = (filt["Fm"], filt["logW"], filt["X"], filt["Xanc"], filt["idx"])
+        ctx.mark_non_differentiable(*const)
+        return (filt["lse"],) + const
+
+    @staticmethod
+    def backward(ctx, dlse, *_):
+        q1, f, g, rest, obs_TB, eps = ctx.saved
+        r = ops.filter_backward_wobs_input(ctx.desc, q1, f, g, *rest, obs_TB, eps, ctx.filt, dlse=_cg(dlse), hb=ctx.hb)
+        return (None,) * 5 + _filter_grads(r, ctx.desc, *rest[5:9], None) + (r["dhb_q1"], r["dhb_f"])
+
+
 class FilterWobsMissingBsimFunction(torch.autograd.Function):
     """psvo_filter_forward_wobs_missing / psvo_filter_backward_wobs_missing_ext: FilterWobsMissingFunction in front of a
     BsimWobsMissingFunction (PSVO under FLAGS.missing_obs with FLAGS.BSim_missing_obs).

@@ -1,7 +1,8 @@
 // The two wide-observation filter kernels.  filter_wobs.hip includes this file four times: PSVO_AD = 0 (and PSVO_MS = 0) gives
 // filter_fwd_wobs_kernel and filter_bwd_wobs_kernel, text and code as they always were; PSVO_AD = 1 gives filter_fwd_wobs_ad_kernel
 // and filter_bwd_wobs_ad_kernel, the kernels of psvo_filter_forward_wobs_adaptive / psvo_filter_backward_wobs_adaptive; PSVO_MS = 1
-// gives the missing-observation pair, and both together the adaptive missing-observation pair (below).
+// gives the missing-observation pair, and both together the adaptive missing-observation pair (below).  filter_wobs_in.hip includes it
+// a fifth time: PSVO_IN = 1 on top of PSVO_MS = 1, the input-driven pair (below).
 //
 // Adaptive resampling (filter_fwd_impl.h / filter_bwd_impl.h have the definition; it is the same here): the draw is made and
 // written every step, and the sequence INHERITS it only when ESS = (sum w)^2 / sum w^2 has fallen below ess_frac N (or when
@@ -23,7 +24,24 @@
 // terms left them, so a step with nothing observed (log g = 0 exactly) that follows a resampled step of a bootstrap filter
 // without q2 has ESS = N and is kept.  The adaptive argument blocks; the LDS of the missing-observation form: the adaptive form's
 // red[40 + wave], wave <= 7, ends at red[47], the last of the 48 floats ahead of the cg row (the log-factorial rows for counts).
-#if PSVO_AD && PSVO_MS
+//
+// Exogenous inputs (PSVO_IN = 1 on top of PSVO_MS = 1, PSVO_AD = 0; filter_wobs_in.hip: filter_fwd_wobs_in_kernel /
+// filter_bwd_wobs_in_kernel, the kernels of psvo_filter_forward_wobs_input / psvo_filter_backward_wobs_input): the first layer of
+// MLP_q1 / MLP_f is applied to concat[x_t, v_t], and the input's share hb[t,b,:] = v[b,t,:] W1[Dx:] of the hidden pre-activation is
+// the same for every particle.  The kernels keep the EFFECTIVE bias row b1 + hb[t,b,:] of the step (one fp32 add, made by the lane
+// that stages the word) in a two-row LDS buffer hbuf[2][2 H] (q1 | f), the pattern of ybuf: the words of the next step's row are
+// requested while this step computes -- lane tid takes word tid and, where a single wave stages 2 H = 128 words, word tid + NT --
+// and land in the half that the step BEFORE this one read, ahead of the step's own stores and of the barrier that ends it.  Nothing of step t reads
+// that half, so neither the IWAE reverse step (no barrier between bwd_input and the end of the step) nor a one-wave forward
+// step (block_max has no barrier at nw == 1) can see a row replaced under it; no barrier is added.  Every MQ::eval<true> /
+// MQ::bwd_input<true> of step t reads the row of step t (RowBias in filter_wobs_in.hip: the same operations, the bias words
+// taken from the row).
+#if PSVO_IN
+#define PSVO_WOBS_FWD_KERNEL filter_fwd_wobs_in_kernel
+#define PSVO_WOBS_BWD_KERNEL filter_bwd_wobs_in_kernel
+#define PSVO_WOBS_FWD_ARGS FwdArgsIn
+#define PSVO_WOBS_BWD_ARGS BwdArgsIn
+#elif PSVO_AD && PSVO_MS
 #define PSVO_WOBS_FWD_KERNEL filter_fwd_wobs_msad_kernel
 #define PSVO_WOBS_BWD_KERNEL filter_bwd_wobs_msad_kernel
 #define PSVO_WOBS_FWD_ARGS FwdArgsAd
@@ -77,6 +95,11 @@ __global__ void __launch_bounds__(512) PSVO_WOBS_FWD_KERNEL(const PSVO_WOBS_FWD_
 #if PSVO_MS
     float* cg = red + 48;               // !CNT (no lfbuf then): [kMaxDy] -(log sig_g + 1/2 log 2 pi), the constant of one term
 #endif
+#if PSVO_IN
+    using RB = RowBias<DX, H>;
+    float* hbuf = red + 48 + 2 * kMaxDy;        // [2][2 H] effective bias rows (q1 | f) of step t (t & 1) and t + 1; 16-byte aligned
+    const int NB = a.bootstrap ? H : 2 * H;     // words of a row that are staged
+#endif
 
     MQ::load(wq1, a.q1, tid, NT);
     if (!a.bootstrap) MQ::load(wf, a.f, tid, NT);
@@ -91,6 +114,12 @@ __global__ void __launch_bounds__(512) PSVO_WOBS_FWD_KERNEL(const PSVO_WOBS_FWD_
         ybuf[tid] = y0;
         if constexpr (CNT) lfbuf[tid] = log_factorial(y0);
     }
+#if PSVO_IN
+    for (int i = tid; i < NB; i += NT) {        // the row of step 0, b1 from HBM (the images are not visible yet)
+        const int k = i & (H - 1);
+        hbuf[i] = i >= H ? a.f.b1[k] + a.hb_f[(size_t)b * H + k] : a.q1.b1[k] + a.hb_q1[(size_t)b * H + k];
+    }
+#endif
 
     float sq1[DX], sq2[DX], sfv[DX], s0[DX], fs0[DX];
 #pragma unroll
@@ -156,9 +185,19 @@ __global__ void __launch_bounds__(512) PSVO_WOBS_FWD_KERNEL(const PSVO_WOBS_FWD_
 
         float eps_n[DX], mu2_n[DX], u_n = 0.f, y_n = 0.f;
         int idx_n = 0;
+#if PSVO_IN
+        float hb_n[2] = {0.f, 0.f};         // words tid and tid + NT of the next step's row (NT >= 64, 2 H <= 128)
+#endif
         if (t + 1 < T) {
             load_inputs(t + 1, eps_n, mu2_n, u_n, idx_n);
             if (tid < Dy) y_n = a.obs[(tb + B) * Dy + tid];
+#if PSVO_IN
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int i = tid + j * NT;
+                if (i < NB) hb_n[j] = (i >= H ? a.hb_f : a.hb_q1)[(tb + B) * H + (i & (H - 1))];
+            }
+#endif
         }
 
         // ---- proposal: product of two diagonal Gaussians on *scales* (SVO.py:186-197) ----------
@@ -223,6 +262,26 @@ __global__ void __launch_bounds__(512) PSVO_WOBS_FWD_KERNEL(const PSVO_WOBS_FWD_
 
         // ---- next-step proposal / transition means of every pre-resampling particle -----------
         float p1[DX], fm[DX];
+#if PSVO_IN
+        const float* hb_t = hbuf + (t & 1) * 2 * H + zo;        // b1 + hb[t] of MLP_q1, then of MLP_f
+        RB::eval(wq1_t, hb_t, x, p1);
+        if (a.bootstrap) {
+#pragma unroll
+            for (int d = 0; d < DX; ++d) fm[d] = p1[d];
+        } else {
+            RB::eval(wfm_t, hb_t + H, x, fm);
+        }
+        // the prefetched bias row: b1 (the image's word) + hb, into the half that step t - 1 read.  Here, ahead of the step's
+        // stores: the words were requested before the emission loop and have landed, and a wait for them placed behind the
+        // stores would wait for the stores as well (vmcnt counts both, and the count is not exact across the branches below)
+        if (t + 1 < T) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int i = tid + j * NT;
+                if (i < NB) hbuf[((t + 1) & 1) * 2 * H + i] = (i >= H ? wf : wq1)[MQ::kB1 + (i & (H - 1))] + hb_n[j];
+            }
+        }
+#else
         MQ::template eval<true>(wq1_t, x, p1);
         if (a.bootstrap) {
 #pragma unroll
@@ -230,6 +289,7 @@ __global__ void __launch_bounds__(512) PSVO_WOBS_FWD_KERNEL(const PSVO_WOBS_FWD_
         } else {
             MQ::template eval<true>(wfm_t, x, fm);
         }
+#endif
         if (valid) {
 #pragma unroll
             for (int d = 0; d < DX; ++d) {
@@ -385,7 +445,14 @@ __global__ void __launch_bounds__(512) PSVO_WOBS_BWD_KERNEL(const PSVO_WOBS_BWD_
     int* sa = reinterpret_cast<int*>(red + 16);   // [NT] staged ancestors (-1: no particle)
     float* sv = red + 16 + NT;          // [NV][NT] staged values
     float* sg = sv + NV * NT;           // [Dy][NT] d sig_g sums, one column per lane
+#if PSVO_IN
+    using RB = RowBias<DX, H>;
+    float* hbuf = sg + Dy * NT;         // [2][2 H] effective bias rows (q1 | f) of step t (t & 1) and t - 1; 16-byte aligned
+    float* kst = hbuf + 4 * H;          // [2][5 DX] step constants, as below
+    const int NB = a.bootstrap ? H : 2 * H;
+#else
     float* kst = sg + Dy * NT;          // [2][5 DX] step constants c | 1/c | 1/s1 | 1/s2 | 1/fs of t = 0 and of t >= 1
+#endif
 
     MQ::load(wq1, a.q1, tid, NT);
     if (!a.bootstrap) MQ::load(wf, a.f, tid, NT);
@@ -395,6 +462,13 @@ __global__ void __launch_bounds__(512) PSVO_WOBS_BWD_KERNEL(const PSVO_WOBS_BWD_
         if constexpr (!CNT) isg[tid] = 1.f / a.sig_g[tid];
         ybuf[((T - 1) & 1) * kMaxDy + tid] = a.obs[((size_t)(T - 1) * B + b) * Dy + tid];
     }
+#if PSVO_IN
+    for (int i = tid; i < NB; i += NT) {        // the row of step T - 1, b1 from HBM (the images are not visible yet)
+        const int k = i & (H - 1);
+        const size_t r = ((size_t)(T - 1) * B + b) * H + k;
+        hbuf[((T - 1) & 1) * 2 * H + i] = i >= H ? a.f.b1[k] + a.hb_f[r] : a.q1.b1[k] + a.hb_q1[r];
+    }
+#endif
     if constexpr (!CNT) {
         for (int e = 0; e < Dy; ++e) sg[e * NT + tid] = 0.f;
     }
@@ -458,6 +532,16 @@ __global__ void __launch_bounds__(512) PSVO_WOBS_BWD_KERNEL(const PSVO_WOBS_BWD_
             if constexpr (CNT) y_n = PSVO_ARG(BwdArgs, obs)[(tb - B) * Dy + tid];      // (see dlse below)
             else y_n = a.obs[(tb - B) * Dy + tid];
         }
+#if PSVO_IN
+        float hb_n[2] = {0.f, 0.f};         // words tid and tid + NT of the row of step t - 1, in flight during this step
+        if (t >= 1) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int i = tid + j * NT;
+                if (i < NB) hb_n[j] = (i >= H ? a.hb_f : a.hb_q1)[(tb - B) * H + (i & (H - 1))];
+            }
+        }
+#endif
 
         float x[DX];
 #pragma unroll
@@ -494,6 +578,19 @@ __global__ void __launch_bounds__(512) PSVO_WOBS_BWD_KERNEL(const PSVO_WOBS_BWD_
         }
         if (!valid) dlw = 0.f;
         dlnw = first ? 0.f : dlw;
+#if PSVO_IN
+        // the row of step t - 1 goes to the half that step t + 1 read: an IWAE step has no barrier between bwd_input and the end
+        // of the step, and waves still inside this step's bwd_input read the other half.  Here, ahead of the step's first store:
+        // the words were requested before x and logW, which have just been waited for, and a wait placed behind the stores of
+        // the emission loop would wait for those as well
+        if (t >= 1) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int i = tid + j * NT;
+                if (i < NB) hbuf[((t - 1) & 1) * 2 * H + i] = (i >= H ? wf : wq1)[MQ::kB1 + (i & (H - 1))] + hb_n[j];
+            }
+        }
+#endif
 
         // ---- emission: outputs in the order o = 0 .. Dy - 1 -----------------------------------------------
         float dx[DX];
@@ -613,8 +710,16 @@ __global__ void __launch_bounds__(512) PSVO_WOBS_BWD_KERNEL(const PSVO_WOBS_BWD_
                 if (!a.bootstrap) a.dF[(tb * DX + d) * N + n] = dFn[d];
             }
         }
+#if PSVO_IN
+        {
+            const float* hb_t = hbuf + (t & 1) * 2 * H + zo;        // the relu masks of step t: b1 + hb[t]
+            RB::bwd_input(wq1_t, hb_t, x, dPn, dx);
+            if (!a.bootstrap) RB::bwd_input(wfm_t, hb_t + H, x, dFn, dx);
+        }
+#else
         MQ::template bwd_input<true>(wq1_t, x, dPn, dx);
         if (!a.bootstrap) MQ::template bwd_input<true>(wfm_t, x, dFn, dx);
+#endif
 
         // ---- x = mu + c eps, mu = c (mean1/s1 + mu2/s2) ----------------------------------------------------
         float dmean1[DX];

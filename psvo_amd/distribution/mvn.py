@@ -75,8 +75,12 @@ class tf_mvn(nn.Module):
     def log_prob(self, Input, output, name=None):
         return self.get_mvn(Input).log_prob(output)
 
-    def mean(self, Input, name=None):
+    def mean(self, Input, name=None, inputs=None):
         # (mvn.py:104-117 builds the distribution and takes its mean: the scale plays no part, so its four small
         #  kernels are not launched -- the hoisted networks call this several times per step)
-        mu, _ = self.transformation.transform(Input)
+        # inputs: the exogenous input rows of a transformation with Di > 0 (None: zeros)
+        if inputs is None:
+            mu, _ = self.transformation.transform(Input)
+        else:
+            mu, _ = self.transformation.transform(Input, inputs)
         return mu

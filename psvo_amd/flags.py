@@ -103,6 +103,10 @@ DEFINITIONS = [
     # (not in the reference's registry) PSVO on gappy data: the missing-observation filter, then the wide backward simulation in its
     # missing-observation form, at every 1 <= Dy <= 32.  Off by default: without it --missing_obs with --PSVO stays refused
     ("BSim_missing_obs", bool, False, "PSVO: run --missing_obs on the missing-observation backward-simulation kernels (1 <= Dy <= 32)"),
+    # exogenous inputs (not in the reference's registry; its dead code not_used/SMC_supreme/SMC.py had the concept): the transition
+    # and the proposal are driven by a given input, x_{t+1} ~ f(. | x_t, v_t), v (B,T,Di) read as Vtrain / Vtest beside the
+    # observations.  0 = off: every path is exactly what it is without the flag.  Filter objectives (SVO, AESMC, IWAE)
+    ("Di", int, 0, "SVO / AESMC / IWAE: dimension of the exogenous input v_t that drives f and q1 (0 = autonomous dynamics)"),
     # MAP trajectory for the filter objectives (not in the reference's registry, which has no decoder): the single most probable
     # path through the filter's particles (particle Viterbi).  Off by default, evaluation only
     ("MAP_path", bool, False, "SVO / AESMC / IWAE: return the most probable trajectory through the filter's particles (particle Viterbi)"),

@@ -150,6 +150,7 @@ class SSM(nn.Module):
         self.poisson_emission = FLAGS.poisson_emission
         self.count_emission = bool(getattr(FLAGS, "count_emission", False))      # (not in the reference)
         self.missing_obs = bool(getattr(FLAGS, "missing_obs", False))            # (not in the reference) NaN = not observed
+        self.Di = int(getattr(FLAGS, "Di", 0) or 0)                              # (not in the reference) exogenous input width
         self.X0_use_separate_RNN, self.use_stack_rnn = FLAGS.X0_use_separate_RNN, FLAGS.use_stack_rnn
         self.PSVO, self.PSVOwR, self.SVO = FLAGS.PSVO, getattr(FLAGS, "PSVOwR", False), FLAGS.SVO
         self.BSim_use_single_RNN = FLAGS.BSim_use_single_RNN
@@ -179,7 +180,13 @@ class SSM(nn.Module):
         mk = lambda layers, Dout, Din, name: MLP_transformation(layers, Dout, Din, output_cov=self.output_cov,
                                                                 diag_cov=self.diag_cov, name=name)
         self.q0_tran = mk(self.q0_layers, self.Dx, q0_in, "q0_tran")
-        self.q1_tran = mk(self.q1_layers, self.Dx, self.Dx, "q1_tran")
+        if self.Di > 0:
+            # exogenous inputs: the first layer of q1 and f (one network under use_bootstrap) is applied to concat[x_t, v_t]
+            mk_in = lambda layers, name: MLP_transformation(layers, self.Dx, self.Dx + self.Di, output_cov=self.output_cov,
+                                                            diag_cov=self.diag_cov, name=name, Di=self.Di)
+        else:
+            mk_in = lambda layers, name: mk(layers, self.Dx, self.Dx, name)
+        self.q1_tran = mk_in(self.q1_layers, "q1_tran")
         self.q2_tran = mk(self.q2_layers, self.Dx, E, "q2_tran") if self.use_2_q else None
         if self.PSVO or self.PSVOwR:
             single = self.BSim_use_single_RNN                # features of static_rnn(y_smoother_f): (B, Dh)
@@ -187,7 +194,7 @@ class SSM(nn.Module):
             self.BSim_q_init_tran = mk(self.q0_layers, self.Dx, Eb, "BSim_q_init_tran")
             self.q1_inv_tran = mk(self.q1_layers, self.Dx, self.Dx, "q1_inv_tran")
             self.BSim_q2_tran = mk(self.q2_layers, self.Dx, Eb, "BSim_q2_tran")
-        self.f_tran = self.q1_tran if self.use_bootstrap else mk(self.f_layers, self.Dx, self.Dx, "f_tran")
+        self.f_tran = self.q1_tran if self.use_bootstrap else mk_in(self.f_layers, "f_tran")
         self.g_tran = mk(self.g_layers, self.Dy, self.Dx, "g_tran")
 
     def init_dist(self):                                     # model.py:112-160

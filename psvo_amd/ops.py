@@ -209,8 +209,10 @@ _ADAPTIVE_ENTRY = {"psvo_filter_forward": "psvo_filter_forward_adaptive",
 
 
 def filter_forward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, fm0, fsig0,
-                   obs, eps, u=None, idx_in=None, entry="psvo_filter_forward", ess_frac=None, rs_in=None):
+                   obs, eps, u=None, idx_in=None, entry="psvo_filter_forward", ess_frac=None, rs_in=None, hb=None):
     """psvo_filter_forward (`entry`: an entry point with the same contract).  Returns dict(X, Xanc, Fm, logW, idx, lse).
+    hb = (hb_q1, hb_f) (T,B,H) each, hb_f None under bootstrap: the bias rows of psvo_filter_forward_wobs_input, the only entry
+    that takes them.
     ess_frac (a float > 0): psvo_filter_forward_adaptive -- resampling where ESS < ess_frac N; rs_in (T,B) int32 teacher-forces
     the decisions; the dict then also holds rs (T,B) int32 and ess (T,B)."""
     lib = _lib.load()
@@ -238,6 +240,15 @@ def filter_forward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, 
         _chk(rs_in, (T, B), "rs_in", torch.int32)
     elif rs_in is not None:
         raise ValueError("filter_forward: rs_in without ess_frac")
+    if (hb is not None) != (entry == "psvo_filter_forward_wobs_input"):
+        raise ValueError("filter_forward: the bias rows hb belong to psvo_filter_forward_wobs_input, and it needs them")
+    rows = ()
+    if hb is not None:
+        _chk(hb[0], (T, B, H), "hb_q1")
+        if hb[0] is None or (not desc.bootstrap and hb[1] is None):
+            raise ValueError("filter_forward_wobs_input needs hb_q1 and, unless bootstrap, hb_f")
+        _chk(hb[1], (T, B, H), "hb_f")
+        rows = (_ptr(hb[0]), None if desc.bootstrap else _ptr(hb[1]))
     out = {
         "X": _empty(T, B, Dx, N, device=dev), "Xanc": _empty(T, B, Dx, N, device=dev),
         "Fm": _empty(T, B, Dx, N, device=dev), "logW": _empty(T, B, N, device=dev),
@@ -253,7 +264,7 @@ def filter_forward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, 
         _ptr(sig_q1), _ptr(sig_q2), _ptr(sig_f), _ptr(sig_g), _ptr(mu2), _ptr(m0), _ptr(sig0), _ptr(fm0),
         _ptr(fsig0), _ptr(obs), _ptr(eps), _ptr(u), _ptr(idx_in),
         _ptr(out["X"]), _ptr(out["Xanc"]), _ptr(out["Fm"]), _ptr(out["P1"]), _ptr(out["logW"]), _ptr(out["idx"]),
-        _ptr(out["lse"]), *adaptive, _stream())
+        _ptr(out["lse"]), *adaptive, *rows, _stream())
     return out
 
 
@@ -276,6 +287,13 @@ def filter_forward_wobs_missing(*args, **kw):
     term is left out of the emission log-density (1 <= Dy <= 32, one hidden layer, every emission form); arguments, outputs and
     layouts of filter_forward."""
     return filter_forward(*args, entry="psvo_filter_forward_wobs_missing", **kw)
+
+
+def filter_forward_wobs_input(*args, hb, **kw):
+    """psvo_filter_forward_wobs_input: filter_forward_wobs_missing with input-driven transitions -- the first-layer bias of MLP_q1 /
+    MLP_f at step t is b1 + hb[t,b,:], hb = (hb_q1, hb_f) (T,B,H) the input's share v_t W1[Dx:] of the hidden pre-activation
+    (hb_f None under bootstrap); q1 / f hold W1[:Dx].  Arguments, outputs and layouts of filter_forward."""
+    return filter_forward(*args, entry="psvo_filter_forward_wobs_input", hb=hb, **kw)
 
 
 def filter_forward_wobs_missing_adaptive(*args, ess_frac, rs_in=None, **kw):
@@ -466,6 +484,40 @@ def mlp_wgrad(X, dOut, w, Din, H, Dout, grad=None, axis=2, wobs=False):
     return grad
 
 
+def mlp_wgrad_rowbias(X, dOut, hb, w, Din, H, Dout, grad=None, axis=2):
+    """psvo_mlp_wgrad_rowbias: mlp_wgrad (one hidden layer, Din, Dout <= 4) where the first-layer bias of segment s is
+    b1 + hb[s]; hb has the shape of X ahead of `axis`, then H.  Returns (flat grad [dW1|db1|dW2|db2], dhb like hb) with
+    dhb[s] = sum over the segment's rows of d pre; `grad` given: accumulated into (dhb is always written)."""
+    lib = _lib.load()
+    dev = X.device
+    ax = axis
+    if (not X.is_contiguous() or not dOut.is_contiguous() or X.shape[ax] != Din or dOut.shape[ax] != Dout
+            or X.shape[:ax] != dOut.shape[:ax] or X.shape[ax + 1:] != dOut.shape[ax + 1:]):
+        raise ValueError("mlp_wgrad_rowbias: bad row tensors %s / %s for Din=%d, Dout=%d, axis=%d"
+                         % (tuple(X.shape), tuple(dOut.shape), Din, Dout, ax))
+    _chk(hb, tuple(X.shape[:ax]) + (H,), "hb")
+    if hb is None or len(w) != 4:
+        raise ValueError("mlp_wgrad_rowbias: needs the bias rows hb and an MLP with one hidden layer")
+    S = 1
+    for v in X.shape[:ax]:
+        S *= v
+    L = 1
+    for v in X.shape[ax + 1:]:
+        L *= v
+    ws = _mlp_struct(w, Din, H, Dout, "w")
+    NP = mlp_grad_size(Din, H, Dout)
+    partial = _empty(lib.psvo_mlp_wgrad_rowbias_blocks(S), NP, device=dev)
+    acc = grad is not None
+    if grad is None:
+        grad = _empty(NP, device=dev)
+    elif grad.numel() != NP:
+        raise ValueError("mlp_wgrad_rowbias: gradient slice of %d floats for an MLP of %d parameters" % (grad.numel(), NP))
+    dhb = _empty(*hb.shape, device=dev)
+    _launch("psvo_mlp_wgrad_rowbias", lib.psvo_mlp_wgrad_rowbias, S, L, Din, H, Dout, _ptr(X), _ptr(dOut), _ptr(hb),
+            ctypes.byref(ws), _ptr(partial), _ptr(grad), _ptr(dhb), int(acc), _stream())
+    return grad, dhb
+
+
 def mlp_wgrad_wobs(X, dOut, w, Din, H, Dout, grad=None, axis=2):
     """psvo_mlp_wgrad_wobs: mlp_wgrad for an MLP with 3 <= Dout <= 32 outputs"""
     return mlp_wgrad(X, dOut, w, Din, H, Dout, grad=grad, axis=axis, wobs=True)
@@ -541,7 +593,7 @@ def split_mlp_grad(g, Din, H, Dout, layers=1):
 
 def filter_backward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, fm0, fsig0, obs, eps, filt,
                     dlse=None, dFm=None, dlogW=None, gbufs=None, before_wgrad=None, defer_wgrad=False, wobs=False,
-                    nparts=None, ext=False, adaptive=False, missing=False):
+                    nparts=None, ext=False, adaptive=False, missing=False, hb=None):
     """psvo_filter_backward + psvo_mlp_wgrad (adaptive: psvo_filter_backward_adaptive, following the decisions filt["rs"]).
     `filt` = forward outputs.  dFm (T,B,Dx,N) / dlogW (T,B,N)
     are upstream gradients (or None); with nparts > 1 they come in parts, (T,B,nparts,Dx,N) / (T,B,nparts,N), which the
@@ -551,7 +603,10 @@ def filter_backward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0,
     missing (with wobs): psvo_filter_backward_wobs_missing, 1 <= Dy <= 32 (with dFm / dlogW or ext=True -- the missing-observation
     backward simulation ran behind it -- psvo_filter_backward_wobs_missing_ext); MLP_g's weight gradient from the d G rows is
     psvo_mlp_wgrad_wobs for Dy >= 3 and the plain psvo_mlp_wgrad for Dy <= 2; with adaptive="wobs" as well,
-    psvo_filter_backward_wobs_missing_adaptive, following filt["rs"] (dlse only)."""
+    psvo_filter_backward_wobs_missing_adaptive, following filt["rs"] (dlse only).
+    hb = (hb_q1, hb_f) (with wobs and missing, dlse only): psvo_filter_backward_wobs_input, the reverse of
+    filter_forward_wobs_input; the weight gradients of MLP_q1 / MLP_f are psvo_mlp_wgrad_rowbias and the result also holds
+    dhb_q1 and dhb_f (T,B,H; dhb_f None under bootstrap)."""
     lib = _lib.load()
     B, T, N, Dx, Dy, H = desc.B, desc.T, desc.N, desc.Dx, desc.Dy, desc.H
     dev = eps.device
@@ -595,6 +650,15 @@ def filter_backward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0,
         _chk(filt["rs"], (T, B), "filt['rs']", torch.int32)
         name = "psvo_filter_backward_wobs_adaptive" if wobs else "psvo_filter_backward_adaptive"
         decisions = (_ptr(filt["rs"]),)
+    if hb is not None:
+        if not (wobs and missing) or adaptive or ext:
+            raise ValueError("filter_backward: the bias rows hb belong to psvo_filter_backward_wobs_input -- the missing-observation "
+                             "route, resampling at every step or never, upstream gradient dlse only")
+        _chk(hb[0], (T, B, H), "hb_q1"); _chk(hb[1], (T, B, H), "hb_f")
+        if hb[0] is None or (not desc.bootstrap and hb[1] is None):
+            raise ValueError("filter_backward_wobs_input needs hb_q1 and, unless bootstrap, hb_f")
+        name = "psvo_filter_backward_wobs_input"
+        decisions = (_ptr(hb[0]), None if desc.bootstrap else _ptr(hb[1]))
     sacc = z((lib.psvo_filter_wobs_ws_floats if wobs else lib.psvo_filter_ws_floats)(B, T, N, Dx, Dy))
     upstream = (_ptr(dlse),) if (wobs and not ext) else (_ptr(dlse), nparts, _ptr(dFm), _ptr(dlogW))
     with _fixed_order():
@@ -614,8 +678,13 @@ def filter_backward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0,
     def wgrad(g_stream=None, after=None):
         """the two or three weight-gradient launches; g_stream: issue MLP_g's on that stream (ordered after the event
         `after`, i.e. after this kernel's rows exist) beside MLP_q1's on the current one -- the caller joins both"""
-        out["gq1"] = mlp_wgrad(filt["X"], out["dP"], q1, Dx, H, Dx, grad=gb[0])
-        out["gf"] = None if desc.bootstrap else mlp_wgrad(filt["X"], out["dF"], f, Dx, H, Dx, grad=gb[1])
+        if hb is not None:      # the first-layer bias of a row's segment is b1 + hb[t,b]; the segment sums of d pre are d hb
+            out["gq1"], out["dhb_q1"] = mlp_wgrad_rowbias(filt["X"], out["dP"], hb[0], q1, Dx, H, Dx, grad=gb[0])
+            out["gf"], out["dhb_f"] = ((None, None) if desc.bootstrap else
+                                       mlp_wgrad_rowbias(filt["X"], out["dF"], hb[1], f, Dx, H, Dx, grad=gb[1]))
+        else:
+            out["gq1"] = mlp_wgrad(filt["X"], out["dP"], q1, Dx, H, Dx, grad=gb[0])
+            out["gf"] = None if desc.bootstrap else mlp_wgrad(filt["X"], out["dF"], f, Dx, H, Dx, grad=gb[1])
         if g_stream is not None and gb[2] is not None:
             g_stream.wait_event(after)
             for t in (filt["X"], out["dG"]):
@@ -649,6 +718,13 @@ def filter_backward_wobs_missing(*args, **kw):
     """psvo_filter_backward_wobs_missing + psvo_mlp_wgrad (q1, f; g at Dy <= 2) + psvo_mlp_wgrad_wobs (g at Dy >= 3): the reverse
     of filter_forward_wobs_missing; arguments and result of filter_backward (dlse only)."""
     return filter_backward(*args, wobs=True, missing=True, **kw)
+
+
+def filter_backward_wobs_input(*args, hb, **kw):
+    """psvo_filter_backward_wobs_input + psvo_mlp_wgrad_rowbias (q1, f) + MLP_g's weight gradient as in
+    filter_backward_wobs_missing: the reverse of filter_forward_wobs_input; arguments of filter_backward (dlse only) plus
+    hb = (hb_q1, hb_f); the result also holds dhb_q1 / dhb_f."""
+    return filter_backward(*args, wobs=True, missing=True, hb=hb, **kw)
 
 
 def filter_backward_wobs_missing_adaptive(*args, **kw):

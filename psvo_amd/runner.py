@@ -27,7 +27,7 @@ from .SMC.AESMC import AESMC
 from .SMC.IWAE import IWAE
 from .SMC.PSVO import PSVO
 from .SMC.PSVOwR import PSVOwR
-from .SMC.SVO import SVO, check_map_path, check_missing_obs, check_resample_ess
+from .SMC.SVO import SVO, check_inputs, check_map_path, check_missing_obs, check_resample_ess
 from .trainer import trainer
 from .utils.data_generator import PoissonEmitter, count_loading, generate_dataset, knock_out
 from .utils.data_loader import load_data
@@ -45,16 +45,29 @@ def _device():
 
 
 def _dataset(FLAGS):
-    """(hidden_train, hidden_test, obs_train, obs_test); updates the flags that describe the data"""
+    """(hidden_train, hidden_test, obs_train, obs_test) and, with --Di > 0, (inputs_train, inputs_test) behind them; updates the
+    flags that describe the data"""
     count = bool(getattr(FLAGS, "count_emission", False))
     missing = bool(getattr(FLAGS, "missing_obs", False))
+    Di = int(getattr(FLAGS, "Di", 0) or 0)
     if FLAGS.generateTrainingData:
         # (count emission: Poisson counts of the FHN latent through a fixed loading, data_generator.count_loading)
         g = PoissonEmitter(*count_loading(FLAGS.Dy, 2)) if count else None
-        data = generate_dataset(FLAGS.n_train, FLAGS.n_test, FLAGS.time, model="fhn", Dy=FLAGS.Dy, g=g, lb=-2.5, ub=2.5)
+        if Di > 0:      # (the FHN current becomes I + v_t; anything but one channel is refused there)
+            if FLAGS.Dx != 2:
+                raise ValueError("--generateTrainingData --Di: the generated inputs drive the FHN model (Dx = 2), got Dx = %d"
+                                 % FLAGS.Dx)
+            data = generate_dataset(FLAGS.n_train, FLAGS.n_test, FLAGS.time, model="fhn", Dy=FLAGS.Dy, g=g, lb=-2.5, ub=2.5,
+                                    input_dim=Di)
+        else:
+            data = generate_dataset(FLAGS.n_train, FLAGS.n_test, FLAGS.time, model="fhn", Dy=FLAGS.Dy, g=g, lb=-2.5, ub=2.5)
         rate = float(getattr(FLAGS, "missing_rate", 0.0) or 0.0)
         if missing and rate > 0.0:      # (after generation: training set, then test set)
-            data = data[:2] + (knock_out(data[2], rate), knock_out(data[3], rate))
+            data = data[:2] + (knock_out(data[2], rate), knock_out(data[3], rate)) + data[4:]
+    elif Di > 0:
+        data = load_data(FLAGS.datadir + FLAGS.datadict, FLAGS.Dx, FLAGS.isPython2, FLAGS.q_uses_true_X, Di=Di)
+        obs_train, obs_test = data[2], data[3]
+        FLAGS.n_train, FLAGS.n_test, FLAGS.time = obs_train.shape[0], obs_test.shape[0], obs_test.shape[1]
     else:
         data = load_data(FLAGS.datadir + FLAGS.datadict, FLAGS.Dx, FLAGS.isPython2, FLAGS.q_uses_true_X)
         obs_train, obs_test = data[2], data[3]
@@ -116,6 +129,10 @@ def main(FLAGS):
     check_map_path(bool(getattr(FLAGS, "MAP_path", False)), backward_simulation=bool(FLAGS.PSVO or FLAGS.PSVOwR),
                    output_cov=bool(FLAGS.output_cov), Dy=FLAGS.Dy,
                    layers=[FLAGS.q1_layers, FLAGS.g_layers] + ([] if FLAGS.use_bootstrap else [FLAGS.f_layers]))
+    check_inputs(getattr(FLAGS, "Di", 0), backward_simulation=bool(FLAGS.PSVO or FLAGS.PSVOwR),
+                 resample_ess=getattr(FLAGS, "resample_ess", 0.0), particle_forecast=bool(getattr(FLAGS, "particle_forecast", False)),
+                 output_cov=bool(FLAGS.output_cov), Dy=FLAGS.Dy,
+                 layers=[FLAGS.q1_layers, FLAGS.g_layers] + ([] if FLAGS.use_bootstrap else [FLAGS.f_layers]))
     if FLAGS.use_2_q:
         FLAGS.q_uses_true_X = False
     device = _device()
@@ -123,7 +140,8 @@ def main(FLAGS):
     torch.manual_seed(FLAGS.seed)
     np.random.seed(FLAGS.seed)
 
-    hidden_train, hidden_test, obs_train, obs_test = _dataset(FLAGS)
+    hidden_train, hidden_test, obs_train, obs_test, *inputs = _dataset(FLAGS)
+    inputs = dict(zip(("inputs_train", "inputs_test"), inputs))          # (--Di > 0: the exogenous inputs; else nothing)
     if rank == 0:
         print("finished preparing dataset")
 
@@ -139,11 +157,12 @@ def main(FLAGS):
 
     fit = trainer(model, smc, FLAGS)
     fit.init_data_saving(run_dir)
-    history, log = fit.train(obs_train, obs_test, hidden_train, hidden_test, FLAGS.print_freq)
+    history, log = fit.train(obs_train, obs_test, hidden_train, hidden_test, FLAGS.print_freq, **inputs)
 
     # final evaluation of the first saving_num held-out sequences (collective: every rank takes part), then rank 0 writes
     keep = FLAGS.saving_num
-    feed = getattr(fit, "saving_feed_dict", None) or {fit.obs: obs_test[:keep], fit.hidden: hidden_test[:keep]}
+    feed = getattr(fit, "saving_feed_dict", None) or {fit.obs: obs_test[:keep], fit.hidden: hidden_test[:keep],
+                                                      **({fit.INPUTS: inputs["inputs_test"][:keep]} if inputs else {})}
     Xs_val = fit.evaluate(log["Xs"], feed)
     y_hat_val = fit.evaluate(log["y_hat"], feed)
     if rank == 0:

@@ -133,6 +133,8 @@ def _collate(per_batch, keepdims):
 
 
 class trainer:
+    INPUTS = "inputs"       # feed key of the exogenous inputs (FLAGS.Di > 0), beside self.obs / self.hidden
+
     # schedule state, reference names (trainer.py:63-80): bestCost = index of the best validation ELBO so far,
     # *_count = evaluations since it improved
     def __init__(self, model, SMC, FLAGS):
@@ -178,8 +180,9 @@ class trainer:
         lo, hi = dp.shard(len(a))
         return a[lo:hi]
 
-    def train_step(self, obs_batch, hidden_batch, lr):
-        """one sess.run(train_op) of the reference (trainer.py:147-151).
+    def train_step(self, obs_batch, hidden_batch, lr, inputs_batch=None):
+        """one sess.run(train_op) of the reference (trainer.py:147-151).  inputs_batch: the exogenous inputs of the batch
+        (FLAGS.Di > 0), moved and sliced with the observations.
 
         On the GPU the local part of the step (zero the gradient buffer, objective, reverse pass: ~90 launches on three
         streams) is captured once per batch shape into a hipGraph and replayed with the batch copied into static
@@ -187,37 +190,42 @@ class trainer:
         PSVO_HIPGRAPH=0, or a failed capture, issues everything eagerly."""
         obs = self._to_dev(self._local(obs_batch))
         hidden = self._to_dev(self._local(hidden_batch))
-        log_ZSMC = self._graphed_local_step(obs, hidden)
+        inputs = None if inputs_batch is None else self._to_dev(self._local(inputs_batch))
+        extra = {} if inputs is None else {"inputs": inputs}
+        log_ZSMC = self._graphed_local_step(obs, hidden, inputs)
         if log_ZSMC is None:
             self.flat.zero_grad()
-            log_ZSMC, _ = self.SMC.get_log_ZSMC(obs, hidden)
+            log_ZSMC, _ = self.SMC.get_log_ZSMC(obs, hidden, **extra)
             with autograd.deferred_join():
                 log_ZSMC.backward()
         dp.all_reduce_sum_(self.flat.grad)
         self.optimizer.step(lr, world_size=dp.world_size())
         return log_ZSMC.detach()
 
-    def _graphed_local_step(self, obs, hidden):
-        """replay (capturing on first use) the hipGraph of the local step for this batch shape; None = run eagerly"""
+    def _graphed_local_step(self, obs, hidden, inputs=None):
+        """replay (capturing on first use) the hipGraph of the local step for this batch shape; None = run eagerly.
+        inputs (FLAGS.Di > 0): a static buffer beside the observations'."""
         import os
         if (not obs.is_cuda or os.environ.get("PSVO_HIPGRAPH", "1") == "0"
                 or getattr(self.SMC, "generator", None) is None):
             return None      # (a CPU generator cannot be registered with the graph)
         graphs = self.__dict__.setdefault("_graphs", {})
-        key = (tuple(obs.shape), tuple(hidden.shape))
+        key = (tuple(obs.shape), tuple(hidden.shape)) + (() if inputs is None else (tuple(inputs.shape),))
         g = graphs.get(key)
         if g is None:
             try:
                 from .graph import GraphedStep
                 s_obs, s_hidden = obs.clone(), hidden.clone()
+                s_inputs = None if inputs is None else inputs.clone()
+                s_extra = {} if inputs is None else {"inputs": s_inputs}
 
                 def local_step():
                     self.flat.zero_grad()
-                    z, _ = self.SMC.get_log_ZSMC(s_obs, s_hidden)
+                    z, _ = self.SMC.get_log_ZSMC(s_obs, s_hidden, **s_extra)
                     with autograd.deferred_join():
                         z.backward()
                     return z.detach()
-                g = (GraphedStep(local_step, generators=[self.SMC.generator]), s_obs, s_hidden)
+                g = (GraphedStep(local_step, generators=[self.SMC.generator]), s_obs, s_hidden, s_inputs)
             except Exception as exc:     # fall back to eager issue for this shape from now on
                 if dp.rank() == 0:
                     print("hipGraph capture of the training step failed (%s: %s); issuing eagerly"
@@ -227,14 +235,21 @@ class trainer:
             graphs[key] = g
         if g is False:
             return None
-        step, s_obs, s_hidden = g
+        step, s_obs, s_hidden, s_inputs = g
         s_obs.copy_(obs)
         s_hidden.copy_(hidden)
+        if s_inputs is not None:
+            s_inputs.copy_(inputs)
         return step()
 
-    def train(self, obs_train, obs_test, hidden_train, hidden_test, print_freq):
+    def train(self, obs_train, obs_test, hidden_train, hidden_test, print_freq, inputs_train=None, inputs_test=None):
+        """inputs_train / inputs_test (n, T, Di): the exogenous inputs of a model with FLAGS.Di > 0; they are shuffled, sliced
+        and moved with the observations wherever those are."""
         self.obs_train, self.obs_test = obs_train, obs_test
         self.hidden_train, self.hidden_test = hidden_train, hidden_test
+        if int(getattr(self.SMC, "Di", 0) or 0) > 0 and (inputs_train is None or inputs_test is None):
+            raise ValueError("--Di = %d: train() needs inputs_train and inputs_test beside the observations" % self.SMC.Di)
+        self.inputs_train, self.inputs_test = inputs_train, inputs_test
 
         assert self.batch_size % dp.world_size() == 0, "batch_size must split evenly over the ranks"
         self.flat = FlatParams(self.model)
@@ -252,9 +267,16 @@ class trainer:
             if i == 0:
                 self.evaluate_and_save_metrics(i)
 
-            obs_train, hidden_train = _shuffle(obs_train, hidden_train)
+            if inputs_train is None:
+                obs_train, hidden_train = _shuffle(obs_train, hidden_train)
+            else:       # (one shared permutation, the same draw from numpy's generator as without inputs)
+                obs_train, hidden_train, inputs_train = _shuffle(obs_train, hidden_train, inputs_train)
             for j in range(0, len(obs_train), self.batch_size):
-                self.train_step(obs_train[j:j + self.batch_size], hidden_train[j:j + self.batch_size], self.lr)
+                if inputs_train is None:
+                    self.train_step(obs_train[j:j + self.batch_size], hidden_train[j:j + self.batch_size], self.lr)
+                else:
+                    self.train_step(obs_train[j:j + self.batch_size], hidden_train[j:j + self.batch_size], self.lr,
+                                    inputs_batch=inputs_train[j:j + self.batch_size])
             if check_exchange is not None:
                 check_exchange()                                 # every epoch: a timed-out exchange means garbage gradients
 
@@ -283,6 +305,8 @@ class trainer:
         two-dimensional latents, lattice_val_<epoch>.p -- the data behind the reference's quiver plot (trainer.py:337-361),
         which its notebook reads back (notebooks/PSVO.ipynb: `lattice_dict["X_trajs"], ["X"], ["nextX"]`)."""
         self.saving_feed_dict = {self.obs: obs_test[:self.saving_num], self.hidden: hidden_test[:self.saving_num]}
+        if getattr(self, "inputs_test", None) is not None:
+            self.saving_feed_dict[self.INPUTS] = self.inputs_test[:self.saving_num]
         Xs_val = None
         forecast = bool(getattr(self.SMC, "forecast", False))
         map_path = bool(getattr(self.SMC, "MAP_path", False))
@@ -348,7 +372,10 @@ class trainer:
             fetches += ["forecast_y_mean", "forecast_y_var", "forecast_lpd"]
         m, ess = {}, {}
         for split, obs, hid in (("train", self.obs_train, self.hidden_train), ("test", self.obs_test, self.hidden_test)):
-            elbos, y_hat, y, *rest = self.evaluate(fetches, {self.obs: obs, self.hidden: hid})
+            feed = {self.obs: obs, self.hidden: hid}
+            if getattr(self, "inputs_" + split, None) is not None:
+                feed[self.INPUTS] = getattr(self, "inputs_" + split)
+            elbos, y_hat, y, *rest = self.evaluate(fetches, feed)
             if forecast:
                 fc, rest = rest[-3:], rest[:-3]
                 lpd, rsq, cal, *per_entry = _forecast_metrics(*fc, np.asarray(obs, dtype=np.float32), missing_obs=missing)
@@ -479,17 +506,18 @@ class trainer:
             torch.save(self.model.state_dict(), self.RLT_DIR + "model/model_epoch_{}.pt".format(iter_num + 1))
 
     # ------------------------------------------------------------------------------------------
-    def _run(self, names, obs, hidden):
-        """one forward evaluation of a batch (sess.run(fetches) of the reference)"""
+    def _run(self, names, obs, hidden, inputs=None):
+        """one forward evaluation of a batch (sess.run(fetches) of the reference); inputs: its exogenous inputs (FLAGS.Di > 0)"""
         with torch.no_grad():
             obs_d = self._to_dev(obs)
-            log_ZSMC, log = self.SMC.get_log_ZSMC(obs_d, self._to_dev(hidden))
+            extra = {} if inputs is None else {"inputs": self._to_dev(inputs)}
+            log_ZSMC, log = self.SMC.get_log_ZSMC(obs_d, self._to_dev(hidden), **extra)
             out = {"log_ZSMC": float(log_ZSMC)}
             if any(n in names for n in ("Xs", "y_hat", "y")):
                 Xs = log["Xs"]
                 out["Xs"] = Xs.contiguous().cpu().numpy()
                 if "y_hat" in names or "y" in names:
-                    y_hat, y = self.SMC.n_step_prediction(self.MSE_steps, Xs, obs_d)
+                    y_hat, y = self.SMC.n_step_prediction(self.MSE_steps, Xs, obs_d, **extra)
                     out["y_hat"] = [v.cpu().numpy() for v in y_hat]
                     out["y"] = [v.cpu().numpy() for v in y]
             if any(n.startswith("forecast_") for n in names):       # FLAGS.particle_forecast only
@@ -523,11 +551,13 @@ class trainer:
         single = not isinstance(fetches, list)
         names = [fetches] if single else list(fetches)
         obs_all, hid_all = feed_dict_w_batches[self.obs], feed_dict_w_batches[self.hidden]
+        v_all = feed_dict_w_batches.get(self.INPUTS)          # the exogenous inputs (FLAGS.Di > 0), or None
         n = len(obs_all)
         assert n >= self.batch_size
         starts = list(range(0, n, self.batch_size))
         W, r = dp.world_size(), dp.rank()
-        mine = {k: self._run(names, obs_all[s:s + self.batch_size], hid_all[s:s + self.batch_size])
+        cut = lambda s: {} if v_all is None else {"inputs": v_all[s:s + self.batch_size]}
+        mine = {k: self._run(names, obs_all[s:s + self.batch_size], hid_all[s:s + self.batch_size], **cut(s))
                 for k, s in enumerate(starts) if k % W == r}
         if W > 1:
             import torch.distributed as dist

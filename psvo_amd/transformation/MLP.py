@@ -22,8 +22,13 @@ def _he_normal_(w):
 
 class MLP_transformation(nn.Module):
     def __init__(self, Dhs, Dout, Din, use_residual=False, output_cov=False, diag_cov=False,
-                 name="MLP_transformation"):
+                 name="MLP_transformation", Di=0):
         super().__init__()
+        # exogenous inputs (FLAGS.Di, not in the reference): the last Di of the Din columns are an input v that is given beside
+        # the state, the first layer is applied to concat[x, v]; transform(x, inputs) takes the two apart
+        self.Di = int(Di)
+        if self.Di and (use_residual or not 0 < self.Di < Din):
+            raise ValueError("%s: Di = %d input columns out of Din = %d (no residual connection)" % (name, Di, Din))
         if output_cov and not diag_cov:
             # reference MLP.py:41,63-66: Dout^2 outputs reshaped to a matrix, cov = A A^T -> MultivariateNormalFullCovariance
             raise NotImplementedError("output_cov without diag_cov (full covariance) is outside the MI355X hot-path scope "
@@ -67,15 +72,30 @@ class MLP_transformation(nn.Module):
             return "dtype %s (float32 only)" % Input.dtype
         return None
 
-    def transform(self, Input):
+    def transform(self, Input, inputs=None):
         """reference MLP.py:48-68; returns (mu, cov): cov = None without the covariance head, else exp(sigma_layer(hidden)) + 1e-6
         (diag_cov; MLP.py:58-61).
+
+        With Di > 0 `Input` holds the Din - Di state columns and `inputs` the Di input columns of the same rows (broadcast over
+        leading axes `Input` has and `inputs` lacks is the caller's business); None means a zero input.
 
         Tensors in HBM go through native kernels only: the fused one-hidden-layer pair psvo_rows_mlp_* where it applies
         (one launch forward, one backward), otherwise one psvo_dense_* launch per Dense layer (any number of hidden layers,
         widths up to 4096) -- there is no PyTorch-op fallback on the GPU.  CPU tensors take the plain
         matmul form below; that is the host-side mirror the CPU tests of the host logic (encoder wiring, k-step
         prediction, R-square) run on a machine without a GPU, never part of the GPU path."""
+        if self.Di:
+            if Input.shape[-1] != self.Din - self.Di:
+                raise ValueError("%s: %d state columns expected beside the Di = %d input columns, got %d"
+                                 % (self.name, self.Din - self.Di, self.Di, Input.shape[-1]))
+            if inputs is None:
+                inputs = Input.new_zeros(Input.shape[:-1] + (self.Di,))
+            elif inputs.shape != Input.shape[:-1] + (self.Di,):
+                raise ValueError("%s: inputs %s beside states %s (Di = %d)"
+                                 % (self.name, tuple(inputs.shape), tuple(Input.shape), self.Di))
+            Input = torch.cat([Input, inputs.to(Input.dtype)], dim=-1)
+        elif inputs is not None:
+            raise ValueError("%s: inputs given to a transformation without input columns (Di = 0)" % self.name)
         if Input.is_cuda:
             if Input.dtype != torch.float32:
                 raise ValueError("%s: the native kernels compute in float32, got %s (no PyTorch fallback exists)"

@@ -13,6 +13,10 @@ Contract kept from the reference (cited lines: its files)
     initial state x_0 ~ U(lb, ub)^Dx, then one emission draw per time step, t = 0 first;
   * `f` / `g` may be supplied: anything with a `.sample(x)` method (the reference's distribution objects) or a plain callable.
 PoissonEmitter is such a `g`: counts y ~ Poisson(softplus(C x + d)) for the count emission (FLAGS.count_emission).
+
+Exogenous inputs (FLAGS.Di = 1, FHN only; not in the reference, whose generator carries an unused `Di`): with `input_dim=1` the
+injected current of step t -> t + 1 is I + v_t, v a per-sequence piecewise-constant pulse train (pulse_train) drawn from numpy's
+GLOBAL generator right after the sequence's x_0, and generate_dataset returns v_train, v_test (n, time, 1) behind its four arrays.
 """
 import numpy as np
 from scipy.integrate import odeint
@@ -26,8 +30,9 @@ def _advance(rhs, state, dt):
     return odeint(rhs, state, np.array([0.0, dt]))[1]
 
 
-def _fhn_step(X_prev, params):
+def _fhn_step(X_prev, params, v=0.0):
     a, b, c, I, dt = params
+    I = I + v                   # (an exogenous input adds to the injected current over the step)
     return _advance(lambda X, t: (X[0] - X[0] ** 3 / 3.0 - X[1] + I, a * (b * X[0] - c * X[1])), X_prev, dt)
 
 
@@ -42,8 +47,8 @@ class _Deterministic:
     def __init__(self, step, params):
         self._step, self._params = step, params
 
-    def sample(self, x):
-        return self._step(x, self._params)
+    def sample(self, x, v=None):
+        return self._step(x, self._params) if v is None else self._step(x, self._params, float(v[0]))
 
 
 class _LinearGaussian:
@@ -91,14 +96,30 @@ def _sampler(obj):
     return obj.sample if hasattr(obj, "sample") else obj
 
 
-def generate_hidden_obs(time, Dx, Dy, x_0, f, g):
-    """one sequence: X[0] = x_0, X[t] = f(X[t-1]); Y[t] = g(X[t]) (src/utils/data_generator.py:12-26)"""
+def pulse_train(time, Di, low=5, high=15, amplitude=1.0, p_on=0.5):
+    """(time, Di): per channel, consecutive segments of low .. high steps, each a pulse of height U(-amplitude, amplitude) with
+    probability p_on, else 0.  Draws per segment, in order: its length, whether it is on, its height (always drawn)."""
+    v = np.zeros((time, Di))
+    for d in range(Di):
+        t = 0
+        while t < time:
+            n = np.random.randint(low, high + 1)
+            on = np.random.uniform() < p_on
+            height = np.random.uniform(-amplitude, amplitude)
+            v[t:t + n, d] = height if on else 0.0
+            t += n
+    return v
+
+
+def generate_hidden_obs(time, Dx, Dy, x_0, f, g, v=None):
+    """one sequence: X[0] = x_0, X[t] = f(X[t-1]); Y[t] = g(X[t]) (src/utils/data_generator.py:12-26); v (time, Di):
+    X[t] = f(X[t-1], v[t-1])"""
     step, emit = _sampler(f), _sampler(g)
     X, Y = np.empty((time, Dx)), np.empty((time, Dy))
     state = np.asarray(x_0, dtype=float)
     for t in range(time):
         if t:
-            state = step(state)
+            state = step(state) if v is None else step(state, v[t - 1])
         X[t], Y[t] = state, emit(state)
     return X, Y
 
@@ -113,9 +134,14 @@ def knock_out(obs, rate):
     return out
 
 
-def generate_dataset(n_train, n_test, time, model="lorenz", Dy=1, Di=1, f=None, g=None, x_0_in=None, lb=-2.5, ub=2.5):
+def generate_dataset(n_train, n_test, time, model="lorenz", Dy=1, Di=1, f=None, g=None, x_0_in=None, lb=-2.5, ub=2.5,
+                     input_dim=0):
+    """(`Di` is the reference's argument, unused there and here; `input_dim` > 0 switches the exogenous input on)"""
     if model not in _MODELS:
         raise ValueError("Unknown model {}".format(model))
+    if input_dim and (model != "fhn" or input_dim != 1 or f is not None):
+        raise ValueError("generated exogenous inputs: the FHN model with its own transition and one input channel (the injected "
+                         "current, --Di=1) only; got model %r, Di = %r" % (model, input_dim))
     Dx, step, params, G, var = _MODELS[model]
     f = f if f is not None else _Deterministic(step, params)
     g = g if g is not None else _LinearGaussian(G, var * np.eye(Dy))
@@ -124,7 +150,14 @@ def generate_dataset(n_train, n_test, time, model="lorenz", Dy=1, Di=1, f=None, 
 
     hidden = np.zeros((n_train + n_test, time, Dx))
     obs = np.zeros((n_train + n_test, time, Dy))
+    inputs = np.zeros((n_train + n_test, time, input_dim))
     for i in range(n_train + n_test):
         x_0 = np.random.uniform(low=lb, high=ub, size=Dx) if x_0_in is None else x_0_in
-        hidden[i], obs[i] = generate_hidden_obs(time, Dx, Dy, x_0, f, g)
+        if input_dim:
+            inputs[i] = pulse_train(time, input_dim)
+            hidden[i], obs[i] = generate_hidden_obs(time, Dx, Dy, x_0, f, g, v=inputs[i])
+        else:
+            hidden[i], obs[i] = generate_hidden_obs(time, Dx, Dy, x_0, f, g)
+    if input_dim:
+        return hidden[:n_train], hidden[n_train:], obs[:n_train], obs[n_train:], inputs[:n_train], inputs[n_train:]
     return hidden[:n_train], hidden[n_train:], obs[:n_train], obs[n_train:]

@@ -8,6 +8,10 @@ Rules kept from the reference (cited lines are its file):
   * 2-D observation arrays (n, T) get a trailing feature axis (:23-25);
   * latents: Xtrue is split at n_train (:31-33); else Xtrain / Xtest (:34-36); else zeros of shape (n, T, Dx) --
     unless the proposal is centred on the true latents (q_uses_true_X), which then is an error (:37-42).
+
+Exogenous inputs (FLAGS.Di > 0, not in the reference): Vtrain and Vtest / Vvalid -- the held-out key that goes with the chosen
+held-out observations -- are read as well, must be finite and (n, T, Di) like their observations, and follow the four arrays.
+With Di = 0 nothing else is read and the result is the reference's.
 """
 import pickle
 
@@ -30,6 +34,28 @@ def _held_out_observations(data):
     return found[0] if len(found) == 1 or found[0].shape[0] > found[1].shape[0] else found[1]
 
 
+def _held_out_key(data):
+    """the key _held_out_observations takes its array from"""
+    found = [k for k in _HELD_OUT_KEYS if k in data]
+    return found[0] if len(found) == 1 or data[found[0]].shape[0] > data[found[1]].shape[0] else found[1]
+
+
+def _inputs(data, key, like, Di):
+    """data[key] as the exogenous inputs of the observations `like`: present, (n, T, Di), finite"""
+    if key not in data:
+        raise ValueError("--Di = %d: the data set holds no exogenous inputs under %r (Vtrain and Vtest / Vvalid beside the "
+                         "observations)" % (Di, key))
+    v = np.asarray(data[key], dtype=float)
+    if v.ndim == 2:
+        v = v[:, :, None]
+    if v.shape != like.shape[:2] + (Di,):
+        raise ValueError("--Di = %d: %s must be (n, T, Di) = %s like its observations, got %s"
+                         % (Di, key, like.shape[:2] + (Di,), v.shape))
+    if not np.isfinite(v).all():
+        raise ValueError("--Di = %d: %s holds non-finite values; an input is given, never missing" % (Di, key))
+    return v
+
+
 def _with_feature_axis(a):
     return a[:, :, None] if a.ndim == 2 else a
 
@@ -45,7 +71,7 @@ def _latents(data, n_train, n_test, T, Dx, required):
     return np.zeros((n_train, T, Dx)), np.zeros((n_test, T, Dx))
 
 
-def load_data(path, Dx, isPython2, q_uses_true_X):
+def load_data(path, Dx, isPython2, q_uses_true_X, Di=0):
     data = _read_pickle(path, isPython2)
     obs_train = data["Ytrain"]
     obs_test = _held_out_observations(data)
@@ -53,4 +79,7 @@ def load_data(path, Dx, isPython2, q_uses_true_X):
         obs_train, obs_test = _with_feature_axis(obs_train), _with_feature_axis(obs_test)
     n_train, T = obs_train.shape[:2]
     hidden_train, hidden_test = _latents(data, n_train, obs_test.shape[0], T, Dx, required=q_uses_true_X)
+    if Di > 0:
+        return (hidden_train, hidden_test, obs_train, obs_test,
+                _inputs(data, "Vtrain", obs_train, Di), _inputs(data, "V" + _held_out_key(data)[1:], obs_test, Di))
     return hidden_train, hidden_test, obs_train, obs_test
