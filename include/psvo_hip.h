@@ -348,6 +348,27 @@ int psvo_particle_forecast_missing(const psvo_desc* desc, int K,
                            float* ymean, float* yvar, float* xmean, float* lpd, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Particle forecast under exogenous inputs (added within ABI 6: purely additive).  psvo_particle_forecast_missing with an
+ * input-driven transition, x_{t+1} ~ f(. | x_t, v_t): the first layer of MLP_f is applied to concat[x, v], and the input's share
+ * of its pre-activation is handed over as rows, as psvo_filter_forward_wobs_input takes them,
+ *     hb_f[s,b,:] = v[b,s,:] W1[Dx:]                  (Tv,B,H) at the kernel width, zero beyond the model's hidden width,
+ * while f.W1 holds the state's rows W1[:Dx] alone.  The transition from horizon k to k + 1 of origin (t, b) is
+ *     x^(k+1)_n = relu(x^(k)_n W1[:Dx] + (b1 + hb_f[t+k,b,:])) W2 + b2 + sig_f (*) eps[k,t,b,:,n]:
+ * the state of origin t at horizon k meets v_{t+k}.  Tv >= T; rows T .. Tv-1 are inputs planned past the end of the data, and
+ * where t + k >= Tv the bias is b1 alone (zero input, the rule of the filter's t = 0 terms).  b1 + hb_f is ONE fp32 add, made
+ * once per (origin, horizon); everything else is the arithmetic of psvo_particle_forecast_missing in its order, so hb_f = 0
+ * gives that call's outputs bit for bit, and with K = 0 no row is used.  Emission, moments, lpd, NaN = not observed and the fold
+ * orders are those of psvo_particle_forecast_missing; no atomics: two calls give bit-identical outputs.
+ * PSVO_ERR_INVALID for hb_f == NULL or Tv < T (beside the refusals of psvo_particle_forecast); PSVO_ERR_UNSUPPORTED exactly
+ * where psvo_particle_forecast_missing answers it.
+ * ------------------------------------------------------------------------------------------- */
+int psvo_particle_forecast_input(const psvo_desc* desc, int K,
+                           const psvo_mlp* f, const psvo_mlp* g, const float* sig_f, const float* sig_g,
+                           const float* X, const float* logW, const float* obs, const float* eps,
+                           float* ymean, float* yvar, float* xmean, float* lpd,
+                           const float* hb_f, int Tv, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * MAP trajectory (particle Viterbi; Godsill, Doucet and West 2001) on the particle system a forward filter left in HBM: the
  * single most probable path through the T x N lattice of particles, where psvo_ffbs_smooth gives marginals and
  * psvo_ffbs_sample random paths.  Added within ABI 6: purely additive.  Notation of psvo_ffbs_smooth; per sequence b:
@@ -951,6 +972,43 @@ int psvo_mlp_wgrad_rowbias_blocks(long long S);
 int psvo_mlp_wgrad_rowbias(long long S, int L, int Din, int H, int Dout, const float* X, const float* dOut,
                            const float* hb, const psvo_mlp* w, float* partial, float* grad, float* dhb,
                            int accumulate, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Exogenous inputs with adaptive resampling (added within ABI 6: purely additive).  The intersection of two sections above and
+ * nothing new: psvo_filter_forward_wobs_input / psvo_filter_backward_wobs_input -- the first-layer bias of MLP_q1 / MLP_f at step t
+ * is b1 + hb[t,b,:], one fp32 add -- with the decision of psvo_filter_forward_wobs_adaptive, word for word:
+ * ESS[t,b] = (sum_n w_n)^2 / sum_n w_n^2 taken from the weights as they are, the sequence inherits the draw iff
+ * !(ESS[t,b] >= ess_frac * N) or as rs_in says, and the draw is made and written at every step; a kept particle carries its own
+ * means MLP_q1(x_t; v_t), MLP_f(x_t; v_t) and its normalised weight into the next step.
+ *  forward:  the arguments of psvo_filter_forward_wobs_adaptive, then hb_q1, hb_f (ahead of stream).  hb = 0 gives the outputs of
+ *            psvo_filter_forward_wobs_missing_adaptive bit for bit; ess_frac > 1 those of psvo_filter_forward_wobs_input with
+ *            desc->resample = 1; a threshold no ESS falls below gives X, Fm, logW and lse of that call with desc->resample = 0.
+ *  reverse:  the arguments of psvo_filter_backward_wobs_adaptive, then hb_q1, hb_f; upstream gradient dlse only; rs (T,B) is a
+ *            constant.  dP / dF are the rows d MLP_q1 / d MLP_f; psvo_mlp_wgrad_rowbias turns them into the weight gradients and
+ *            d hb, unchanged.
+ *  Envelope: that of the input pair (1 <= Dy <= 32, every emission form, T >= 2) with the adaptive contract ahead of it
+ *  (ess_frac > 0, desc->resample, rs_out and ess_out / rs: else PSVO_ERR_INVALID).  No EXT form.
+ * ------------------------------------------------------------------------------------------- */
+int psvo_filter_forward_wobs_input_adaptive(const psvo_desc* desc,
+                             const psvo_mlp* q1, const psvo_mlp* f, const psvo_mlp* g,
+                             const float* sig_q1, const float* sig_q2, const float* sig_f, const float* sig_g,
+                             const float* mu2,
+                             const float* m0, const float* sig0, const float* fm0, const float* fsig0,
+                             const float* obs, const float* eps, const float* u, const int32_t* idx_in,
+                             float* X, float* Xanc, float* Fm, float* P1, float* logW, int32_t* idx_out,
+                             float* lse, float ess_frac, const int32_t* rs_in, int32_t* rs_out, float* ess_out,
+                             const float* hb_q1, const float* hb_f, void* stream);
+int psvo_filter_backward_wobs_input_adaptive(const psvo_desc* desc,
+                              const psvo_mlp* q1, const psvo_mlp* f, const psvo_mlp* g,
+                              const float* sig_q1, const float* sig_q2, const float* sig_f, const float* sig_g,
+                              const float* mu2,
+                              const float* m0, const float* sig0, const float* fm0, const float* fsig0,
+                              const float* obs, const float* eps,
+                              const float* X, const float* Fm, const float* P1, const float* logW, const float* lse,
+                              const int32_t* idx, const float* dlse,
+                              float* dP, float* dF, float* dG, float* dmu2, float* dm0, float* dfm0,
+                              float* dsig_q1, float* dsig_q2, float* dsig_f, float* dsig_g, float* dsig0, float* dfsig0,
+                              float* ws, const int32_t* rs, const float* hb_q1, const float* hb_f, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Adaptive resampling on missing observations (added within ABI 6: purely additive).  The intersection of the two sections

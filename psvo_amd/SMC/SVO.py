@@ -10,19 +10,21 @@ import torch
 
 from .. import ops
 from ..autograd import (FilterAdaptiveFunction, FilterCovFunction, FilterFunction, FilterWobsAdaptiveFunction,
-                        FilterWobsFunction, FilterWobsInputFunction, FilterWobsMissingAdaptiveFunction,
-                        FilterWobsMissingBsimFunction, FilterWobsMissingFunction)
+                        FilterWobsFunction, FilterWobsInputAdaptiveFunction, FilterWobsInputFunction,
+                        FilterWobsMissingAdaptiveFunction, FilterWobsMissingBsimFunction, FilterWobsMissingFunction)
 
 
 def check_resample_ess(raw, never_resamples=False, backward_simulation=False, output_cov=False, Dy=1, plain_dy=2,
-                       wide_obs=False, layers=(), wobs_max_dy=32, missing_obs=False):
+                       wide_obs=False, layers=(), wobs_max_dy=32, missing_obs=False, inputs=False):
     """--resample_ess as a float: 0.0 = off, else the ESS threshold tau as a fraction of N, 0 < tau <= 1.  ValueError, naming
     the limit, for a threshold outside that range and for everything the adaptive kernels do not cover (runner.main calls this
     on the flags before it touches a device, SVO.__init__ on the model it is given).  `wide_obs`: --resample_ess_wide_obs, the
     adaptive wide-observation kernels for plain_dy < Dy <= wobs_max_dy (`layers`: the hidden layers of the per-particle MLPs,
     one each there); no effect at Dy <= plain_dy or with the threshold off.  `missing_obs`: --missing_obs with
     --resample_ess_missing_obs, the adaptive missing-observation kernels at every width check_missing_obs accepts (which also
-    checks width and depth there); `wide_obs` is not needed and has no effect then."""
+    checks width and depth there); `wide_obs` is not needed and has no effect then.  `inputs`: --Di > 0 with
+    --resample_ess_inputs, the adaptive input-driven kernels at every width check_inputs accepts (which also checks width and
+    depth there); `wide_obs` is not needed then either."""
     tau = float(0.0 if raw is None else raw)
     if tau == 0.0:
         return 0.0
@@ -38,7 +40,7 @@ def check_resample_ess(raw, never_resamples=False, backward_simulation=False, ou
     if output_cov:
         raise ValueError("--resample_ess with output_cov: the state-dependent-scale kernels (psvo_filter_forward_cov) have "
                          "no adaptive form; adaptive resampling takes state-independent scales only")
-    if missing_obs:
+    if missing_obs or inputs:
         return tau
     if Dy > plain_dy and not wide_obs:
         raise ValueError("--resample_ess with Dy = %d: without --resample_ess_wide_obs the adaptive kernels are the plain filter "
@@ -112,11 +114,14 @@ def check_missing_obs(on, missing_rate=0.0, backward_simulation=False, resample_
 
 
 def check_inputs(Di, backward_simulation=False, resample_ess=0.0, particle_forecast=False, output_cov=False, Dy=1, layers=(),
-                 wobs_max_dy=32):
+                 wobs_max_dy=32, particle_forecast_inputs=False, resample_ess_inputs=False):
     """--Di (the width of the exogenous input v_t that drives f and q1) as an int, 0 = off.  ValueError, naming the limit, for a
     negative width and for everything the input-driven kernels (psvo_filter_forward_wobs_input) do not cover (runner.main calls
     this on the flags before it touches a device, SVO.__init__ on the model it is given).  `layers`: the hidden layers of the
-    per-particle MLPs, one each."""
+    per-particle MLPs, one each.  `particle_forecast_inputs` (--particle_forecast_inputs): --particle_forecast runs on
+    psvo_particle_forecast_input; `resample_ess_inputs` (--resample_ess_inputs): --resample_ess runs on
+    psvo_filter_forward_wobs_input_adaptive (SVO, AESMC).  Without them the two combinations stay refused, and neither has an
+    effect at Di = 0."""
     Di = int(0 if Di is None else Di)
     if Di < 0:
         raise ValueError("--Di = %d: the input dimension is a count, Di >= 0 (0 = autonomous dynamics)" % Di)
@@ -126,10 +131,10 @@ def check_inputs(Di, backward_simulation=False, resample_ess=0.0, particle_forec
     if backward_simulation:
         raise ValueError("--Di with --PSVO / --PSVOwR: %s; the backward simulations' own proposal networks have no input form"
                          % limit)
-    if float(resample_ess or 0.0) != 0.0:
+    if float(resample_ess or 0.0) != 0.0 and not resample_ess_inputs:
         raise ValueError("--Di with --resample_ess: %s, which resamples at every step (or never); the adaptive kernels have no "
                          "input form" % limit)
-    if particle_forecast:
+    if particle_forecast and not particle_forecast_inputs:
         raise ValueError("--Di with --particle_forecast: the forecast kernel (psvo_particle_forecast) propagates the cloud through "
                          "an autonomous f; it has no input form")
     if output_cov:
@@ -262,7 +267,9 @@ class SVO:
                             resample_ess=getattr(FLAGS, "resample_ess", 0.0),
                             particle_forecast=bool(getattr(FLAGS, "particle_forecast", False)),
                             output_cov=bool(getattr(model, "output_cov", False)), Dy=getattr(model, "Dy", cls._PLAIN_DY),
-                            layers=[t.Dhs for t in dict.fromkeys(trans)], wobs_max_dy=cls._WOBS_MAX_DY)
+                            layers=[t.Dhs for t in dict.fromkeys(trans)], wobs_max_dy=cls._WOBS_MAX_DY,
+                            particle_forecast_inputs=bool(getattr(FLAGS, "particle_forecast_inputs", False)),
+                            resample_ess_inputs=bool(getattr(FLAGS, "resample_ess_inputs", False)))
 
     @classmethod
     def _route_wide_obs(cls, model, bsim_wide_obs=False, missing_obs=False):
@@ -354,7 +361,9 @@ class SVO:
                                   plain_dy=cls._PLAIN_DY, wide_obs=bool(getattr(FLAGS, "resample_ess_wide_obs", False)),
                                   layers=[t.Dhs for t in dict.fromkeys(trans)], wobs_max_dy=cls._WOBS_MAX_DY,
                                   missing_obs=bool((getattr(model, "missing_obs", False) or getattr(FLAGS, "missing_obs", False))
-                                                   and getattr(FLAGS, "resample_ess_missing_obs", False)))
+                                                   and getattr(FLAGS, "resample_ess_missing_obs", False)),
+                                  inputs=bool((getattr(model, "Di", 0) or getattr(FLAGS, "Di", 0))
+                                              and getattr(FLAGS, "resample_ess_inputs", False)))
 
     # ------------------------------------------------------------------------------------------
     def get_log_ZSMC(self, obs, hidden, noise=None, inputs=None):
@@ -433,6 +442,15 @@ class SVO:
             raise ValueError("--Di = %d: inputs must be (batch, time, Di) = %s, got %s"
                              % (self.Di, (batch_size, time, self.Di), tuple(inputs.shape)))
         return inputs
+
+    def _input_share(self, v_TB, p):
+        """hb[t,b,:] = v_TB[t,b,:] W1[Dx:] (time, B, H) of the MLP tuple `p` at the kernels' width: the input's share of its first
+        layer"""
+        return v_TB @ p[0][self.Dx:]
+
+    def _state_rows(self, p):
+        """the MLP tuple `p` with the state's rows W1[:Dx] of its first layer alone, as the input-driven kernels take it"""
+        return None if p is None else (p[0][:self.Dx],) + tuple(p[1:])
 
     def _transition_scale(self, filt):
         """the constant scale the filter weighted the transition with (sigma_q1 when f shares q1's network, else sigma_f), or
@@ -676,9 +694,8 @@ class SVO:
             # small matrix product per network on the B T rows (torch differentiates it: d W1[Dx:] and d v come from d hb); the
             # kernels take W1[:Dx] and add hb to b1 step by step.  (W1 is padded to the kernel width: zeros in hb beyond it.)
             v_TB = inputs.transpose(0, 1).contiguous().float()
-            hb = (v_TB @ q1p[0][self.Dx:], None if fp is None else v_TB @ fp[0][self.Dx:])
-            q1p = (q1p[0][:self.Dx],) + tuple(q1p[1:])
-            fp = None if fp is None else (fp[0][:self.Dx],) + tuple(fp[1:])
+            hb = (self._input_share(v_TB, q1p), None if fp is None else self._input_share(v_TB, fp))
+            q1p, fp = self._state_rows(q1p), self._state_rows(fp)
         first, extra = self._mlp_args(q1p, fp, self._mlp_params(model.g_tran))
         sig_f = None if model.use_bootstrap else self._sigma(self.f)
         self._m0, self._sig0, self._fm0, self._fsig0 = m0, sig0, fm0, fsig0
@@ -693,6 +710,15 @@ class SVO:
             node, desc._gbufs = FilterWobsMissingFunction, None
             if self.uses_backward_simulation:       # (PSVO, FLAGS.BSim_missing_obs: Fm and logW carry gradients back)
                 node = FilterWobsMissingBsimFunction
+        if self.Di and self.resample_ess:
+            # psvo_filter_forward_wobs_input_adaptive / _backward_wobs_input_adaptive (FLAGS.resample_ess_inputs): the input
+            # route below with the decision per (step, sequence) made by the kernel
+            desc._gbufs = None
+            lse, Fm, logW, X, Xanc, idx, rs, ess = FilterWobsInputAdaptiveFunction.apply(
+                desc, obs_TB, eps, u, idx_in, self.resample_ess, noise.get("rs_f"),
+                *first, self._sigma(self.q1), sig_q2, sig_f, self._sigma(self.g), mu2, m0, sig0, fm0, fsig0, *extra, *hb)
+            return {"lse": lse, "Fm": Fm, "logW": logW, "X": X, "Xanc": Xanc, "idx": idx, "eps": eps, "u": u,
+                    "rs": rs, "ess": ess}
         if self.Di:                 # psvo_filter_forward_wobs_input / _backward_wobs_input: the same envelope, a bias row per step
             desc._gbufs = None
             lse, Fm, logW, X, Xanc, idx = FilterWobsInputFunction.apply(
@@ -828,7 +854,7 @@ class SVO:
         y_N_BxTxDy = [obs[:, k:, :] for k in range(n_steps + 1)]
         return y_hat_N_BxTxDy, y_N_BxTxDy
 
-    def particle_forecast(self, n_steps, hidden, obs, noise=None):
+    def particle_forecast(self, n_steps, hidden, obs, noise=None, inputs=None):
         """k-step predictive distribution of the cloud `hidden` (B,T,N,Dx), as log["Xs"] is, for k = 0 .. n_steps from every
         origin t (psvo_particle_forecast; not in the reference).  Every particle is pushed through f -- q1's network and scale
         when f shares them -- with transition noise: noise["eps_p"] (n_steps,T,B,Dx,N) injects the standard normals, else they
@@ -843,7 +869,11 @@ class SVO:
         With FLAGS.missing_obs and FLAGS.particle_forecast_missing_obs (psvo_particle_forecast_missing) a non-finite entry of `obs`
         was not observed: "lpd" sums the observed entries of the target row and is 0 where it has none, "n_observed" (B,T,n_steps+1)
         int is the number of observed entries of obs[b, t+k] (0 outside the data) and "valid" narrows to (B,T,n_steps+1): the
-        target lies inside the data and has at least one observed entry."""
+        target lies inside the data and has at least one observed entry.
+
+        With FLAGS.Di > 0 (FLAGS.particle_forecast_inputs; psvo_particle_forecast_input) `inputs` (B,Tv,Di), Tv >= T, drives f: the
+        state of origin t at horizon k meets v_{t+k}, as in n_step_prediction; rows T .. Tv-1 are inputs planned past the data,
+        and where t + k >= Tv the input is zero.  ValueError when it is missing or mis-shaped.  The returned keys are unchanged."""
         if torch.is_grad_enabled():
             raise ValueError("particle_forecast has no gradient: call it under torch.no_grad() (evaluation only)")
         self._route_forecast(self.model)
@@ -866,9 +896,22 @@ class SVO:
             eps = self._randn(K, T, B, Dx, N, device=X.device)
         f_tran, f_dist = (model.q1_tran, self.q1) if model.use_bootstrap else (model.f_tran, self.f)
         desc = ops.make_desc(B, T, N, 1, Dx, model.Dy, H, bootstrap=model.use_bootstrap, emission=self._emission_code(), layers=1)
-        fc = ops.particle_forecast(desc, K, _c(self._mlp_params(f_tran)), _c(self._mlp_params(model.g_tran)),
+        fp, extra = _c(self._mlp_params(f_tran)), {"missing": True} if missing else {}
+        if getattr(self, "Di", 0):
+            # the bias rows of SMC, over the Tv rows given (self.Dx: get_log_ZSMC sets it, and this call may come before any)
+            if inputs is None:
+                self._check_input_rows(inputs, B, T)
+            if inputs.dim() != 3 or inputs.shape[0] != B or inputs.shape[1] < T or inputs.shape[2] != self.Di:
+                raise ValueError("--Di = %d: particle_forecast inputs must be (batch, Tv, Di) = (%d, Tv >= %d, %d), got %s"
+                                 % (self.Di, B, T, self.Di, tuple(inputs.shape)))
+            self.Dx = Dx
+            extra = {"hb_f": _c(self._input_share(inputs.transpose(0, 1).contiguous().float(), fp))}
+            fp = self._state_rows(fp)
+        elif inputs is not None:
+            raise ValueError("particle_forecast: inputs given to a model without an input channel (--Di = 0)")
+        fc = ops.particle_forecast(desc, K, fp, _c(self._mlp_params(model.g_tran)),
                                    _c(self._sigma(f_dist)), _c(self._sigma(self.g)), X, obs=obs_TB, eps=eps,
-                                   **({"missing": True} if missing else {}))      # (without the flag: the call as it always was)
+                                   **extra)      # (without the flags: the call as it always was)
         t = torch.arange(T, device=X.device)
         out = {"y_mean": fc["ymean"].permute(2, 1, 0, 3), "y_var": fc["yvar"].permute(2, 1, 0, 3),
                "x_mean": fc["xmean"].permute(2, 1, 0, 3), "lpd": fc["lpd"].permute(2, 1, 0),

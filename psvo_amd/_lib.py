@@ -66,6 +66,9 @@ SIGNATURES = {
     "psvo_filter_backward_wobs_missing_adaptive": (ctypes.c_int, [_DESC, _MLP, _MLP, _MLP] + [_P] * 31 + [_P, _P]),
     "psvo_filter_forward_wobs_input": (ctypes.c_int, [_DESC, _MLP, _MLP, _MLP] + [_P] * 20 + [_P, _P] + [_P]),
     "psvo_filter_backward_wobs_input": (ctypes.c_int, [_DESC, _MLP, _MLP, _MLP] + [_P] * 31 + [_P, _P] + [_P]),
+    "psvo_filter_forward_wobs_input_adaptive": (ctypes.c_int, [_DESC, _MLP, _MLP, _MLP] + [_P] * 20
+                                                + [ctypes.c_float, _P, _P, _P] + [_P, _P] + [_P]),
+    "psvo_filter_backward_wobs_input_adaptive": (ctypes.c_int, [_DESC, _MLP, _MLP, _MLP] + [_P] * 31 + [_P] + [_P, _P] + [_P]),
     "psvo_mlp_wgrad_rowbias_blocks": (ctypes.c_int, [ctypes.c_longlong]),
     "psvo_mlp_wgrad_rowbias": (ctypes.c_int, [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                               _P, _P, _P, _MLP, _P, _P, _P, ctypes.c_int, _P]),
@@ -86,6 +89,7 @@ SIGNATURES = {
     "psvo_ffbs_sample": (ctypes.c_int, [_DESC] + [_P] * 11 + [_P]),
     "psvo_particle_forecast": (ctypes.c_int, [_DESC, ctypes.c_int, _MLP, _MLP] + [_P] * 10 + [_P]),
     "psvo_particle_forecast_missing": (ctypes.c_int, [_DESC, ctypes.c_int, _MLP, _MLP] + [_P] * 10 + [_P]),
+    "psvo_particle_forecast_input": (ctypes.c_int, [_DESC, ctypes.c_int, _MLP, _MLP] + [_P] * 10 + [_P, ctypes.c_int] + [_P]),
     "psvo_map_path": (ctypes.c_int, [_DESC, _MLP] + [_P] * 12 + [_P]),
     "psvo_filter_backward_cov": (ctypes.c_int, [_DESC, _MLP, _MLP, _MLP] + [_P] * 39 + [_P]),
     "psvo_bsim_forward_cov": (ctypes.c_int, [_DESC] + [_P] * 4 + [_MLP, _MLP, _MLP] + [_P] * 23 + [_P]),

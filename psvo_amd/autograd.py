@@ -450,6 +450,29 @@ class FilterWobsInputFunction(torch.autograd.Function):
         return (None,) * 5 + _filter_grads(r, ctx.desc, *rest[5:9], None) + (r["dhb_q1"], r["dhb_f"])
 
 
+class FilterWobsInputAdaptiveFunction(torch.autograd.Function):
+    """psvo_filter_forward_wobs_input_adaptive / psvo_filter_backward_wobs_input_adaptive: FilterWobsInputFunction resampling a
+    sequence only where its effective sample size has fallen below ess_frac N (FLAGS.Di > 0 with FLAGS.resample_ess and
+    FLAGS.resample_ess_inputs; 1 <= Dy <= 32, one hidden layer, every emission form).
+
+    apply(<the arguments of FilterAdaptiveFunction>, hb_q1, hb_f) takes the two bias-row tensors of FilterWobsInputFunction behind
+    everything else and returns FilterAdaptiveFunction's outputs; only lse is differentiable.  The reverse returns d hb_q1 /
+    d hb_f as FilterWobsInputFunction does.  One stream, gradients returned as tensors."""
+
+    @staticmethod
+    def forward(ctx, desc, obs_TB, eps, u, idx_in, ess_frac, rs_in, *t):
+        ctx.hb = (_cf(t[-2]), _cf(t[-1]))
+        filt = _filter_forward(ctx, ops.filter_forward_wobs_input_adaptive, desc, obs_TB, eps, u, idx_in, t[:-2], hb=ctx.hb,
+                               ess_frac=ess_frac, rs_in=rs_in)
+        return _adaptive_outputs(ctx, filt)
+
+    @staticmethod
+    def backward(ctx, dlse, *_):
+        q1, f, g, rest, obs_TB, eps = ctx.saved
+        r = ops.filter_backward_wobs_input_adaptive(ctx.desc, q1, f, g, *rest, obs_TB, eps, ctx.filt, dlse=_cg(dlse), hb=ctx.hb)
+        return (None,) * 7 + _filter_grads(r, ctx.desc, *rest[5:9], None) + (r["dhb_q1"], r["dhb_f"])
+
+
 class FilterWobsMissingBsimFunction(torch.autograd.Function):
     """psvo_filter_forward_wobs_missing / psvo_filter_backward_wobs_missing_ext: FilterWobsMissingFunction in front of a
     BsimWobsMissingFunction (PSVO under FLAGS.missing_obs with FLAGS.BSim_missing_obs).

@@ -15,7 +15,7 @@ LIB = os.path.join(CSRC, "libpsvo_hip.so")
 SOURCES = ["bsim_wobs.hip", "bsim_wobs_ms.hip", "bsim_cov.hip", "psvowr_bwd_l2.hip", "psvowr_bwd.hip", "bsim_bwd_dx4_l2.hip", "bsim_fwd_l2.hip", "bsim_fwd.hip",
            "bsim_bwd_dx2_l2.hip", "bsim_bwd_dx3_l2.hip", "psvowr_fwd.hip", "psvowr_fwd_l2.hip", "bsim_bwd_dx4.hip",
            "bsim_bwd_dx2.hip", "bsim_bwd_dx3.hip", "filter_bwd_l2.hip", "bsim_bwd2_dx2.hip", "filter_bwd.hip",
-           "filter_fwd_l2.hip", "filter_cov.hip", "filter_wobs.hip", "filter_wobs_in.hip", "filter_fwd.hip", "bsim_bwd2_dx4.hip", "bsim_bwd2_dx3.hip", "mlp_grad.hip", "lstm_bwd.hip",
+           "filter_fwd_l2.hip", "filter_cov.hip", "filter_wobs.hip", "filter_wobs_in.hip", "filter_wobs_inad.hip", "filter_fwd.hip", "bsim_bwd2_dx4.hip", "bsim_bwd2_dx3.hip", "mlp_grad.hip", "lstm_bwd.hip",
            "lstm.hip", "rows_mlp.hip", "bsim_bwd.hip", "api.hip", "dense.hip", "adam.hip", "ffbs.hip", "ffbsi.hip",
            "forecast.hip", "map_path.hip", "mlp_wgrad_rowbias.hip"]
 HEADERS = ["common.h", "mlp2_valu.h", os.path.join("..", "..", "include", "psvo_hip.h")]      # every unit includes these
@@ -25,9 +25,11 @@ UNIT_HEADERS = {"bsim_bwd_impl.h": ("bsim_bwd_dx", "bsim_bwd2_dx", "bsim_bwd.hip
                 "ffbs_pair.h": ("ffbs.hip", "ffbsi.hip", "map_path.hip"),
                 "filter_fwd_impl.h": ("filter_fwd",),
                 "filter_bwd_impl.h": ("filter_bwd",),
-                "filter_wobs_impl.h": ("filter_wobs.hip", "filter_wobs_in.hip"),
-                "filter_wobs_args.h": ("filter_wobs.hip", "filter_wobs_in.hip"),
-                "wobs_common.h": ("filter_wobs.hip", "filter_wobs_in.hip", "bsim_wobs", "forecast.hip", "map_path.hip")}
+                "filter_wobs_impl.h": ("filter_wobs.hip", "filter_wobs_in.hip", "filter_wobs_inad.hip"),
+                "filter_wobs_args.h": ("filter_wobs.hip", "filter_wobs_in.hip", "filter_wobs_inad.hip"),
+                "row_bias.h": ("filter_wobs_in.hip", "filter_wobs_inad.hip", "forecast.hip"),
+                "wobs_common.h": ("filter_wobs.hip", "filter_wobs_in.hip", "filter_wobs_inad.hip", "bsim_wobs", "forecast.hip",
+                                  "map_path.hip")}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-slp-vectorize"]
 # Round 2 built the two-hidden-layer units with `-mllvm -vgpr-regalloc=basic`: their per-lane H x H layer held 2 H values per
 # lane and under that pressure the default (greedy) allocator split live ranges around divergent regions, with hipcc 7.2 placing

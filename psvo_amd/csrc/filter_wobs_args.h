@@ -1,4 +1,4 @@
-// What the units of the wide-observation filter kernels share (filter_wobs.hip, filter_wobs_in.hip): the argument blocks of the
+// What the units of the wide-observation filter kernels share (filter_wobs.hip, filter_wobs_in.hip, filter_wobs_inad.hip): the argument blocks of the
 // two kernels of filter_wobs_impl.h, their LDS sizes, and the envelope and dispatch of the entry points.
 #pragma once
 #include "wobs_common.h"
@@ -80,6 +80,17 @@ struct FwdArgsIn : FwdArgs {
 struct BwdArgsIn : BwdArgs {
     const float *hb_q1, *hb_f;
 };
+
+// Both (psvo_filter_forward_wobs_input_adaptive / psvo_filter_backward_wobs_input_adaptive, filter_wobs_inad.hip): the adaptive
+// blocks with the bias rows behind them, so that every field keeps the offset it has in FwdArgsAd / BwdArgsAd -- rs is still
+// the last word of the BwdArgsAd part, where arg_rs() fetches it.  Types of their own once more.
+struct FwdArgsInAd : FwdArgsAd {
+    const float *hb_q1, *hb_f;
+};
+struct BwdArgsInAd : BwdArgsAd {
+    const float *hb_q1, *hb_f;
+};
+static_assert(sizeof(BwdArgsInAd) == sizeof(BwdArgsAd) + 2 * sizeof(const float*), "the bias rows sit behind rs");
 
 // (ms: the missing-observation form keeps one more row, the per-output constants, where the count form has its log-factorials)
 template <int DX, int H>

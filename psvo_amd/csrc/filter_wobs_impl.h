@@ -34,9 +34,24 @@
 // and land in the half that the step BEFORE this one read, ahead of the step's own stores and of the barrier that ends it.  Nothing of step t reads
 // that half, so neither the IWAE reverse step (no barrier between bwd_input and the end of the step) nor a one-wave forward
 // step (block_max has no barrier at nw == 1) can see a row replaced under it; no barrier is added.  Every MQ::eval<true> /
-// MQ::bwd_input<true> of step t reads the row of step t (RowBias in filter_wobs_in.hip: the same operations, the bias words
+// MQ::bwd_input<true> of step t reads the row of step t (RowBias in row_bias.h: the same operations, the bias words
 // taken from the row).
-#if PSVO_IN
+//
+// All three (PSVO_IN = 1, PSVO_MS = 1 and PSVO_AD = 1; filter_wobs_inad.hip: filter_fwd_wobs_inad_kernel / filter_bwd_wobs_inad_kernel,
+// the kernels of psvo_filter_forward_wobs_input_adaptive / psvo_filter_backward_wobs_input_adaptive): a sixth compilation and no new
+// line.  The two sets of lines do not touch: the adaptive form's red[40 + wave] ends at red[47] and hbuf starts behind
+// red + 48 + 2 kMaxDy (forward), behind the d sig_g columns (reverse); the decision feeds selects and, in the reverse pass, scalar
+// branches around the gather, none of which holds a read or a store of hbuf; and every barrier of the input form is taken at
+// every step of the adaptive form too (block_sum's under `!rs_here` by every wave or by none).  The semantics are the
+// intersection of the two definitions: ESS from the weights as they are, the draw made and written every step, rs a constant of
+// the reverse pass, the rows d P / d F left for psvo_mlp_wgrad_rowbias.  The argument blocks are the adaptive ones with the bias
+// rows behind them (filter_wobs_args.h).
+#if PSVO_IN && PSVO_AD
+#define PSVO_WOBS_FWD_KERNEL filter_fwd_wobs_inad_kernel
+#define PSVO_WOBS_BWD_KERNEL filter_bwd_wobs_inad_kernel
+#define PSVO_WOBS_FWD_ARGS FwdArgsInAd
+#define PSVO_WOBS_BWD_ARGS BwdArgsInAd
+#elif PSVO_IN
 #define PSVO_WOBS_FWD_KERNEL filter_fwd_wobs_in_kernel
 #define PSVO_WOBS_BWD_KERNEL filter_bwd_wobs_in_kernel
 #define PSVO_WOBS_FWD_ARGS FwdArgsIn

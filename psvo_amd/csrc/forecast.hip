@@ -17,7 +17,20 @@
 // readers reach after reading; the observation row of horizon k + 1 is staged ahead of barrier k in the same way.
 // No atomics; every sum is a wave scan or a fold over <= 8 waves in wave order: the output is the same bit for bit on every
 // run, whatever PSVO_TUNE_DETERMINISTIC says.
+//
+// Exogenous inputs (IN: psvo_particle_forecast_input, on top of MS): the transition from horizon k to k + 1 of origin (t, b) takes
+// the first-layer bias b1 + hb_f[t+k,b,:] where the others take b1 (b1 alone where t + k >= Tv: zero input).  The EFFECTIVE row is
+// kept in a two-half LDS buffer hbuf[2][kFcOrigins][H], a row per origin of the workgroup: lane j < H of the origin's first wave
+// requests word j of row k at the top of horizon k, beside the noise, and stores b1[j] + word (ONE fp32 add, as the filter's
+// input form makes it; b1 from the LDS image) into half k & 1 next to stage_row(k + 1), ahead of barrier k.  The transition of
+// horizon k reads that half behind barrier k (row_bias.h: RowBias, the operations of MlpLds::eval<true> in their order, so that
+// hb_f = 0 gives the bits of the missing form).  The half is next written in horizon k + 2, behind barrier k + 1, which every
+// reader of row k has reached after its transition; the other half, which horizon k - 1's transition may still be reading while
+// row k is stored, is not touched.  So no barrier is added: a horizon stays ONE workgroup barrier.  (A row stored one horizon
+// earlier -- row k + 1 ahead of barrier k -- would land in the half that the slower waves of the origin still read in the
+// transition of horizon k - 1.)  A clamped dead origin of the last workgroup stages the row of origin T B - 1: in bounds.
 #include "common.h"
+#include "row_bias.h"
 #include "wobs_common.h"
 
 namespace psvo {
@@ -36,6 +49,18 @@ struct ForecastArgs {
     float *ymean, *yvar, *xmean, *lpd;
 };
 
+// the arguments of the input form: ForecastArgs field for field, so that what the kernel reads by name or by offset is found in
+// either, then the input's.  A type of its own: the argument block of the other instantiations does not move
+struct ForecastArgsIn {
+    int B, T, N, Dy, K;
+    int nwo, G;
+    psvo_mlp f, g;
+    const float *sig_f, *sig_g, *X, *logW, *obs, *eps;
+    float *ymean, *yvar, *xmean, *lpd;
+    const float* hb_f;                          // (Tv,B,H) the input's share of MLP_f's first layer
+    int Tv;                                     // rows of hb_f, Tv >= T
+};
+
 // EMIS: psvo_desc.emission as a compile-time form, so that the Gaussian instantiations carry neither the softplus nor the fp64
 // log-factorial of the count emission
 // MS: the missing-observation form (psvo_particle_forecast_missing), compile-time too, so that the MS = false instantiations keep
@@ -43,8 +68,10 @@ struct ForecastArgs {
 // same in every lane and only feeds a select; the log-density adds the observed terms in the order e = 0 .. Dy - 1, each Gaussian
 // term with its own constant c_e = -(log sig_g[e] + 1/2 log 2 pi) from one more LDS row (the filter's rule, filter_wobs_impl.h),
 // and a target row with nothing observed gives lpd = 0 exactly.  ymean, yvar and xmean do not read obs.
-template <int DX, int H, int EMIS, bool MS>
-__global__ void __launch_bounds__(512) forecast_kernel(const ForecastArgs a) {
+// IN: the input form (above), compile-time as well: every line of it sits under `if constexpr (IN)`.
+template <int DX, int H, int EMIS, bool MS, bool IN = false>
+__global__ void __launch_bounds__(512) forecast_kernel(const std::conditional_t<IN, ForecastArgsIn, ForecastArgs> a) {
+    using ForecastArgs = std::conditional_t<IN, ForecastArgsIn, psvo::ForecastArgs>;     // (what PSVO_ARG takes its offsets from)
     using MF = MlpLds<DX, H, DX, 1>;
     using MG = wobs::GLds<DX, H>;
     __shared__ __attribute__((aligned(16))) float wf[MF::kSize];
@@ -54,6 +81,7 @@ __global__ void __launch_bounds__(512) forecast_kernel(const ForecastArgs a) {
     __shared__ float lfbuf[2][kFcOrigins][kMaxDy];              // count emission: log Gamma(y + 1) of the rows in ybuf
     __shared__ float red[2][kFcWaves][kFcSlot];                 // per-wave partial sums of horizon k (k & 1)
     __shared__ float cg[kMaxDy];                                // MS, Gaussian forms: the constant of one term (else unused)
+    __shared__ __attribute__((aligned(16))) float hbuf[IN ? 2 : 1][IN ? kFcOrigins : 1][IN ? H : 4];   // IN: bias rows of horizon k (k & 1), k - 1
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, NT = blockDim.x;
     const int N = a.N, Dy = a.Dy, K = a.K;
@@ -64,6 +92,11 @@ __global__ void __launch_bounds__(512) forecast_kernel(const ForecastArgs a) {
     asm volatile("" : "+v"(B));
     asm volatile("" : "+v"(T));
     asm volatile("" : "+v"(nwo));
+    [[maybe_unused]] int Tv = 0;
+    if constexpr (IN) {
+        Tv = a.Tv;
+        asm volatile("" : "+v"(Tv));
+    }
     const int TB = T * B;
     const int og = wave / nwo, wo = wave - og * nwo;             // origin within the workgroup, wave within the origin
     const int o_raw = blockIdx.x * a.G + og;
@@ -75,6 +108,13 @@ __global__ void __launch_bounds__(512) forecast_kernel(const ForecastArgs a) {
     const int n = valid ? nl : N - 1;
     const float ninf = -__builtin_huge_valf();
     const bool first = wo == 0;                                  // the wave that stages the origin's rows and folds its slots
+    // IN: the lanes that stage the bias row (opaque, as the sizes above: a mask held across the loop costs the count
+    // instantiations a scalar pair they do not have)
+    [[maybe_unused]] int stager = 0;
+    if constexpr (IN) {
+        stager = first && lane < H;
+        asm volatile("" : "+v"(stager));
+    }
 
     MF::load(wf, a.f, tid, NT);
     MG::load(wg, a.g, Dy, tid, NT);
@@ -139,6 +179,11 @@ __global__ void __launch_bounds__(512) forecast_kernel(const ForecastArgs a) {
 #pragma unroll
             for (int d = 0; d < DX; ++d) ek[d] = eps[(((size_t)k * TB + o) * DX + d) * N + n];
         }
+        [[maybe_unused]] float hbk = 0.f;       // IN: word `lane` of hb_f[t+k,b,:], in flight during the emission walk
+        if constexpr (IN) {
+            if (more && stager && t + k < Tv)
+                hbk = PSVO_ARG(ForecastArgs, hb_f)[((size_t)(t + k) * B + b) * H + lane];
+        }
         float* slot = red[k & 1][wave];
         const float* y = ybuf[k & 1][og];
         const float* lf = lfbuf[k & 1][og];
@@ -199,6 +244,12 @@ __global__ void __launch_bounds__(512) forecast_kernel(const ForecastArgs a) {
             if (lane == 63) slot[2 * kMaxDy + d] = sx;
         }
         if (more) stage_row(k + 1);
+        if constexpr (IN) {     // the bias row of THIS horizon's transition: read behind the barrier, its half rewritten at k + 2
+            if (more && stager) {
+                const float b1 = wf[MF::kB1 + lane];
+                hbuf[k & 1][og][lane] = t + k < Tv ? b1 + hbk : b1;
+            }
+        }
         __syncthreads();
 
         // ---- fold the origin's slots in wave order: lane j of its first wave owns output j -------------------------------
@@ -241,31 +292,34 @@ __global__ void __launch_bounds__(512) forecast_kernel(const ForecastArgs a) {
         // ---- transition -----------------------------------------------------------------------------------------------------
         if (more) {
             float fx[DX];
-            MF::template eval<true>(wf, x, fx);
+            if constexpr (IN) wobs::RowBias<DX, H>::eval(wf, hbuf[k & 1][og], x, fx);
+            else MF::template eval<true>(wf, x, fx);
 #pragma unroll
             for (int d = 0; d < DX; ++d) x[d] = fmaf(sf[d], ek[d], fx[d]);
         }
     }
 }
 
-template <int DX, int H, int EMIS, bool MS>
-static int launch_forecast(ForecastArgs& a, hipStream_t stream) {
+template <int DX, int H, int EMIS, bool MS, bool IN = false, class Args = ForecastArgs>
+static int launch_forecast(Args& a, hipStream_t stream) {
     const long long TB = (long long)a.T * a.B;
     a.nwo = (a.N + 63) >> 6;
     a.G = a.nwo == 1 ? kFcOrigins : 1;
     const int NT = 64 * a.nwo * a.G;
     const int blocks = (int)((TB + a.G - 1) / a.G);
     clear_hip_error();
-    hipLaunchKernelGGL((forecast_kernel<DX, H, EMIS, MS>), dim3(blocks), dim3(NT), 0, stream, a);
+    hipLaunchKernelGGL((forecast_kernel<DX, H, EMIS, MS, IN>), dim3(blocks), dim3(NT), 0, stream, a);
     return launch_status();
 }
 
 }  // namespace psvo
 
-// the checks and the launch behind psvo_particle_forecast and psvo_particle_forecast_missing (ms)
+// the checks and the launch behind psvo_particle_forecast, psvo_particle_forecast_missing (ms) and psvo_particle_forecast_input
+// (in, on top of ms: hb_f and Tv are checked with the other arguments, ahead of the envelope)
 static int particle_forecast_checked(const psvo_desc* desc, int K, const psvo_mlp* f, const psvo_mlp* g, const float* sig_f,
                                      const float* sig_g, const float* X, const float* logW, const float* obs, const float* eps,
-                                     float* ymean, float* yvar, float* xmean, float* lpd, void* stream, bool ms) {
+                                     float* ymean, float* yvar, float* xmean, float* lpd, void* stream, bool ms,
+                                     bool in = false, const float* hb_f = nullptr, int Tv = 0) {
     using namespace psvo;
     if (!desc || !f || !g || !X) return PSVO_ERR_INVALID;
     if (!f->W1 || !f->b1 || !f->W2 || !f->b2 || !g->W1 || !g->b1 || !g->W2 || !g->b2) return PSVO_ERR_INVALID;
@@ -273,6 +327,7 @@ static int particle_forecast_checked(const psvo_desc* desc, int K, const psvo_ml
     if (lpd && !obs) return PSVO_ERR_INVALID;
     if (eps && !sig_f) return PSVO_ERR_INVALID;
     if (desc->B <= 0 || desc->T <= 0 || desc->N <= 0 || K < 0) return PSVO_ERR_INVALID;
+    if (in && (!hb_f || Tv < desc->T)) return PSVO_ERR_INVALID;
     if (!desc_layers_ok(desc) || desc->layers == 2) return PSVO_ERR_UNSUPPORTED;
     if (!desc_emission_ok(desc, 2)) return PSVO_ERR_UNSUPPORTED;
     if (!sig_g && desc->emission != 2) return PSVO_ERR_INVALID;
@@ -286,6 +341,19 @@ static int particle_forecast_checked(const psvo_desc* desc, int K, const psvo_ml
     a.sig_f = sig_f; a.sig_g = sig_g; a.X = X; a.logW = logW; a.obs = obs; a.eps = eps;
     a.ymean = ymean; a.yvar = yvar; a.xmean = xmean; a.lpd = lpd;
     hipStream_t s = static_cast<hipStream_t>(stream);
+    if (in) {
+        ForecastArgsIn ai;
+        ai.B = a.B; ai.T = a.T; ai.N = a.N; ai.Dy = a.Dy; ai.K = a.K;
+        ai.nwo = ai.G = 1;
+        ai.f = a.f; ai.g = a.g;
+        ai.sig_f = sig_f; ai.sig_g = sig_g; ai.X = X; ai.logW = logW; ai.obs = obs; ai.eps = eps;
+        ai.ymean = ymean; ai.yvar = yvar; ai.xmean = xmean; ai.lpd = lpd;
+        ai.hb_f = hb_f; ai.Tv = Tv;
+        return pick_dx(desc->Dx, [&](auto dx) {
+            return pick_h(desc->H, [&](auto h) {
+                return pick<0, 1, 2>(desc->emission, [&](auto em) {
+                    return launch_forecast<dx(), h(), em(), true, true>(ai, s); }); }); });
+    }
     return pick_dx(desc->Dx, [&](auto dx) {
         return pick_h(desc->H, [&](auto h) {
             return pick<0, 1, 2>(desc->emission, [&](auto em) {
@@ -303,4 +371,12 @@ extern "C" int psvo_particle_forecast_missing(const psvo_desc* desc, int K, cons
                                               const float* obs, const float* eps, float* ymean, float* yvar, float* xmean,
                                               float* lpd, void* stream) {
     return particle_forecast_checked(desc, K, f, g, sig_f, sig_g, X, logW, obs, eps, ymean, yvar, xmean, lpd, stream, true);
+}
+
+extern "C" int psvo_particle_forecast_input(const psvo_desc* desc, int K, const psvo_mlp* f, const psvo_mlp* g,
+                                            const float* sig_f, const float* sig_g, const float* X, const float* logW,
+                                            const float* obs, const float* eps, float* ymean, float* yvar, float* xmean,
+                                            float* lpd, const float* hb_f, int Tv, void* stream) {
+    return particle_forecast_checked(desc, K, f, g, sig_f, sig_g, X, logW, obs, eps, ymean, yvar, xmean, lpd, stream, true, true,
+                                     hb_f, Tv);
 }

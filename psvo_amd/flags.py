@@ -107,6 +107,12 @@ DEFINITIONS = [
     # and the proposal are driven by a given input, x_{t+1} ~ f(. | x_t, v_t), v (B,T,Di) read as Vtrain / Vtest beside the
     # observations.  0 = off: every path is exactly what it is without the flag.  Filter objectives (SVO, AESMC, IWAE)
     ("Di", int, 0, "SVO / AESMC / IWAE: dimension of the exogenous input v_t that drives f and q1 (0 = autonomous dynamics)"),
+    # (not in the reference's registry) the particle forecast of an input-driven model, on the input form of its kernel: the state
+    # of origin t at horizon k meets v_{t+k}.  Off by default: without it --Di with --particle_forecast stays refused
+    ("particle_forecast_inputs", bool, False, "run --particle_forecast with --Di: the cloud is propagated under the exogenous inputs"),
+    # (not in the reference's registry) adaptive resampling of an input-driven model, on the adaptive form of the input filter
+    # kernels.  Off by default: without it --Di with --resample_ess stays refused
+    ("resample_ess_inputs", bool, False, "SVO / AESMC: run --resample_ess with --Di on the adaptive input-driven kernels"),
     # MAP trajectory for the filter objectives (not in the reference's registry, which has no decoder): the single most probable
     # path through the filter's particles (particle Viterbi).  Off by default, evaluation only
     ("MAP_path", bool, False, "SVO / AESMC / IWAE: return the most probable trajectory through the filter's particles (particle Viterbi)"),

@@ -205,14 +205,17 @@ def _launch(name, fn, *args):
 # refusal: the wide adaptive route is filter_forward_wobs_adaptive)
 _ADAPTIVE_ENTRY = {"psvo_filter_forward": "psvo_filter_forward_adaptive",
                    "psvo_filter_forward_wobs_adaptive": "psvo_filter_forward_wobs_adaptive",
-                   "psvo_filter_forward_wobs_missing_adaptive": "psvo_filter_forward_wobs_missing_adaptive"}
+                   "psvo_filter_forward_wobs_missing_adaptive": "psvo_filter_forward_wobs_missing_adaptive",
+                   "psvo_filter_forward_wobs_input_adaptive": "psvo_filter_forward_wobs_input_adaptive"}
+# ... and the ones that take the bias rows hb
+_INPUT_ENTRY = ("psvo_filter_forward_wobs_input", "psvo_filter_forward_wobs_input_adaptive")
 
 
 def filter_forward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, fm0, fsig0,
                    obs, eps, u=None, idx_in=None, entry="psvo_filter_forward", ess_frac=None, rs_in=None, hb=None):
     """psvo_filter_forward (`entry`: an entry point with the same contract).  Returns dict(X, Xanc, Fm, logW, idx, lse).
-    hb = (hb_q1, hb_f) (T,B,H) each, hb_f None under bootstrap: the bias rows of psvo_filter_forward_wobs_input, the only entry
-    that takes them.
+    hb = (hb_q1, hb_f) (T,B,H) each, hb_f None under bootstrap: the bias rows of psvo_filter_forward_wobs_input and
+    psvo_filter_forward_wobs_input_adaptive, the only entries that take them.
     ess_frac (a float > 0): psvo_filter_forward_adaptive -- resampling where ESS < ess_frac N; rs_in (T,B) int32 teacher-forces
     the decisions; the dict then also holds rs (T,B) int32 and ess (T,B)."""
     lib = _lib.load()
@@ -240,7 +243,7 @@ def filter_forward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0, 
         _chk(rs_in, (T, B), "rs_in", torch.int32)
     elif rs_in is not None:
         raise ValueError("filter_forward: rs_in without ess_frac")
-    if (hb is not None) != (entry == "psvo_filter_forward_wobs_input"):
+    if (hb is not None) != (entry in _INPUT_ENTRY):
         raise ValueError("filter_forward: the bias rows hb belong to psvo_filter_forward_wobs_input, and it needs them")
     rows = ()
     if hb is not None:
@@ -294,6 +297,14 @@ def filter_forward_wobs_input(*args, hb, **kw):
     MLP_f at step t is b1 + hb[t,b,:], hb = (hb_q1, hb_f) (T,B,H) the input's share v_t W1[Dx:] of the hidden pre-activation
     (hb_f None under bootstrap); q1 / f hold W1[:Dx].  Arguments, outputs and layouts of filter_forward."""
     return filter_forward(*args, entry="psvo_filter_forward_wobs_input", hb=hb, **kw)
+
+
+def filter_forward_wobs_input_adaptive(*args, hb, ess_frac, rs_in=None, **kw):
+    """psvo_filter_forward_wobs_input_adaptive: filter_forward_wobs_input resampling where ESS < ess_frac N; arguments of
+    filter_forward with the bias rows hb = (hb_q1, hb_f), the result also holds rs (T,B) int32 and ess (T,B)."""
+    if ess_frac is None:
+        raise ValueError("filter_forward_wobs_input_adaptive needs the threshold ess_frac")
+    return filter_forward(*args, entry="psvo_filter_forward_wobs_input_adaptive", hb=hb, ess_frac=ess_frac, rs_in=rs_in, **kw)
 
 
 def filter_forward_wobs_missing_adaptive(*args, ess_frac, rs_in=None, **kw):
@@ -606,7 +617,8 @@ def filter_backward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0,
     psvo_filter_backward_wobs_missing_adaptive, following filt["rs"] (dlse only).
     hb = (hb_q1, hb_f) (with wobs and missing, dlse only): psvo_filter_backward_wobs_input, the reverse of
     filter_forward_wobs_input; the weight gradients of MLP_q1 / MLP_f are psvo_mlp_wgrad_rowbias and the result also holds
-    dhb_q1 and dhb_f (T,B,H; dhb_f None under bootstrap)."""
+    dhb_q1 and dhb_f (T,B,H; dhb_f None under bootstrap).  With adaptive="wobs" as well: psvo_filter_backward_wobs_input_adaptive,
+    following filt["rs"]."""
     lib = _lib.load()
     B, T, N, Dx, Dy, H = desc.B, desc.T, desc.N, desc.Dx, desc.Dy, desc.H
     dev = eps.device
@@ -651,14 +663,15 @@ def filter_backward(desc, q1, f, g, sig_q1, sig_q2, sig_f, sig_g, mu2, m0, sig0,
         name = "psvo_filter_backward_wobs_adaptive" if wobs else "psvo_filter_backward_adaptive"
         decisions = (_ptr(filt["rs"]),)
     if hb is not None:
-        if not (wobs and missing) or adaptive or ext:
+        if not (wobs and missing) or ext:
             raise ValueError("filter_backward: the bias rows hb belong to psvo_filter_backward_wobs_input -- the missing-observation "
-                             "route, resampling at every step or never, upstream gradient dlse only")
+                             "route, upstream gradient dlse only")
         _chk(hb[0], (T, B, H), "hb_q1"); _chk(hb[1], (T, B, H), "hb_f")
         if hb[0] is None or (not desc.bootstrap and hb[1] is None):
             raise ValueError("filter_backward_wobs_input needs hb_q1 and, unless bootstrap, hb_f")
-        name = "psvo_filter_backward_wobs_input"
-        decisions = (_ptr(hb[0]), None if desc.bootstrap else _ptr(hb[1]))
+        # (adaptive: the decisions filt["rs"], checked above, ahead of the rows)
+        name = "psvo_filter_backward_wobs_input_adaptive" if adaptive else "psvo_filter_backward_wobs_input"
+        decisions = decisions + (_ptr(hb[0]), None if desc.bootstrap else _ptr(hb[1]))
     sacc = z((lib.psvo_filter_wobs_ws_floats if wobs else lib.psvo_filter_ws_floats)(B, T, N, Dx, Dy))
     upstream = (_ptr(dlse),) if (wobs and not ext) else (_ptr(dlse), nparts, _ptr(dFm), _ptr(dlogW))
     with _fixed_order():
@@ -725,6 +738,12 @@ def filter_backward_wobs_input(*args, hb, **kw):
     filter_backward_wobs_missing: the reverse of filter_forward_wobs_input; arguments of filter_backward (dlse only) plus
     hb = (hb_q1, hb_f); the result also holds dhb_q1 / dhb_f."""
     return filter_backward(*args, wobs=True, missing=True, hb=hb, **kw)
+
+
+def filter_backward_wobs_input_adaptive(*args, hb, **kw):
+    """psvo_filter_backward_wobs_input_adaptive + the weight gradients of filter_backward_wobs_input: the reverse of
+    filter_forward_wobs_input_adaptive, following the decisions filt["rs"]; arguments and result of filter_backward_wobs_input."""
+    return filter_backward(*args, wobs=True, missing=True, adaptive="wobs", hb=hb, **kw)
 
 
 def filter_backward_wobs_missing_adaptive(*args, **kw):
@@ -847,19 +866,29 @@ def ffbs_sample(desc, filt, sig_f=None, u=None, idx_in=None):
     return out
 
 
-def particle_forecast(desc, K, f, g, sig_f, sig_g, X, logW=None, obs=None, eps=None, missing=False):
+def particle_forecast(desc, K, f, g, sig_f, sig_g, X, logW=None, obs=None, eps=None, missing=False, hb_f=None):
     """psvo_particle_forecast: the k-step predictive distribution, k = 0..K, of the weighted cloud `X` (T,B,Dx,N) at every origin.
     `f`, `g` are the MLP tuples of the transition and the emission at the kernels' width (one hidden layer), `sig_f` (Dx) and
     `sig_g` (Dy) their scales (sig_g may be None for the count emission).  `logW` (T,B,N) log-weights or None = equal weights,
     `obs` (T,B,Dy) or None = no predictive log-density, `eps` (K,T,B,Dx,N) standard normals or None = noise-free propagation.
     Returns dict(ymean, yvar (K+1,T,B,Dy), xmean (K+1,T,B,Dx), lpd (K+1,T,B) or None without obs; lpd is 0 where t + k >= T).
     missing: psvo_particle_forecast_missing -- a NaN in `obs` is an entry that was not observed, lpd sums the observed entries of
-    the target row and is 0 where that row has none.  Asynchronous on the launch stream."""
+    the target row and is 0 where that row has none.
+    hb_f (Tv,B,H), Tv >= T: psvo_particle_forecast_input -- the exogenous input's share of the first layer of `f` (whose W1 is then
+    the state's rows W1[:Dx]); the transition of horizon k from origin t adds hb_f[t+k,b,:] to b1, nothing where t + k >= Tv; rows
+    T .. Tv-1 are inputs planned past the data.  Observations are read as under `missing`.  Asynchronous on the launch stream."""
     lib = _lib.load()
     B, T, N, Dx, Dy, H = desc.B, desc.T, desc.N, desc.Dx, desc.Dy, desc.H
     K = int(K)
     if K < 0:
         raise ValueError("particle_forecast: K = %d horizons; K >= 0" % K)
+    Tv = T
+    if hb_f is not None:
+        Tv = int(hb_f.shape[0]) if hb_f.dim() == 3 else T
+        if Tv < T:
+            raise ValueError("hb_f must have shape (Tv, B, H) = (Tv, %d, %d) with Tv >= T = %d, got %s"
+                             % (B, H, T, tuple(hb_f.shape)))
+        _chk(hb_f, (Tv, B, H), "hb_f")
     if X is None:
         raise ValueError("particle_forecast needs the cloud X (T,B,Dx,N)")
     _chk(X, (T, B, Dx, N), "X"); _chk(logW, (T, B, N), "logW"); _chk(obs, (T, B, Dy), "obs")
@@ -873,9 +902,12 @@ def particle_forecast(desc, K, f, g, sig_f, sig_g, X, logW=None, obs=None, eps=N
     out = {"ymean": _empty(K + 1, T, B, Dy, device=dev), "yvar": _empty(K + 1, T, B, Dy, device=dev),
            "xmean": _empty(K + 1, T, B, Dx, device=dev), "lpd": _empty(K + 1, T, B, device=dev) if obs is not None else None}
     name = "psvo_particle_forecast_missing" if missing else "psvo_particle_forecast"
+    extra = ()
+    if hb_f is not None:
+        name, extra = "psvo_particle_forecast_input", (_ptr(hb_f), Tv)
     _launch(name, getattr(lib, name), ctypes.byref(desc), K, ctypes.byref(fs), ctypes.byref(gs),
             _ptr(sig_f), _ptr(sig_g), _ptr(X), _ptr(logW), _ptr(obs), _ptr(eps), _ptr(out["ymean"]), _ptr(out["yvar"]),
-            _ptr(out["xmean"]), _ptr(out["lpd"]), _stream())
+            _ptr(out["xmean"]), _ptr(out["lpd"]), *extra, _stream())
     return out
 
 

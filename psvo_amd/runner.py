@@ -118,7 +118,8 @@ def main(FLAGS):
                        backward_simulation=bool(FLAGS.PSVO or FLAGS.PSVOwR), output_cov=bool(FLAGS.output_cov), Dy=FLAGS.Dy,
                        wide_obs=bool(getattr(FLAGS, "resample_ess_wide_obs", False)),
                        layers=[FLAGS.q1_layers, FLAGS.g_layers] + ([] if FLAGS.use_bootstrap else [FLAGS.f_layers]),
-                       missing_obs=bool(getattr(FLAGS, "missing_obs", False) and getattr(FLAGS, "resample_ess_missing_obs", False)))
+                       missing_obs=bool(getattr(FLAGS, "missing_obs", False) and getattr(FLAGS, "resample_ess_missing_obs", False)),
+                       inputs=bool(getattr(FLAGS, "Di", 0) and getattr(FLAGS, "resample_ess_inputs", False)))
     check_missing_obs(bool(getattr(FLAGS, "missing_obs", False)), missing_rate=getattr(FLAGS, "missing_rate", 0.0),
                       backward_simulation=bool(FLAGS.PSVO or FLAGS.PSVOwR), resample_ess=getattr(FLAGS, "resample_ess", 0.0),
                       particle_forecast=bool(getattr(FLAGS, "particle_forecast", False)), output_cov=bool(FLAGS.output_cov),
@@ -132,7 +133,9 @@ def main(FLAGS):
     check_inputs(getattr(FLAGS, "Di", 0), backward_simulation=bool(FLAGS.PSVO or FLAGS.PSVOwR),
                  resample_ess=getattr(FLAGS, "resample_ess", 0.0), particle_forecast=bool(getattr(FLAGS, "particle_forecast", False)),
                  output_cov=bool(FLAGS.output_cov), Dy=FLAGS.Dy,
-                 layers=[FLAGS.q1_layers, FLAGS.g_layers] + ([] if FLAGS.use_bootstrap else [FLAGS.f_layers]))
+                 layers=[FLAGS.q1_layers, FLAGS.g_layers] + ([] if FLAGS.use_bootstrap else [FLAGS.f_layers]),
+                 particle_forecast_inputs=bool(getattr(FLAGS, "particle_forecast_inputs", False)),
+                 resample_ess_inputs=bool(getattr(FLAGS, "resample_ess_inputs", False)))
     if FLAGS.use_2_q:
         FLAGS.q_uses_true_X = False
     device = _device()

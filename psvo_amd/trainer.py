@@ -521,7 +521,7 @@ class trainer:
                     out["y_hat"] = [v.cpu().numpy() for v in y_hat]
                     out["y"] = [v.cpu().numpy() for v in y]
             if any(n.startswith("forecast_") for n in names):       # FLAGS.particle_forecast only
-                fc = self.SMC.particle_forecast(self.MSE_steps, log["Xs"], obs_d)
+                fc = self.SMC.particle_forecast(self.MSE_steps, log["Xs"], obs_d, **extra)
                 out["forecast_y_mean"] = fc["y_mean"].contiguous().cpu().numpy()      # (B, T, K+1, Dy)
                 out["forecast_y_var"] = fc["y_var"].contiguous().cpu().numpy()
                 out["forecast_lpd"] = fc["lpd"].contiguous().cpu().numpy()            # (B, T, K+1); 0 where t + k >= T
