@@ -14,8 +14,15 @@ gets that fp32 value cast back, so both sides use the same numbers.  The oracle 
 graph-attached log its get_log_ZSMC returns: lse = logsumexp(log_Ws, 1), logW = log_Ws, Fm (Fs) = f.mean (mean_and_sigma) of
 X_prevs, score = sum_t (f_log_probs + g_log_probs - bw_log_Omegas), lseW = logsumexp(bw_log_W, 1).  The oracle objects are the
 features' own (tests/adaptive_reference.py, wobs_adaptive_reference.py, missing_reference.py, missing_adaptive_reference.py,
-missing_bsim_reference.py, count_reference.py; O.OBJECTIVES for the plain and state-dependent-scale routes), and so are the masks,
-the count data and the layout of the forced resampling decisions.
+missing_bsim_reference.py, count_reference.py, exo_reference.py, exo_adaptive_reference.py; O.OBJECTIVES for the plain,
+state-dependent-scale and wide PSVO routes), and so are the masks, the count data, the exogenous inputs and the layout of the
+forced resampling decisions.
+
+The input families (FLAGS.Di: "input", "input_adaptive") have one more leaf on both sides, the input v (B, T, Di): the product
+gets it as an fp32 leaf, the references through InputOracle.  Besides the parameters (compare) their input rows W1[Dx:] are
+compared on their own and d v per sequence, each d v[b] at its own scale under the same two clauses, and wherever the reference
+has d v[b, t] exactly zero the bound is ATOL alone (input_rows, compare_inputs): these are the only routes that turn a
+cotangent into rows d hb[t, b, :], and a row written to another step or sequence lands where the reference has none.
 
 Comparison (compare): over test_gpu_parity._pairs, a missing gradient counting as zero, under the suite's rule for gradients --
 error <= 2e-3 x the reference tensor's largest entry + 1e-6 -- or else the K32 clause of tests/test_gpu_instantiations.py: error
@@ -24,7 +31,8 @@ cotangents make sums cancel, so the second clause binds more often than under th
 arithmetic, never against the kernel.  A model seed is fit for a case when the fp32 oracle itself stays inside the first clause
 on at least three quarters of the tensors (fp32_share_over; tests/test_vjp_host.py holds every case to it on the CPU).
 
-A helper, not a test; only tests and tools import it.
+140 cases in groups (a)-(k) (CASES below; tests/test_gpu_vjp.py runs them in 6.3 s on one MI355X).  A helper, not a test; only
+tests and tools import it.
 """
 import contextlib
 
@@ -33,6 +41,8 @@ import torch
 from oracle import psvo_oracle as O
 from tests import adaptive_reference as AR
 from tests import count_reference as CR
+from tests import exo_adaptive_reference as XA
+from tests import exo_reference as ER
 from tests import helpers as Hh
 from tests import missing_adaptive_reference as MA
 from tests import missing_bsim_reference as MB
@@ -56,14 +66,17 @@ FILTER_NODE = {
     "missing": ("FilterWobsMissingFunction", {"lse"}),
     "missing_adaptive": ("FilterWobsMissingAdaptiveFunction", {"lse"}),
     "missing_bsim": ("FilterWobsMissingBsimFunction", {"lse", "Fm", "logW"}),
+    "input": ("FilterWobsInputFunction", {"lse"}),
+    "input_adaptive": ("FilterWobsInputAdaptiveFunction", {"lse"}),
 }
 BSIM_NODE = {
     ("PSVO", "plain"): ("BsimFunction", "score"), ("PSVO", "cov"): ("BsimCovFunction", "score"),
-    ("PSVO", "missing_bsim"): ("BsimWobsMissingFunction", "score"),
+    ("PSVO", "missing_bsim"): ("BsimWobsMissingFunction", "score"), ("PSVO", "wide"): ("BsimWobsFunction", "score"),
     ("PSVOwR", "plain"): ("BsimWRFunction", "lseW"), ("PSVOwR", "cov"): ("BsimWRCovFunction", "lseW"),
 }
-ADAPTIVE = ("adaptive", "wide_adaptive", "missing_adaptive")
+ADAPTIVE = ("adaptive", "wide_adaptive", "missing_adaptive", "input_adaptive")
 MISSING = ("missing", "missing_adaptive", "missing_bsim")
+INPUT = ("input", "input_adaptive")     # FLAGS.Di > 0 (Case.flags carries Di): the exogenous input is a leaf on both sides
 
 
 class Case(object):
@@ -80,8 +93,12 @@ class Case(object):
     @property
     def id(self):
         parts = [self.route, self.obj, "N%d" % self.N, "Dx%d" % self.Dx, "Dy%d" % self.Dy, "+".join(self.cots)]
+        if self.flags.get("Di"):
+            parts.append("Di%d" % self.flags["Di"])
         if self.emission != GAUSS:
             parts.append(self.emission)
+        if self.flags.get("missing_obs"):
+            parts.append("missing")
         if self.hot is not None:
             parts.append("onehot_t%d_b%d" % self.hot)
         return "-".join(parts)
@@ -149,6 +166,21 @@ class Problem(object):
     pass
 
 
+class InputOracle(object):
+    """exo_reference.smc (ess_frac None) or exo_adaptive_reference.smc on the objective `o` and the inputs `v` (B, T, Di), in the
+    get_log_ZSMC(obs, noise) shape oracle_run expects.  Every run holds v as a fresh leaf of the run's dtype in .v, so that
+    .v.grad is d v once the surrogate has been differentiated."""
+
+    def __init__(self, o, v, ess_frac=None):
+        self.o, self.f, self.ess_frac, self._v, self.v = o, o.f, ess_frac, v, None
+
+    def get_log_ZSMC(self, obs, noise):
+        self.v = self._v.to(obs.dtype).cpu().clone().requires_grad_(True)
+        if self.ess_frac is None:
+            return ER.smc(self.o, obs, self.v, noise)
+        return XA.smc(self.o, obs, self.v, noise, self.ess_frac)
+
+
 def setup(case, device="cpu"):
     """tests/test_gpu_parity.py::_setup for `case` on `device` (same seeding), with the family's flags, data and reference"""
     from psvo_amd.model import SSM
@@ -176,6 +208,8 @@ def setup(case, device="cpu"):
         kw.update(resample_ess_missing_obs=True)
     if fam == "missing_bsim":
         kw.update(BSim_missing_obs=True)
+    if fam == "input_adaptive":
+        kw.update(resample_ess_inputs=True)
     if case.emission == COUNT:
         kw.update(count_emission=True)
     if case.emission == UNIT:
@@ -193,10 +227,11 @@ def setup(case, device="cpu"):
         p.obs = CR.counts(B, T, case.Dy, 100 + seed).double()
     p.noise = O.make_noise(Hh.oracle_flags(FLAGS, case.obj), B, T, seed=1234 + seed)
     p.e_never = None
-    if fam in MISSING:
+    if fam in MISSING or FLAGS.missing_obs:
         miss, _, p.e_never = mask(case.Dy, seed)
         p.obs = MR.knock_out(p.obs, miss)
     p.forced = forced_decisions() if fam in ADAPTIVE else None
+    p.inputs = ER.inputs(B, T, FLAGS.Di, seed) if fam in INPUT else None
     # the tuple the adaptive references read their emission from: (objective, .., flags at [9], ..)
     pseudo = (case.obj, B, T, case.N, case.Dx, case.Dy, hs, case.boot, case.two_q,
               {"count_emission": True} if case.emission == COUNT else {}, seed, TAU)
@@ -210,6 +245,8 @@ def setup(case, device="cpu"):
         p.objective = lambda P: MA.objective(P, FLAGS, pseudo)
     elif fam == "missing_bsim":
         p.objective = lambda P: MB.objective(P, FLAGS, case.obj)
+    elif fam in INPUT:
+        p.objective = lambda P: InputOracle(ER.objective(P, FLAGS, case.obj), p.inputs, TAU if fam in ADAPTIVE else None)
     elif case.emission == COUNT:
         p.objective = lambda P: CR.objective(P, FLAGS, case.obj)
     else:
@@ -254,11 +291,14 @@ def oracle_run(p, dtype=torch.float64, teacher=None):
 
 
 def oracle_vjp(p, cots, dtype=torch.float64, teacher=None):
-    """gradients of sum_k <cots[k], output k> in P's .grad; returns (P, teacher of this run, the outputs detached)"""
+    """gradients of sum_k <cots[k], output k> in P's .grad; returns (P, teacher of this run, the outputs detached).  On the
+    input families P["inputs"] is the run's input leaf (B, T, Di), its .grad d v"""
     P, o, _, log = oracle_run(p, dtype, teacher)
     outs = oracle_outputs(o, log, p.case.family)
     loss = sum((c.to(dtype) * outs[k]).sum() for k, c in cots.items())
     loss.backward()
+    if p.inputs is not None:
+        P["inputs"] = o.v
     return P, teacher_of(log), {k: v.detach() for k, v in outs.items()}
 
 
@@ -293,14 +333,16 @@ def differentiable_outputs(log, case):
 
 def product_vjp(p, cots, teacher):
     """the product's forward pass (model on the GPU) and .backward() on the surrogate, under the case's tuning switches;
-    the gradients are left in the model's .grad; returns the node outputs, detached"""
+    the gradients are left in the model's .grad; returns (the node outputs, detached; d v (B, T, Di) of the fp32 input leaf on
+    the input families, else None)"""
     from psvo_amd import _lib
     nz = hip_noise(p, teacher)
     p.model.zero_grad()
+    v = None if p.inputs is None else p.inputs.float().cuda().requires_grad_(True)
     with contextlib.ExitStack() as st:
         for key, value in p.case.tune:
             st.enter_context(Hh.tuning(getattr(_lib, key), value))
-        _, log = p.smc.get_log_ZSMC(p.obs.float().cuda(), None, noise=nz)
+        _, log = p.smc.get_log_ZSMC(p.obs.float().cuda(), None, noise=nz, **({} if v is None else {"inputs": v}))
         outs = differentiable_outputs(log, p.case)
         assert set(cots) <= set(outs), (sorted(cots), sorted(outs))
         loss = sum((c.cuda() * outs[k]).sum() for k, c in cots.items())
@@ -308,7 +350,7 @@ def product_vjp(p, cots, teacher):
         torch.cuda.synchronize()
     if p.case.obj == "PSVOwR" and p.case.family == "plain":
         p.smc.check_exchange()
-    return {k: v.detach() for k, v in outs.items()}
+    return {k: o.detach() for k, o in outs.items()}, (None if v is None else v.grad)
 
 
 def grad_rows(model, P, P_ref):
@@ -321,6 +363,60 @@ def grad_rows(model, P, P_ref):
         src = par if other is None else other[i][2]
         g = torch.zeros_like(ref) if src.grad is None else src.grad.detach().double().cpu().reshape(ref.shape)
         rows.append((name, float((g - r).abs().max()), max(float(r.abs().max()), 1e-6)))
+    return rows
+
+
+def input_rows(p, P, P_ref, dv=None):
+    """the rows an input family adds to grad_rows, same triples: the input rows W1[Dx:] of q1 (and of f, where it is its own
+    network) on their own, so that they do not hide behind the state block, and d v -- `dv` (B, T, Di) where P is the model, else
+    P["inputs"].grad -- per sequence, "inputs[b]" at the scale of the reference's d v[b].  The (t, b) rows that the reference has
+    exactly zero (the last step always: nothing reads v[:, T - 1]; under a one-hot cotangent whatever the entry does not depend
+    on) are taken out of their sequence and form one row of scale 0, whose first-clause bound is therefore ATOL alone."""
+    Dx = p.case.Dx
+    grad = lambda t: None if t is None or t.grad is None else t.grad.detach().double().cpu()
+    other = None if P is p.model else {n: t for n, _, t in _pairs(p.model, P)}
+    rows = []
+    for name, par, ref in _pairs(p.model, P_ref):
+        if name in ("q1.W0", "f.W0"):
+            r, g = grad(ref), grad(par if other is None else other[name])
+            r = torch.zeros_like(ref) if r is None else r
+            g = torch.zeros_like(ref) if g is None else g.reshape(ref.shape)
+            rows.append((name + "[Dx:]", float((g[Dx:] - r[Dx:]).abs().max()), max(float(r[Dx:].abs().max()), 1e-6)))
+    ref = grad(P_ref["inputs"])
+    ref = torch.zeros_like(P_ref["inputs"]) if ref is None else ref
+    got = grad(P["inputs"]) if other is not None else (None if dv is None else dv.detach().double().cpu())
+    d = ((torch.zeros_like(ref) if got is None else got) - ref).abs()
+    zero = (ref == 0).all(-1)                                            # (B, T)
+    assert bool(zero[:, T - 1].all())
+    for b in range(B):
+        if not bool(zero[b].all()):
+            rows.append(("inputs[%d]" % b, float(d[b][~zero[b]].max()), float(ref[b].abs().max())))
+    rows.append(("inputs[where the reference is exactly 0]", float(d[zero].max()), 0.0))
+    return rows
+
+
+def compare_inputs(p, P, dv, yardstick, subject=None):
+    """compare() for input_rows: the product's (p.model's .grad and `dv`; or the oracle layout `subject`) against the fp64
+    oracle's P under the same two clauses, the fp32 oracle's own error on the same block being the yardstick of the second;
+    the block the reference has exactly zero is held to ATOL alone.  Under the random cotangent the reference's d v must be
+    non-zero on every sequence, and so must its input rows."""
+    rows = input_rows(p, p.model if subject is None else subject, P, dv)
+    if p.case.hot is None:
+        assert {n for n, _, _ in rows} >= {"inputs[%d]" % b for b in range(B)}, rows
+        assert all(s > 1e-6 for n, _, s in rows if n.endswith("[Dx:]")), rows
+    assert ("f.W0[Dx:]" in {n for n, _, _ in rows}) == (not p.case.boot) and rows[0][0] == "q1.W0[Dx:]"
+    over = [r for r in rows if not r[1] <= RTOL * r[2] + ATOL]
+    second = []
+    if over:
+        err32 = {n: e for n, e, _ in input_rows(p, yardstick(), P)}
+        second = [(n, e, s, err32[n]) for n, e, s in over]
+    bad = [r for r in second if r[2] == 0.0 or not r[1] <= K32 * r[3]]
+    worst = max((r for r in rows if r[2] > 0.0), key=lambda r: r[1] / r[2])
+    print("VJP %s, input rows and d v: worst error / largest entry %.3e (%s); error where the reference is exactly 0 %.3e; "
+          "%d of %d blocks on the fp32 yardstick%s" % (
+              p.case.id, worst[1] / worst[2], worst[0], rows[-1][1], len(over), len(rows),
+              "".join("; %s err %.3e fp32-oracle err %.3e" % (n, e, e32) for n, e, _, e32 in second)))
+    assert not bad, "input-gradient mismatch (name, max abs err, largest entry, fp32 oracle's own err): %s" % bad
     return rows
 
 
@@ -434,10 +530,45 @@ G_CASES = [
     Case("bsimwr_cov", "PSVOwR", 8, 2, 1, family="cov", cots=("lseW",), M=4, H=16),
     Case("bsimwr_cov_ws_deterministic", "PSVOwR", 8, 2, 1, family="cov", cots=("lseW",), M=4, H=16, tune=[DET]),
 ]
+# (i) the input-driven filter (FLAGS.Di): the only route that turns a cotangent into rows d hb[t, b, :], which torch folds into
+# d W1[Dx:] and d v.  (obj, N, Dx, Dy, H, Di, ...) as tests/exo_reference.CASES
+_INPUT_SHAPES = [
+    ("AESMC", 16, 2, 1, 16, 1, {}),                              # smallest everything
+    ("AESMC", 16, 2, 1, 16, 16, {}),                             # Di = H: W1[Dx:] is square, no unit of d hb hides in the projection
+    ("SVO", 16, 2, 3, 64, 2, dict(boot=False)),                  # one wave stages 2 H = 128 bias words; separate f (dhb_f)
+    ("SVO", 40, 3, 2, 32, 3, dict(boot=False)),                  # partly filled wave
+    ("SVO", 17, 2, 2, 24, 2, dict(boot=False)),                  # H = 24 at kernel width 32: padded columns of hb / d hb
+    ("IWAE", 24, 4, 17, 64, 2, dict(two_q=False)),               # reverse step without an inner barrier
+    ("AESMC", 100, 3, 10, 32, 2, dict(emission=COUNT)),
+]
+
+
+def _input_case(route, family, obj, N, Dx, Dy, H, Di, kw, **flags):
+    return Case(route, obj, N, Dx, Dy, family=family, H=H, flags=dict(Di=Di, **flags), **kw)
+
+
+I_CASES = [_input_case("filter_wobs_input", "input", *s) for s in _INPUT_SHAPES] + [
+    _input_case("filter_wobs_input", "input", *_INPUT_SHAPES[3], missing_obs=True)]     # never-observed column stays exactly 0
+# (j) the same under adaptive resampling, decisions forced and mixed: the !rs_here chain through d lnw besides
+J_CASES = [_input_case("filter_wobs_input_adaptive", "input_adaptive", *_INPUT_SHAPES[i]) for i in (0, 1, 3, 4, 6)]
+# (k) PSVO on wide observations (FLAGS.BSim_wide_obs, Dy 3..32): the static compilation of the reverse backward simulation and
+# the _ext reverse filter behind it.  (N, Dx, Dy, M, H, ...) as tests/test_gpu_wobs_bsim.CASES
+_WIDE_BSIM = dict(family="wide", cots=("score",), flags=dict(BSim_wide_obs=True))
+K_CASES = [Case("bsim_wobs_static", "PSVO", N, Dx, Dy, M=M, H=H, **{**_WIDE_BSIM, **kw}) for N, Dx, Dy, M, H, kw in (
+    (16, 2, 3, 4, 16, {}),
+    (40, 3, 10, 8, 32, dict(boot=False)),
+    (24, 3, 32, 32, 64, {}),
+    (130, 4, 17, 4, 64, dict(boot=False)),
+    (24, 2, 5, 8, 32, dict(two_q=False)),
+    (16, 2, 10, 8, 32, dict(emission=UNIT)),
+    (40, 3, 10, 8, 32, dict(emission=COUNT)),
+    # the _ext reverse filter gets the backward simulation's gradients and a direct cotangent together
+    (16, 2, 3, 4, 16, dict(cots=("score", "lse", "Fm", "logW"))),
+)]
 # (h) one-hot cotangents at (t0, B - 1), t0 in {0, 1, T - 1}: a single misplaced read moves the whole gradient
 _FIRST_MISSING_COUNT = next(c for c in E_CASES if c.family == "missing" and c.emission == COUNT)
-H_CASES = [c.one_hot_at(t0) for c in (A_CASES[0], C_CASES[0], D_CASES[0], _FIRST_MISSING_COUNT, G_CASES[0])
+H_CASES = [c.one_hot_at(t0) for c in (A_CASES[0], C_CASES[0], D_CASES[0], _FIRST_MISSING_COUNT, G_CASES[0], I_CASES[0], J_CASES[0])
            for t0 in (0, 1, T - 1)]
 
-CASES = A_CASES + B_CASES + C_CASES + D_CASES + E_CASES + F_CASES + G_CASES + H_CASES
+CASES = A_CASES + B_CASES + C_CASES + D_CASES + E_CASES + F_CASES + G_CASES + I_CASES + J_CASES + K_CASES + H_CASES
 assert len({c.id for c in CASES}) == len(CASES)
