@@ -104,7 +104,9 @@ DEPTH_CASES = [
 ]
 
 
-def _setup(obj, B, T, N, M, Dx, Dy, H, bootstrap, two_q, seed=0, **extra):
+def _setup(obj, B, T, N, M, Dx, Dy, H, bootstrap, two_q, seed=0, device="cuda", **extra):
+    """(device="cpu": the same model, objective, observations and draws on the host, for the tests that judge a case by its
+    reference alone -- tests/test_wide_instantiations_host.py)"""
     from psvo_amd.model import SSM
     from psvo_amd.SMC.SVO import SVO
     from psvo_amd.SMC.PSVO import PSVO
@@ -119,7 +121,7 @@ def _setup(obj, B, T, N, M, Dx, Dy, H, bootstrap, two_q, seed=0, **extra):
     kw.update(extra)
     FLAGS = Hh.make_flags(obj, **kw)
     torch.manual_seed(seed)
-    model = Hh.perturb_(SSM(FLAGS)).cuda()
+    model = Hh.perturb_(SSM(FLAGS)).to(device)
     smc = cls(model, FLAGS)
     g = torch.Generator().manual_seed(100 + seed)
     obs = torch.randn(B, T, Dy, generator=g, dtype=torch.float64) * 1.5
